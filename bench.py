@@ -30,7 +30,9 @@ Every roofline block carries, beside the algorithmic-bytes HBM roofline the metr
 of SURVEY 8(d) against the 157.3 TF fp32 vector peak -- what the counters say bounds these kernels) and
 `hbm_measured_frac` (PMC-measured HBM bytes / kernel time / 8 TB/s).
 
-    python bench.py                       # 1 GPU, headline + all config blocks, finishes in minutes
+    python bench.py                       # 1 GPU, the headline workload alone: set up, warm up, time, print the line
+    python bench.py --full                # ... and everything below: all config blocks, checks, CPU baseline, traffic; minutes
+    python bench.py --dump-outputs DIR    # also write what the last timed step computed (a fixed sample) as DIR/*.npy
     python bench.py --config 5 --no-extras --steps 1      # one config as the headline (profiling passes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
@@ -249,6 +251,26 @@ def device_magnitudes(torch, dev, B, T, F, first_seed):
         im = torch.randn((T, F), generator=g, device=dev)
         out[b] = torch.sqrt(re * re + im * im)
     return out, "torch.randn on the device (Philox, seed 20260928)"
+
+
+def dump_outputs(torch, path, state, budget=32 << 20, seed=0):
+    """--dump-outputs: what the timed step hands its caller -- the (B, T, F) complex64 state batch_dev leaves in place -- as float32
+    [re, im] pairs: DIR/spectrograms.npy (k, T, F, 2) with the batch positions in DIR/spectrogram_index.npy.  A state larger than
+    `budget` bytes is sampled, the same way every run (numpy default_rng(seed)): whole spectrograms, or frames (DIR/frames.npy
+    (k, F, 2), DIR/frame_index.npy = b * T + t) when one spectrogram alone is larger."""
+    B, T, F = state.shape
+    rng = np.random.default_rng(seed)
+    os.makedirs(path, exist_ok=True)
+    if T * F * 8 <= budget:
+        name, rows = "spectrogram", state
+    else:
+        name, rows = "frame", state.reshape(B * T, F)
+    n = rows.shape[0]
+    k = min(n, budget // (rows[0].numel() * 8))
+    idx = np.arange(n) if k == n else np.sort(rng.choice(n, size=k, replace=False))
+    got = rows if k == n else rows[torch.from_numpy(idx).to(state.device)]
+    np.save(os.path.join(path, name + "s.npy"), torch.view_as_real(got).cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
 
 
 def physical_cores():
@@ -685,6 +707,11 @@ def main():
     ap.add_argument("--no-default-schedule", action="store_true")
     ap.add_argument("--no-traffic-pass", action="store_true", help="do not measure roofline.traffic with rocprofv3 --pmc child runs (the committed profile is quoted instead)")
     ap.add_argument("--force-generic", action="store_true")
+    ap.add_argument("--full", action="store_true", help="beside the headline: the extra config blocks, the result checks, the CPU baseline, the "
+                                                       "measured HBM traffic and copy rate, the residual all-reduce and the extra file (the --no-* "
+                                                       "and --extras options apply here); a plain run times the headline and prints its line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (rank 0's "
+                                                                        "state, a fixed sample of at most 32 MB) as float32 DIR/*.npy")
     ap.add_argument("--extra-file", default=None, help="where the full (non-contract) results go (default: gpurun_out/bench_extra.json if "
                                                        "that directory exists, else ./bench_extra.json)")
     args = ap.parse_args()
@@ -832,7 +859,19 @@ def main():
 
     # ---- headline ---------------------------------------------------------------------------------------------------
     head, (p, plan, mags, state) = run_batch_config(args.config, args.steps, args.warmup, schedule=args.schedule,
-                                                    B=args.batch, T=args.frames, iters=args.iters)
+                                                    B=args.batch, T=args.frames, iters=args.iters, checks=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, state)
+    if not args.full:
+        # a plain run ends here: the headline figure and nothing else
+        if rank == 0:
+            head["fshift"] = p.fshift
+            print(final_line(head, world, args.steps, args.warmup, p.fsize, head["roofline"], None,
+                             notes="headline only; bench.py --full adds the extra configs, checks, CPU baseline and measured traffic"))
+            sys.stdout.flush()
+        if world > 1:
+            dist.destroy_process_group()
+        return
     B, T, F, iters = head["batch_per_gpu"], head["frames"], head["bins"], head["iters"]
     roof = dict(head["roofline"])
     extra = {"headline_checks": head.get("checks")}

@@ -300,10 +300,38 @@ def fftsize():
     print("fftsize.npz", os.path.getsize(os.path.join(HERE, "fftsize.npz")))
 
 
+def kernels():
+    """The reference's LWSanyQ kernel, 3 sweeps on random shapes (Q = 4, 2, 8, 3; T = 5, 11), with the extended buffers it started
+    from (`python make_golden.py kernels` writes only reference_kernels.npz; test_oracle.py's live comparison reads it)."""
+    from oracle.oracle import RefLib, build as build_oracle
+    build_oracle()
+    rl = RefLib()
+    h = np.load(os.path.join(HERE, "helpers.npz"))
+    rng = np.random.default_rng(7)
+    out = {"thr": np.array(0.5), "sweeps": np.array(3)}
+    for tag, Q in (("64_16", 4), ("64_32", 2), ("64_8", 8), ("48_16", 3)):
+        F = int(tag.split("_")[0]) // 2 + 1
+        W = h[f"W_{tag}"]
+        L = W.shape[2] - 1
+        for T in (5, 11):
+            k = f"{tag}_T{T}"
+            S = rng.standard_normal((T, F)) + 1j * rng.standard_normal((T, F))
+            er, ei = rl.extend(S, L, Q)
+            out[f"S_{k}"], out[f"ext_{k}"] = S, er + 1j * ei
+            amp = np.ascontiguousarray(np.abs(er + 1j * ei))
+            for _ in range(int(out["sweeps"])):
+                rl.call("LWSanyQ", er, ei, W, amp, F, T, L, Q, float(out["thr"]))
+            out[f"out_{k}"] = er + 1j * ei
+    np.savez_compressed(os.path.join(HERE, "reference_kernels.npz"), **out)
+    print("reference_kernels.npz", os.path.getsize(os.path.join(HERE, "reference_kernels.npz")))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "extra":
         extra()
     elif len(sys.argv) > 1 and sys.argv[1] == "fftsize":
         fftsize()
+    elif len(sys.argv) > 1 and sys.argv[1] == "kernels":
+        kernels()
     else:
         main()

@@ -193,3 +193,22 @@ def test_traffic_profile_of_another_kernel_is_refused(tmp_path, monkeypatch):
     monkeypatch.undo()
     t, src = bench.load_traffic("systolic_q4_l5_hann", "2")
     assert t and t > 1e10
+
+
+def test_dump_outputs_writes_a_fixed_bounded_sample(tmp_path):
+    """--dump-outputs (bench.dump_outputs): float32 [re, im] of the state the timed step leaves, within the byte budget -- whole
+    spectrograms, or frames when one spectrogram alone is over it -- the same sample every time, each row the state's own."""
+    import torch
+    g = torch.Generator().manual_seed(0)
+    st = torch.complex(torch.randn(7, 50, 33, generator=g), torch.randn(7, 50, 33, generator=g))
+    cases = ((1 << 20, "spectrogram", 7), (40000, "spectrogram", 3), (5000, "frame", 18))
+    for budget, name, k in cases:
+        for rep in ("a", "b"):
+            bench.dump_outputs(torch, str(tmp_path / ("%d%s" % (budget, rep))), st, budget=budget)
+        d = tmp_path / ("%da" % budget)
+        got, idx = np.load(d / (name + "s.npy")), np.load(d / (name + "_index.npy"))
+        assert got.dtype == np.float32 and idx.dtype == np.float64 and got.nbytes <= budget and len(idx) == k
+        rows = st.numpy() if name == "spectrogram" else st.numpy().reshape(-1, 33)
+        assert np.array_equal(got[..., 0] + 1j * got[..., 1], rows[idx.astype(int)])
+        assert np.array_equal(np.load(tmp_path / ("%db" % budget) / (name + "s.npy")), got)
+        assert sorted(os.listdir(d)) == [name + "_index.npy", name + "s.npy"]

@@ -99,7 +99,7 @@ def test_two_ranks_shard_the_engine():
     assert got[0][5:8] == got[1][5:8]          # every rank holds the same reduced pair
 
 
-def test_bench_py_runs_its_multi_rank_branch():
+def test_bench_py_runs_its_multi_rank_branch(tmp_path):
     """bench.py's own N > 1 branch (sharding through lws_amd/dist.py, barrier + max-over-ranks timing, the residual all-reduce,
     the config-4 shard block) under the launcher the driver uses -- torch.distributed.run, 2 ranks -- on the single GPU of the
     test box: LWS_BENCH_BACKEND=gloo puts the two all-reduces on CPU tensors and lets the ranks share the GPU.  No scaling
@@ -109,8 +109,7 @@ def test_bench_py_runs_its_multi_rank_branch():
     env = dict(os.environ, LWS_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--extra-file", os.path.join(ROOT, "gpurun_out", "bench_extra_2ranks.json")]
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
+           "--full", "--no-cpu-baseline", "--extra-file", str(tmp_path / "bench_extra_2ranks.json")]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -128,7 +127,7 @@ def test_bench_py_runs_its_multi_rank_branch():
     assert ex["headline_checks"]["max_rel_magnitude_error"] < 1e-6
 
 
-def test_bench_py_starts_its_own_ranks():
+def test_bench_py_starts_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` exactly as the driver starts N = 1 -- no launcher, no MASTER_* / RANK / WORLD_SIZE in the
     environment: bench.py starts its two ranks itself (bench.self_launch) and the launcher's last stdout line is rank 0's JSON
     line.  One GPU here, so LWS_BENCH_BACKEND=gloo lets the ranks share it."""
@@ -136,9 +135,8 @@ def test_bench_py_starts_its_own_ranks():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("MASTER_ADDR", "MASTER_PORT", "RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE")}
     env["LWS_BENCH_BACKEND"] = "gloo"
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras",
-           "--extra-file", os.path.join(ROOT, "gpurun_out", "bench_extra_selflaunch.json")]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extras",
+           "--extra-file", str(tmp_path / "bench_extra_selflaunch.json")]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     last = out.stdout.rstrip().splitlines()[-1]

@@ -1,8 +1,8 @@
 """CPU: pins the fp64 C restatement (oracle/lws_oracle.c) against the reference.
 
-Sources of truth: (a) golden vectors generated from the reference (tests/golden/make_golden.py),
-(b) oracle/_ref/liblws_ref.so = the reference's lwslib.cpp compiled in place (skipped if absent).  That library is git-ignored but
-    travels to the GPU box with the snapshot -- for bench.py's cpu_baseline leg only (kind: "reference"); no -m gpu test loads it.
+Sources of truth: golden vectors generated from the reference (tests/golden/make_golden.py), among them the outputs of its
+own kernels on random shapes (reference_kernels.npz, from the reference's lwslib.cpp compiled into oracle/_ref/liblws_ref.so).
+No test loads that library: it serves bench.py's cpu_baseline leg only (kind: "reference").
 Tolerance: the restatement re-associates fp64 sums (one canonical kernel instead of the reference's
 Q2/Q4 specialisations), and a bin whose weighted sum nearly cancels amplifies that by 1/|acc|; the
 reference's own Q2/Q4 kernels differ from its anyQ kernels by up to 1e-9 in the same way
@@ -144,24 +144,26 @@ def test_general_weights_periodic_row(oracle, tag):
     assert np.abs(out - ref).max() < ATOL_MULTI
 
 
-def test_against_compiled_reference_live(oracle, reflib):
-    """Random shapes straight against the reference's kernels (only where /root/reference was built)."""
-    h = load_golden("helpers.npz")
-    rng = np.random.default_rng(7)
+def test_against_compiled_reference_live(oracle):
+    """Random shapes straight against the reference's kernels: its ExtendSpec and 3 sweeps of LWSanyQ on the same inputs, stored
+    by tests/golden/make_golden.py kernels (reference_kernels.npz)."""
+    h, g = load_golden("helpers.npz"), load_golden("reference_kernels.npz")
+    thr, sweeps = float(g["thr"]), int(g["sweeps"])
     for tag, Q in (("64_16", 4), ("64_32", 2), ("64_8", 8), ("48_16", 3)):
         F = int(tag.split("_")[0]) // 2 + 1
         W = h[f"W_{tag}"]
         L = W.shape[2] - 1
         for T in (5, 11):
-            S = rng.standard_normal((T, F)) + 1j * rng.standard_normal((T, F))
-            thr = 0.5
-            er, ei = reflib.extend(S, L, Q)
+            k = f"{tag}_T{T}"
+            S, ext, ref = g[f"S_{k}"], g[f"ext_{k}"], g[f"out_{k}"]
+            assert S.shape == (T, F)
+            er, ei = oracle.extend(S, L, Q)
+            assert np.array_equal(er + 1j * ei, ext)
             amp = np.ascontiguousarray(np.abs(er + 1j * ei))
-            oer, oei = er.copy(), ei.copy()
-            for _ in range(3):
-                reflib.call("LWSanyQ", er, ei, W, amp, F, T, L, Q, thr)
+            oer, oei = np.ascontiguousarray(ext.real), np.ascontiguousarray(ext.imag)
+            for _ in range(sweeps):
                 oracle.sweep(oer, oei, W, amp, F, T, L, Q, thr, M0=M0_ALL)
-            assert np.abs(er - oer).max() < ATOL_MULTI and np.abs(ei - oei).max() < ATOL_MULTI
+            assert np.abs(ref.real - oer).max() < ATOL_MULTI and np.abs(ref.imag - oei).max() < ATOL_MULTI
 
 
 def test_config3_and_config5_fingerprints(oracle):

@@ -23,7 +23,7 @@ def find(con, prefix):
     return None
 
 
-for sub, suffix, what in (("trace", "", "python bench.py --steps 3 --warmup 1 --no-cpu-baseline  (MI355X; the default bench command: headline config 2 + every extra config block"),
+for sub, suffix, what in (("trace", "", "python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline  (MI355X; the full bench command: headline config 2 + every extra config block"),
                           ("trace_headline", "_headline", "python bench.py --steps 5 --warmup 1 --no-extras --no-cpu-baseline  (MI355X; the headline workload alone: BASELINE config 2, 256 x 500 x 513, 100 dense sweeps")):
     con = db(sub)
     if not con:
@@ -41,7 +41,7 @@ for sub, suffix, what in (("trace", "", "python bench.py --steps 3 --warmup 1 --
 SHAPES = {"2": (256, 500, 513, 100, 20.0), "2-T1024": (256, 1024, 513, 100, 20.0), "2-q2": (256, 500, 513, 100, 20.0), "2-q8": (256, 500, 513, 100, 20.0), "2-f501": (256, 500, 501, 100, 20.0), "2-f257": (512, 500, 257, 100, 20.0), "2-q3": (256, 500, 385, 100, 20.0), "2-frac": (256, 500, 513, 100, 20.0), "2-speech": (512, 500, 201, 100, 20.0), "2-q5": (256, 500, 501, 40, 20.0), "2-q8w": (256, 500, 1025, 20, 20.0), "2-q16": (256, 500, 513, 10, 20.0), "2-l8": (256, 500, 513, 40, 20.0), "4shard": (1024, 500, 513, 100, 20.0),
           "5": (64, 56250, 1025, 200, 20.0), "5-f16": (64, 56250, 1025, 200, 10.0)}
 res = {"_how": "rocprofv3 --kernel-trace --pmc FETCH_SIZE and, in a separate pass, --pmc WRITE_SIZE -- python bench.py --config <cfg> "
-               "--no-extras --steps 1 --warmup 1 --no-cpu-baseline (config 3: --extras 3); counters are KiB per dispatch. "
+               "--no-extras --steps 1 --warmup 1 --no-cpu-baseline (config 3: --full --extras 3); counters are KiB per dispatch. "
                "MI355X_MICROARCH.md (HBM section): on gfx950 FETCH_SIZE tallies 128-B requests at 64 B, i.e. reports 1/2 of the "
                "bytes -> doubled here; WRITE_SIZE is exact.  hbm_bytes_per_launch = (2 FETCH_SIZE + WRITE_SIZE) * 1024 of the LAST "
                "launch of the update kernel (the timed step; the warm-up launch of the big shapes runs 3 sweeps only); the band engine launches "

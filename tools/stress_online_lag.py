@@ -1,7 +1,7 @@
 """Random shapes of the online stage: the default (smallest) lag between sweeps against LWS_ONLINE_LAG_PLUS=1, 2, 3, bit for bit.
     python tools/stress_online_lag.py [cases]     (GPU; tests/test_gpu_online_lag.py is the short version)"""
 import os, sys, subprocess, numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if len(sys.argv) > 1 and sys.argv[1] == "run":
     import lws_amd
     tag, n = sys.argv[2], int(sys.argv[3])
