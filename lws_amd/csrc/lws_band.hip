@@ -194,14 +194,9 @@ __global__ void __launch_bounds__(256) k_band_store(typename cx<real>::type *sta
 template <typename real, int LT, int QT, bool EXACT, int NH, int MAXT>
 hipError_t launch_pass(const BArgs<real> &a, int B, hipStream_t stream) {
     using C = typename cx<real>::type;
-    static std::atomic<unsigned long long> done{0};
     const size_t lds = (size_t)a.nsl * (ring_bytes(a.g, sizeof(C)) + mail_bytes(a.g, NH, sizeof(C))) + table_bytes(a.g, LT, sizeof(C));
-    int dev = 0;
-    if (attr_needed(done, &dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_band<real, LT, QT, EXACT, NH, MAXT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done(done, dev);
-    }
+    const hipError_t e = allow_dynamic_lds<&k_band<real, LT, QT, EXACT, NH, MAXT>>((int)LDS_BYTES);
+    if (e != hipSuccess) return e;
     k_band<real, LT, QT, EXACT, NH, MAXT><<<dim3(B), dim3(a.g.nls * a.nsl * (1 + NH)), lds, stream>>>(a);
     return hipGetLastError();
 }
@@ -244,11 +239,6 @@ inline int helpers_of(bool fp64, int LT, int Q) {
     return 0;
 }
 inline int max_threads(bool fp64, int LT, int QT, int helpers) { return fp64 ? 256 : ((helpers || (LT == 5 && QT == 8)) ? 512 : 256); }
-
-int env_i(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
-}
 
 // Every row of W the twiddle image of row 0 to `tol` of the largest weight?  (weights_twiddle accepts 1e-9: enough to choose an
 // engine whose arithmetic is fp32; an fp64 plan promises the reference's values to rounding.)
@@ -297,11 +287,11 @@ bool band_plan(bool fp64, int B, int F, int T, int L, int Q, int Qp, int update,
     if (!rows_are_twiddles(W, Q, Qp, L, Pt, s, fp64 ? 1e-13 : 1e-9)) return false;
     const size_t csize = fp64 ? 16 : 8;
     // (LWS_BAND_NO_HELPERS=1: the exact builds' one-wave-per-slot variant -- comparison runs)
-    const int helpers = env_i("LWS_BAND_NO_HELPERS", 0) ? 0 : helpers_of(fp64, LT, Q);
+    const int helpers = env_int("LWS_BAND_NO_HELPERS", 0) ? 0 : helpers_of(fp64, LT, Q);
     const int maxt = max_threads(fp64, LT, QT, helpers);
     BandPlan best{};
     double best_cost = 1e300;
-    const int skw_force = env_i("LWS_BAND_SKW", 0), nls_force = env_i("LWS_BAND_NLS", 0), ns_force = env_i("LWS_BAND_NS", 0);   // (tests)
+    const int skw_force = env_int("LWS_BAND_SKW", 0), nls_force = env_int("LWS_BAND_NLS", 0), ns_force = env_int("LWS_BAND_NS", 0);   // (tests)
     for (int nls = 64; nls * (1 + helpers) <= maxt; nls *= 2) {
         if (nls_force && nls != nls_force) continue;
         for (int SKW = LT + 2; SKW <= LT + 2 + 10; ++SKW) {
@@ -328,7 +318,7 @@ bool band_plan(bool fp64, int B, int F, int T, int L, int Q, int Qp, int update,
     // spectrograms that go through the skewed scratch at a time: at most 32 GiB of it (LWS_BAND_CHUNK: for tests)
     const size_t per = (size_t)best.g.rows * best.g.nls * (csize + csize / 2);
     int chunk = (int)std::min<size_t>((size_t)std::max(B, 1), std::max<size_t>(1, ((size_t)32 << 30) / per));
-    const int cf = env_i("LWS_BAND_CHUNK", 0);
+    const int cf = env_int("LWS_BAND_CHUNK", 0);
     if (cf > 0) chunk = std::min(chunk, cf);
     best.chunk = chunk;
     best.state_bytes = (size_t)chunk * best.g.rows * best.g.nls * csize;

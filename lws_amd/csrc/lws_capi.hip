@@ -1,6 +1,5 @@
-// lws_capi.hip -- the extern "C" boundary declared in include/lws_hip.h: plan management, buffer
-// ownership, dispatch between the generic order-exact kernel and the systolic batch kernel, and
-// HIP-event timing of the update kernels.
+// lws_capi.hip -- the extern "C" boundary declared in include/lws_hip.h: plan management, buffer ownership, the choice of the
+// engine that runs each stage (choose_engine) and HIP-event timing of the update kernels.
 #include "../../include/lws_hip.h"
 
 #include <algorithm>
@@ -257,7 +256,7 @@ int ensure_scratch(lws_plan *p, int B, int T, int n_thr) {
     return LWS_OK;
 }
 
-int env_int(const char *name, int dflt);
+using lws::env_int;
 
 void begin_timing(lws_plan *p, hipStream_t s) {
     (void)hipEventRecord(p->ev0, s);
@@ -268,7 +267,187 @@ void end_timing(lws_plan *p, hipStream_t s) {
     p->timing_pending = true;
 }
 
-// One stage on the extended device buffers: thresholds -> scaled table -> update kernel.
+// ---- which engine runs a stage ------------------------------------------------------------------------------------------------
+// The engines in the order they are tried: a stage goes to the first whose guard holds.
+enum class Engine { Systolic, TeamFirst, OnlineLds, NofutureLds, Online64, Sys64, Band, GenericSkew, Team, Generic };
+
+struct Stage {
+    int mode;   // lws::Mode, after the Q4-compat rewrite
+    int wsel, B, T, iters, LA;
+};
+
+Stage stage_of(const lws_plan *p, int mode, int wsel, int B, int T, int iters, int LA) {
+    if (mode == lws::MODE_NOFUTURE && (p->flags & LWS_NOFUTURE_Q4_COMPAT) && p->Q == 4 && p->Qp == 4) mode = lws::MODE_NOFUTURE_Q4_COMPAT;
+    return {mode, wsel, B, T, iters, LA};
+}
+
+struct Route {
+    Engine engine = Engine::Generic;
+    bool ordered = false;    // team engine: the online stage on its order-exact kernel
+    bool one_wave = false;   // online64: the one-wave kernel
+    lws::BandPlan bp{};      // band engine
+};
+
+// The engine of a stage: the first one, from `from` on, whose guard holds.  The routing switches (comparison runs) are read once per call:
+//   LWS_TEAM_FIRST=1     the team engine before the LDS engines of the online / no-future stages
+//   LWS_TEAM_FP64=1      fp64 plans: the team engine's re-associating kernels, and its no-future sweeps
+//   LWS_TEAM_ORDERED=1   fp32 plans: the team engine's order-exact online kernel
+//   LWS_NO_TEAM=1, LWS_NO_TEAM_Q8=1 (the online stage of an fp64 plan of Q = 8 on online64), LWS_NO_SYS64=1, LWS_ONLINE64_ONE_WAVE=1
+//   LWS_ONLINE_SERIAL_TAPS=1, LWS_NOFUTURE_SERIAL_TAPS=1: the verification variants of the LDS engines, which promise the generic
+//   engine's bits -- a stage they do not take skips the team engine too
+Route choose_engine(const lws_plan *p, const Stage &st, Engine from = Engine::Systolic) {
+    const int mode = st.mode, F = p->F, T = st.T, L = p->L, Q = p->Q, Qp = p->Qp, LA = st.LA, n = st.iters;
+    const bool fp64 = p->fp64, generic = p->flags & LWS_FORCE_GENERIC, plain = p->flags & LWS_GENERIC_PLAIN_LAYOUT;
+    const bool batch = mode == lws::MODE_BATCH, online = mode == lws::MODE_ONLINE;
+    const bool nofuture = mode == lws::MODE_NOFUTURE || mode == lws::MODE_NOFUTURE_Q4_COMPAT;
+    const bool team_first = env_int("LWS_TEAM_FIRST", 0), team_fp64 = env_int("LWS_TEAM_FP64", 0), no_team = env_int("LWS_NO_TEAM", 0),
+               no_team_q8 = env_int("LWS_NO_TEAM_Q8", 0), no_sys64 = env_int("LWS_NO_SYS64", 0),
+               online_serial = env_int("LWS_ONLINE_SERIAL_TAPS", 0), nofuture_serial = env_int("LWS_NOFUTURE_SERIAL_TAPS", 0);
+    Route r;
+    // (fp64 plans: the online and no-future recursions amplify the rounding of a re-associated sum by 5-10 per frame -- equally valid
+    //  phases, but not the reference's numbers an fp64 plan exists to reproduce.  Their online stage runs on the team engine's
+    //  ORDER-EXACT kernel (increments by many lanes, the sum by one, in the reference's order: the generic engine's bits); the
+    //  re-associating kernels, and no-future sweeps, only with LWS_TEAM_FP64=1.)
+    r.ordered = online && (fp64 ? !team_fp64 : env_int("LWS_TEAM_ORDERED", 0) != 0);
+    r.one_wave = env_int("LWS_ONLINE64_ONE_WAVE", 0) != 0;
+    auto pick = [&](Engine e) { r.engine = e; return r; };
+    auto at = [&](Engine e) { return from <= e; };
+    auto team = [&] {
+        return !generic && (mode == lws::MODE_ONLINE || mode == lws::MODE_NOFUTURE) && lws::team_supports(mode, F, T, L, Q, Qp, LA, n) &&
+               (!r.ordered || lws::team_ordered_fits(F, T, L, Q, LA, n, fp64));
+    };
+    // fp64, Q = 8: the online stage goes to the team engine's order-exact kernel (831 ms for 256 x 500 x 257 against 1 296 on online64,
+    // the same bits) -- with LWS_TEAM_FP64=1 its re-associating kernel with the window in LDS (483 ms)
+    auto q8_team = [&] {
+        return Q == 8 && !no_team && !no_team_q8 && !online_serial && lws::team_supports(mode, F, T, L, Q, Qp, LA, n) &&
+               (team_fp64 ? lws::team_online_in_lds(true, F, T, L, Q, Qp, LA, n) : lws::team_ordered_fits(F, T, L, Q, LA, n, true));
+    };
+
+    // 1. fp32 batch sweeps of the plans a systolic build was made for (plan creation)
+    if (at(Engine::Systolic) && !fp64 && batch && !generic && p->sysb && p->sysb->supports(p->sys, st.wsel, T)) return pick(Engine::Systolic);
+    if (at(Engine::TeamFirst) && team_first && (!fp64 || team_fp64 || online) && team()) return pick(Engine::TeamFirst);
+    // 2. online and no-future sweeps: the moving window / the last Q + 1 frames in LDS (fp64: the generic engine's bits)
+    if (at(Engine::OnlineLds) && !fp64 && online && !generic &&
+        lws::online_lds_supports(F, T, L, Q, Qp, LA, n, 2, p->twiddle_all ? p->tw_P : 0, p->tw_s, p->online_tw.p != nullptr))
+        return pick(Engine::OnlineLds);
+    if (at(Engine::NofutureLds) && nofuture && !generic &&
+        (fp64 ? lws::nofuture_lds64_supports(F, T, L, Q, Qp, p->wperiod[st.wsel]) : lws::nofuture_lds_supports(F, T, L, Q, Qp, p->wperiod[st.wsel])))
+        return pick(Engine::NofutureLds);
+    if (at(Engine::Online64) && fp64 && online && !generic && !q8_team() && lws::online64_supports(F, T, L, Q, Qp, LA, n, 2))
+        return pick(Engine::Online64);
+    // 3. batch sweeps no systolic build takes: the fp64 systolic engine, the band engine (weights with create_weights' twiddle
+    //    structure, a sweep slot's ring in LDS), the generic engine on a time-skewed copy of the state (coalesced taps; same bits)
+    if (at(Engine::Sys64) && fp64 && batch && !generic && !plain && !no_sys64 &&
+        lws::sys64_supports(F, T, L, Q, Qp, 2, p->have[st.wsel] ? p->hostW[st.wsel].data() : nullptr))
+        return pick(Engine::Sys64);
+    if (at(Engine::Band) && batch && !generic && !plain && p->have[st.wsel] &&
+        lws::band_plan(fp64, st.B, F, T, L, Q, Qp, 2, n, p->hostW[st.wsel].data(), &r.bp))
+        return pick(Engine::Band);
+    if (at(Engine::GenericSkew) && batch && !plain) return pick(Engine::GenericSkew);
+    // 4. online and no-future sweeps no LDS engine takes: the team engine (the generic engine's schedule, a bin's taps on a team of lanes)
+    if (at(Engine::Team) && !no_team && (!fp64 || r.ordered || team_fp64) && !online_serial && !nofuture_serial && team()) return pick(Engine::Team);
+    return pick(Engine::Generic);
+}
+
+constexpr int NO_ROOM = 1 << 30;   // (internal) no room for an engine's scratch: the next engine takes the stage
+
+// Scratch of the engines that work on a copy of the state in a layout of their own: sys64, band, the skewed generic engine.
+template <typename real>
+int ensure_route_scratch(lws_plan *p, const Route &r, const Stage &st) {
+    size_t sb = 0, ab = 0;
+    if (r.engine == Engine::Sys64) {
+        sb = lws::sys64_bytes(st.B, p->F, st.T, p->Q, &ab);
+    } else if (r.engine == Engine::Band) {
+        if (p->band_tab_lt[st.wsel] != r.bp.LT) {   // (once per plan and tensor: a blocking copy of a few KB)
+            const std::vector<unsigned char> tab = lws::band_tables(r.bp, p->hostW[st.wsel].data());
+            int rc = p->band_tab[st.wsel].ensure(tab.size());
+            if (rc) return rc;
+            HIP_TRY(hipMemcpy(p->band_tab[st.wsel].p, tab.data(), tab.size(), hipMemcpyHostToDevice));
+            p->band_tab_lt[st.wsel] = r.bp.LT;
+        }
+        sb = r.bp.state_bytes;
+        ab = r.bp.amp_bytes;
+    } else if (r.engine == Engine::GenericSkew) {
+        // (what the copy may take: half of what is free now plus what the plan already holds for it, 48 GiB at most)
+        sb = lws::generic_skew_bytes<real>(st.B, p->F, st.T, p->L, p->Q, &ab);
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+        if (sb + ab > std::min((size_t)48 << 30, free_b / 2 + p->gsk_state.cap + p->gsk_amp.cap)) return NO_ROOM;
+    } else {
+        return LWS_OK;
+    }
+    if (p->gsk_state.ensure(sb) == LWS_OK && p->gsk_amp.ensure(ab) == LWS_OK) return LWS_OK;
+    p->gsk_state.release(); p->gsk_amp.release();   // no room after all: give back what was taken
+    (void)hipGetLastError();                        // (the refused hipMalloc must not be what a later launch reports)
+    g_err.clear();
+    return NO_ROOM;
+}
+
+// Launches the update kernel(s) of the engine and records what ran (lws_last_kernel_name, lws_generic_stage, the timing events).
+template <typename real>
+int launch_route(lws_plan *p, const Route &r, const lws::GenericArgs<real> &a, int B, hipStream_t s) {
+    constexpr bool fp64 = std::is_same<real, double>::value;
+    const bool q4compat = a.mode == lws::MODE_NOFUTURE_Q4_COMPAT;
+    // (the systolic, sys64 and band engines record the timing events around their update kernels themselves)
+    const bool self_timed = r.engine == Engine::Systolic || r.engine == Engine::Sys64 || r.engine == Engine::Band;
+    hipError_t e = hipErrorInvalidValue;
+    int launches = 1;
+    const char *name = "", *what = "", *generic_stage = nullptr;
+    if (!self_timed) begin_timing(p, s);
+    switch (r.engine) {
+    case Engine::Systolic:
+        if constexpr (!fp64) e = p->sysb->launch(p->sys, a.wsel, a.state, a.amp, a.thr, B, a.T, a.n_thr, s, &launches, p->ev0, p->ev1);
+        name = p->sysb->name(p->sys), what = "systolic";
+        break;
+    case Engine::TeamFirst:
+    case Engine::Team:
+        e = lws::launch_team<real>(a, B, r.ordered, s);
+        name = a.mode == lws::MODE_ONLINE ? (r.ordered ? (fp64 ? "team_online_ordered_fp64" : "team_online_ordered_fp32") : (fp64 ? "team_online_fp64" : "team_online_fp32"))
+                                          : (fp64 ? "team_nofuture_fp64" : "team_nofuture_fp32");
+        what = "team engine";
+        break;
+    case Engine::OnlineLds:
+        if constexpr (!fp64) e = lws::launch_online_lds(a, B, p->tw_P, p->tw_s, static_cast<const float *>(p->online_tw.p), s);
+        name = "online_lds_fp32", what = "online";
+        break;
+    case Engine::NofutureLds:
+        if constexpr (fp64) e = lws::launch_nofuture_lds64(a, B, p->wperiod[a.wsel], s);
+        else e = lws::launch_nofuture_lds(a, B, p->wperiod[a.wsel], s);
+        name = fp64 ? (q4compat ? "nofuture_lds_q4compat_fp64" : "nofuture_lds_fp64") : (q4compat ? "nofuture_lds_q4compat_fp32" : "nofuture_lds_fp32");
+        what = fp64 ? "fp64 no-future" : "no-future";
+        break;
+    case Engine::Online64:
+        if constexpr (fp64) e = lws::launch_online64(a, B, r.one_wave, s);
+        name = r.one_wave ? "online_lds_fp64_1w" : "online_lds_fp64", what = "fp64 online";
+        break;
+    case Engine::Sys64:
+        if constexpr (fp64) e = lws::launch_sys64(a, p->hostW[a.wsel].data(), B, p->gsk_state.p, p->gsk_amp.p, s, &launches, p->ev0, p->ev1);
+        name = lws::sys64_name(a.F, a.T, a.Q), what = "fp64 systolic";
+        break;
+    case Engine::Band:
+        e = lws::launch_band<real>(r.bp, a, p->band_tab[a.wsel].p, B, p->gsk_state.p, p->gsk_amp.p, s, &launches, p->ev0, p->ev1);
+        name = lws::band_name(r.bp), what = "band engine";
+        break;
+    case Engine::GenericSkew:
+        e = lws::launch_generic_skewed<real>(a, B, p->gsk_state.p, p->gsk_amp.p, s);
+        name = fp64 ? "generic_skew_fp64" : "generic_skew_fp32", what = "generic (skewed)", generic_stage = "batch";
+        break;
+    case Engine::Generic:
+        e = lws::launch_generic<real>(a, B, s);
+        name = fp64 ? "generic_fp64" : "generic_fp32", what = "generic";
+        generic_stage = a.mode == lws::MODE_BATCH ? "batch" : (a.mode == lws::MODE_ONLINE ? "online" : "no-future");
+        break;
+    }
+    if (self_timed) p->timing_pending = true;
+    else end_timing(p, s);
+    if (e != hipSuccess) return fail(LWS_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
+    p->last_launches = launches;
+    p->last_name = name;
+    if (generic_stage) p->generic_stage = generic_stage;
+    return LWS_OK;
+}
+
+// One stage on the extended device buffers: thresholds -> scaled table -> update kernel(s) of the engine choose_engine names.
 //   mode: lws::Mode.  Assumes state/amp/mean_amp are current.
 template <typename real>
 int run_stage(lws_plan *p, int mode, int wsel, int B, int T, const double *thr, int iters, int LA,
@@ -279,25 +458,7 @@ int run_stage(lws_plan *p, int mode, int wsel, int B, int T, const double *thr, 
     HIP_TRY(lws::launch_scale_thresholds<real>(static_cast<const double *>(p->thr_host_copy.p),
                                               static_cast<const double *>(p->mean_amp.p),
                                               static_cast<real *>(p->thr_scaled.p), B, iters, s));
-    if (mode == lws::MODE_NOFUTURE && (p->flags & LWS_NOFUTURE_Q4_COMPAT) && p->Q == 4 && p->Qp == 4)
-        mode = lws::MODE_NOFUTURE_Q4_COMPAT;
-
-    // the systolic kernel serves batch sweeps of plans it was built for (fp32, summarised weights
-    // with the twiddle structure of create_weights, supported shape); everything else is generic.
-    if (!p->fp64 && mode == lws::MODE_BATCH && !(p->flags & LWS_FORCE_GENERIC)) {
-        if (p->sysb && p->sysb->supports(p->sys, wsel, T)) {
-            int launches = 0;
-            float2 *st = static_cast<float2 *>(p->state.p);
-            const float *am = static_cast<const float *>(p->amp.p), *th = static_cast<const float *>(p->thr_scaled.p);
-            hipError_t e = p->sysb->launch(p->sys, wsel, st, am, th, B, T, iters, s, &launches, p->ev0, p->ev1);
-            p->timing_pending = true;
-            if (e != hipSuccess) return fail(LWS_ERR_HIP, "systolic launch failed: %s", hipGetErrorString(e));
-            p->last_launches = launches;
-            p->last_name = p->sysb->name(p->sys);
-            return LWS_OK;
-        }
-    }
-
+    const Stage st = stage_of(p, mode, wsel, B, T, iters, LA);
     lws::GenericArgs<real> a;
     a.state = static_cast<C *>(p->state.p);
     a.amp = static_cast<const real *>(p->amp.p);
@@ -310,192 +471,13 @@ int run_stage(lws_plan *p, int mode, int wsel, int B, int T, const double *thr, 
     a.M0 = 0;
     a.update = 2;  // both shipped callers pass 2 (lws.pyx:363, online_lws.cpp:160)
     a.qdiv = (real)qdiv;
-    a.mode = mode;
+    a.mode = st.mode;
     a.group = 1;
-    // (LWS_TEAM_FIRST=1, comparison runs: the team engine before the LDS engines of the online / no-future stages)
-    if ((mode == lws::MODE_ONLINE || mode == lws::MODE_NOFUTURE) && !(p->flags & LWS_FORCE_GENERIC) && env_int("LWS_TEAM_FIRST", 0) &&
-        (!p->fp64 || env_int("LWS_TEAM_FP64", 0) || mode == lws::MODE_ONLINE) &&
-        lws::team_supports(mode, a.F, a.T, a.L, a.Q, a.Qp, a.LA, a.n_thr) &&
-        !(mode == lws::MODE_ONLINE && lws::team_online_is_ordered(p->fp64) && !lws::team_ordered_fits(a.F, a.T, a.L, a.Q, a.LA, a.n_thr, p->fp64))) {
-        const bool ordered = mode == lws::MODE_ONLINE && lws::team_online_is_ordered(p->fp64);
-        begin_timing(p, s);
-        hipError_t e = lws::launch_team<real>(a, B, s);
-        end_timing(p, s);
-        if (e != hipSuccess) return fail(LWS_ERR_HIP, "team engine launch failed: %s", hipGetErrorString(e));
-        p->last_launches = 1;
-        p->last_name = mode == lws::MODE_ONLINE ? (ordered ? (p->fp64 ? "team_online_ordered_fp64" : "team_online_ordered_fp32") : (p->fp64 ? "team_online_fp64" : "team_online_fp32"))
-                                                : (p->fp64 ? "team_nofuture_fp64" : "team_nofuture_fp32");
-        return LWS_OK;
-    }
-    if constexpr (std::is_same<real, float>::value) {
-        // online driver: frames of the moving window live in LDS when the shape allows it
-        if (mode == lws::MODE_ONLINE && !(p->flags & LWS_FORCE_GENERIC) &&
-            lws::online_lds_supports(a.F, a.T, a.L, a.Q, a.Qp, a.LA, a.n_thr, a.update, p->twiddle_all ? p->tw_P : 0, p->tw_s, p->online_tw.p != nullptr)) {
-            begin_timing(p, s);
-            hipError_t e = lws::launch_online_lds(a, B, p->tw_P, p->tw_s, static_cast<const float *>(p->online_tw.p), s);
-            end_timing(p, s);
-            if (e != hipSuccess) return fail(LWS_ERR_HIP, "online launch failed: %s", hipGetErrorString(e));
-            p->last_launches = 1;
-            p->last_name = "online_lds_fp32";
-            return LWS_OK;
-        }
-    }
-    if constexpr (std::is_same<real, float>::value) {
-        // no-future sweeps: the last Q + 1 frames live in LDS (same results as the generic engine, bit for bit)
-        if ((mode == lws::MODE_NOFUTURE || mode == lws::MODE_NOFUTURE_Q4_COMPAT) && !(p->flags & LWS_FORCE_GENERIC) &&
-            lws::nofuture_lds_supports(a.F, a.T, a.L, a.Q, a.Qp, p->wperiod[a.wsel])) {
-            begin_timing(p, s);
-            hipError_t e = lws::launch_nofuture_lds(a, B, p->wperiod[a.wsel], s);
-            end_timing(p, s);
-            if (e != hipSuccess) return fail(LWS_ERR_HIP, "no-future launch failed: %s", hipGetErrorString(e));
-            p->last_launches = 1;
-            p->last_name = mode == lws::MODE_NOFUTURE_Q4_COMPAT ? "nofuture_lds_q4compat_fp32" : "nofuture_lds_fp32";
-            return LWS_OK;
-        }
-    }
-    if constexpr (std::is_same<real, double>::value) {
-        // no-future sweeps of an fp64 plan: the LDS engine's one-lane-per-bin variant in double (the generic engine's bits)
-        if ((mode == lws::MODE_NOFUTURE || mode == lws::MODE_NOFUTURE_Q4_COMPAT) && !(p->flags & LWS_FORCE_GENERIC) && !env_int("LWS_NO_ONLINE64", 0) &&
-            lws::nofuture_lds64_supports(a.F, a.T, a.L, a.Q, a.Qp, p->wperiod[a.wsel])) {
-            begin_timing(p, s);
-            hipError_t e = lws::launch_nofuture_lds64(a, B, p->wperiod[a.wsel], s);
-            end_timing(p, s);
-            if (e != hipSuccess) return fail(LWS_ERR_HIP, "fp64 no-future launch failed: %s", hipGetErrorString(e));
-            p->last_launches = 1;
-            p->last_name = mode == lws::MODE_NOFUTURE_Q4_COMPAT ? "nofuture_lds_q4compat_fp64" : "nofuture_lds_fp64";
-            return LWS_OK;
-        }
-    }
-    if constexpr (std::is_same<real, double>::value) {
-        // online driver of an fp64 plan: the frames of the moving window in LDS, every sum in the generic engine's order (same bits)
-        // (Q = 8: three frames' pairs on the two waves' chain -- 1 296 ms for 256 x 500 x 257 against 831 on the team engine's order-exact
-        // kernel, which gives the same bits (the generic engine's): such plans go there unless LWS_NO_TEAM_Q8=1 asks for this kernel.
-        // With LWS_TEAM_FP64=1: the team engine's re-associating kernel with its window in LDS, 483 ms)
-        const bool q8_team = a.Q == 8 && !env_int("LWS_NO_TEAM", 0) && !env_int("LWS_NO_TEAM_Q8", 0) && !env_int("LWS_ONLINE_SERIAL_TAPS", 0) &&
-                             lws::team_supports(mode, a.F, a.T, a.L, a.Q, a.Qp, a.LA, a.n_thr) &&
-                             (env_int("LWS_TEAM_FP64", 0) ? lws::team_online_in_lds(true, a.F, a.T, a.L, a.Q, a.Qp, a.LA, a.n_thr)
-                                                          : lws::team_ordered_fits(a.F, a.T, a.L, a.Q, a.LA, a.n_thr, true));
-        if (mode == lws::MODE_ONLINE && !(p->flags & LWS_FORCE_GENERIC) && !env_int("LWS_NO_ONLINE64", 0) && !q8_team &&
-            lws::online64_supports(a.F, a.T, a.L, a.Q, a.Qp, a.LA, a.n_thr, a.update)) {
-            begin_timing(p, s);
-            hipError_t e = lws::launch_online64(a, B, s);
-            end_timing(p, s);
-            if (e != hipSuccess) return fail(LWS_ERR_HIP, "fp64 online launch failed: %s", hipGetErrorString(e));
-            p->last_launches = 1;
-            p->last_name = lws::online64_name();
-            return LWS_OK;
-        }
-    }
-    if constexpr (std::is_same<real, double>::value) {
-        // batch sweeps of an fp64 plan: the fp64 systolic engine (lws_sys64.hip) when the shape and the weights allow it.  Same
-        // sweeps in the reference's order; a bin's sum is taken in another order, so results agree to rounding, not bit for bit
-        // (LWS_FORCE_GENERIC keeps the order-exact engine).
-        if (mode == lws::MODE_BATCH && !(p->flags & (LWS_FORCE_GENERIC | LWS_GENERIC_PLAIN_LAYOUT)) && !env_int("LWS_NO_SYS64", 0) &&
-            lws::sys64_supports(a.F, a.T, a.L, a.Q, a.Qp, a.update, p->have[wsel] ? p->hostW[wsel].data() : nullptr)) {
-            size_t ab = 0;
-            const size_t sb = lws::sys64_bytes(B, a.F, a.T, a.Q, &ab);
-            if (p->gsk_state.ensure(sb) == LWS_OK && p->gsk_amp.ensure(ab) == LWS_OK) {
-                int launches = 0;
-                hipError_t e = lws::launch_sys64(a, p->hostW[wsel].data(), B, p->gsk_state.p, p->gsk_amp.p, s, &launches, p->ev0, p->ev1);
-                p->timing_pending = true;
-                if (e != hipSuccess) return fail(LWS_ERR_HIP, "fp64 systolic launch failed: %s", hipGetErrorString(e));
-                p->last_launches = launches;
-                p->last_name = lws::sys64_name(a.F, a.T, a.Q);
-                return LWS_OK;
-            }
-            p->gsk_state.release(); p->gsk_amp.release();   // no room for the skewed copy: the generic engine below
-            (void)hipGetLastError();
-            g_err.clear();
-        }
-    }
-    // batch sweeps no systolic build takes (5-8 frames per stencil row above 513 bins, more than 8 frames per row, stencils of
-    // half-width 6-10, fp64 plans beyond Q in {2, 4}): the band engine (lws_band.hip) when the weights have create_weights'
-    // twiddle structure and a sweep slot's ring fits the LDS.  Same sweeps in the reference's order; a bin's sum in another order.
-    if (mode == lws::MODE_BATCH && !(p->flags & (LWS_FORCE_GENERIC | LWS_GENERIC_PLAIN_LAYOUT)) && !env_int("LWS_NO_BAND", 0) && p->have[wsel]) {
-        lws::BandPlan bp;
-        if (lws::band_plan(p->fp64, B, a.F, a.T, a.L, a.Q, a.Qp, a.update, a.n_thr, p->hostW[wsel].data(), &bp)) {
-            if (p->band_tab_lt[wsel] != bp.LT) {   // (once per plan and tensor: a blocking copy of a few KB)
-                const std::vector<unsigned char> tab = lws::band_tables(bp, p->hostW[wsel].data());
-                int rc = p->band_tab[wsel].ensure(tab.size());
-                if (rc) return rc;
-                HIP_TRY(hipMemcpy(p->band_tab[wsel].p, tab.data(), tab.size(), hipMemcpyHostToDevice));
-                p->band_tab_lt[wsel] = bp.LT;
-            }
-            if (p->gsk_state.ensure(bp.state_bytes) == LWS_OK && p->gsk_amp.ensure(bp.amp_bytes) == LWS_OK) {
-                int launches = 0;
-                hipError_t e = lws::launch_band<real>(bp, a, p->band_tab[wsel].p, B, p->gsk_state.p, p->gsk_amp.p, s, &launches, p->ev0, p->ev1);
-                p->timing_pending = true;
-                if (e != hipSuccess) return fail(LWS_ERR_HIP, "band engine launch failed: %s", hipGetErrorString(e));
-                p->last_launches = launches;
-                p->last_name = lws::band_name(bp);
-                return LWS_OK;
-            }
-            p->gsk_state.release(); p->gsk_amp.release();   // no room for the skewed copy: the generic engine below
-            (void)hipGetLastError();
-            g_err.clear();
-        }
-    }
-    if (mode == lws::MODE_BATCH && !(p->flags & LWS_GENERIC_PLAIN_LAYOUT)) {
-        // batch sweeps of the generic engine run on a time-skewed copy of the state (coalesced taps; same bits) unless
-        // that copy would be unreasonably large
-        size_t ab = 0;
-        const size_t sb = lws::generic_skew_bytes<real>(B, p->F, T, p->L, p->Q, &ab);
-        // (what the copy may take: half of what is free now plus what the plan already holds for it, 48 GiB at most)
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-        const size_t limit = std::min((size_t)48 << 30, free_b / 2 + p->gsk_state.cap + p->gsk_amp.cap);
-        bool have_copy = sb + ab <= limit;
-        if (have_copy && (p->gsk_state.ensure(sb) != LWS_OK || p->gsk_amp.ensure(ab) != LWS_OK)) {
-            // no room after all: give back what was taken and run in the plain layout (same results, bit for bit)
-            p->gsk_state.release(); p->gsk_amp.release();
-            have_copy = false;
-            (void)hipGetLastError();   // the refused hipMalloc must not be what the plain-layout launch below reports
-            g_err.clear();
-        }
-        if (have_copy) {
-            begin_timing(p, s);
-            hipError_t e = lws::launch_generic_skewed<real>(a, B, p->gsk_state.p, p->gsk_amp.p, s);
-            end_timing(p, s);
-            if (e != hipSuccess) return fail(LWS_ERR_HIP, "generic (skewed) launch failed: %s", hipGetErrorString(e));
-            p->last_launches = 1;
-            p->last_name = p->fp64 ? "generic_skew_fp64" : "generic_skew_fp32";
-            p->generic_stage = "batch";
-            return LWS_OK;
-        }
-    }
-    // online and no-future sweeps no LDS engine takes (more than 8 frames per stencil row, L > 5, weights without the twiddle
-    // structure, frames beyond the rings): the team engine (lws_team.hip) -- the generic engine's schedule with a bin's taps spread
-    // over a team of lanes.  Same sweeps in the reference's order; a bin's sum in another order.
-    // (the serial-taps verification variants of the LDS engines promise the generic engine's bits: they keep falling through to it.
-    // fp64 plans: the online and no-future recursions amplify the rounding of a re-associated sum by 5-10 per frame -- equally valid
-    // phases, but not the reference's numbers an fp64 plan exists to reproduce.  Their online stage runs on the team engine's
-    // ORDER-EXACT kernel (increments by many lanes, the sum by one, in the reference's order: the generic engine's bits); the
-    // re-associating kernels, and no-future sweeps, only with LWS_TEAM_FP64=1.  fp32 plans: LWS_TEAM_ORDERED=1 selects that kernel too.)
-    {
-        const bool ordered = mode == lws::MODE_ONLINE && lws::team_online_is_ordered(p->fp64);
-        const bool allowed = p->fp64 ? (ordered || env_int("LWS_TEAM_FP64", 0)) : true;
-        if ((mode == lws::MODE_ONLINE || mode == lws::MODE_NOFUTURE) && !(p->flags & LWS_FORCE_GENERIC) && !env_int("LWS_NO_TEAM", 0) && allowed &&
-            !env_int("LWS_ONLINE_SERIAL_TAPS", 0) && !env_int("LWS_NOFUTURE_SERIAL_TAPS", 0) && !(p->fp64 && env_int("LWS_NO_ONLINE64", 0)) &&
-            lws::team_supports(mode, a.F, a.T, a.L, a.Q, a.Qp, a.LA, a.n_thr) &&
-            (!ordered || lws::team_ordered_fits(a.F, a.T, a.L, a.Q, a.LA, a.n_thr, p->fp64))) {
-            begin_timing(p, s);
-            hipError_t e = lws::launch_team<real>(a, B, s);
-            end_timing(p, s);
-            if (e != hipSuccess) return fail(LWS_ERR_HIP, "team engine launch failed: %s", hipGetErrorString(e));
-            p->last_launches = 1;
-            p->last_name = mode == lws::MODE_ONLINE ? (ordered ? (p->fp64 ? "team_online_ordered_fp64" : "team_online_ordered_fp32") : (p->fp64 ? "team_online_fp64" : "team_online_fp32"))
-                                                    : (p->fp64 ? "team_nofuture_fp64" : "team_nofuture_fp32");
-            return LWS_OK;
-        }
-    }
-    begin_timing(p, s);
-    hipError_t e = lws::launch_generic<real>(a, B, s);
-    end_timing(p, s);
-    if (e != hipSuccess) return fail(LWS_ERR_HIP, "generic launch failed: %s", hipGetErrorString(e));
-    p->last_launches = 1;
-    p->last_name = p->fp64 ? "generic_fp64" : "generic_fp32";
-    p->generic_stage = mode == lws::MODE_BATCH ? "batch" : (mode == lws::MODE_ONLINE ? "online" : "no-future");
-    return LWS_OK;
+    Route r = choose_engine(p, st);
+    int rc;
+    while ((rc = ensure_route_scratch<real>(p, r, st)) == NO_ROOM) r = choose_engine(p, st, Engine((int)r.engine + 1));
+    if (rc) return rc;
+    return launch_route<real>(p, r, a, B, s);
 }
 
 struct StageSpec {
@@ -505,6 +487,11 @@ struct StageSpec {
     int LA;
     double qdiv;
 };
+
+// Does the systolic engine take this stage?  (run_pipeline's direct I/O, run_host_pipelined's chunking: the chooser's answer)
+bool on_systolic(const lws_plan *p, const StageSpec &sp, int B, int T) {
+    return sp.iters > 0 && choose_engine(p, stage_of(p, sp.mode, sp.wsel, B, T, sp.iters, sp.LA)).engine == Engine::Systolic;
+}
 
 // prep -> stages (with pad refresh in between) -> extract, for either host (double2) or device
 // (float2 / double2, in place) spectrogram buffers.
@@ -542,8 +529,7 @@ int run_pipeline(lws_plan *p, const io_cx *in_dev, io_cx *out_dev, const io_cx *
         int active = 0, which = -1;
         for (int i = 0; i < nstages; ++i)
             if (stages[i].iters > 0) { ++active; which = i; }
-        if (active == 1 && stages[which].mode == lws::MODE_BATCH && !(p->flags & (LWS_FORCE_GENERIC | LWS_NO_DIRECT_IO)) &&
-            p->sysb && p->sysb->supports(p->sys, stages[which].wsel, T))
+        if (active == 1 && !(p->flags & LWS_NO_DIRECT_IO) && on_systolic(p, stages[which], B, T))
             return run_direct_batch(p, in_dev, out_dev, B, T, stages[which], s);
     }
     int max_it = 1;
@@ -738,10 +724,6 @@ int usable_cpus() {
 }  // namespace lws
 void lws_plan_set_host_threads(lws_plan *p, int n) { if (p) p->host_threads = n; }
 namespace {
-int env_int(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
-}
 
 // spectrograms per chunk of the pipeline below (`per`: bins of one spectrogram)
 // whole_device: some stage of the call runs ONE workgroup per spectrogram (no-future, online, the generic engine): a launch of
@@ -803,10 +785,9 @@ int run_host_pipelined(lws_plan *p, const double *S_in, double *S_out, int B, in
     // 32M 72 ms): long enough for the kernels to fill the device -- a launch of 32 spectrograms takes 6.7 ms, of 64 10.5, of
     // 256 33.9: fewer spectrograms than CUs run several workgroups each, 70-85 % as efficient -- short enough for the first
     // upload and the last download, which nothing overlaps, to be a small part of the call
-    bool whole_device = false;
+    bool whole_device = false;   // (some stage of the call is not on the systolic engine)
     for (int i = 0; i < n; ++i)
-        if (st[i].iters > 0 && (st[i].mode != lws::MODE_BATCH || (p->flags & LWS_FORCE_GENERIC) || !p->sysb || !p->sysb->supports(p->sys, st[i].wsel, T)))
-            whole_device = true;
+        if (st[i].iters > 0 && !on_systolic(p, st[i], B, T)) whole_device = true;
     const int Bc = host_chunk(per, B, cu_count(p->device), whole_device);
     // chunk c = spectrograms [cs[c], cs[c + 1]).  The first upload and the last download have nothing to overlap with: when the
     // batch is cut at all, the first chunk is half a chunk (the device starts after half the narrowing and half the copy), and the
@@ -1153,24 +1134,17 @@ int lws_plan_create(lws_plan **plan, int device, int F, int L, int Q, int Qp, co
         const bool h16 = (flags & LWS_STORAGE_FP16) != 0;
         hipError_t e = hipSuccess;
         // the first build that takes the shape: short frames (<= 129 / 257 bins: four / two sweep slots per wave), up to 513 bins,
-        // Q = 8, up to 1025 bins.  LWS_SYSTOLIC_NO_SHORT=1 skips the short-frame builds (comparison runs)
-        const bool no_short = env_int("LWS_SYSTOLIC_NO_SHORT", 0) != 0;
+        // Q = 8, up to 1025 bins.  LWS_SYSTOLIC_NO_SHORT=1, _NO_TW=1, _NO_R16=1 skip kinds of builds (comparison runs)
+        const unsigned skip = (env_int("LWS_SYSTOLIC_NO_SHORT", 0) ? lws::SYSTOLIC_SHORT : 0u) | (env_int("LWS_SYSTOLIC_NO_TW", 0) ? lws::SYSTOLIC_TW : 0u) |
+                              (env_int("LWS_SYSTOLIC_NO_R16", 0) ? lws::SYSTOLIC_R16 : 0u);
         for (const lws::SystolicBuild *b : {&lws::quarter_q2::systolic_entry(), &lws::quarter::systolic_entry(), &lws::half_q2::systolic_entry(), &lws::half::systolic_entry(),
                                             &lws::q2::systolic_entry(), &lws::systolic_entry(),
                                             &lws::q8::systolic_entry(), &lws::wide_q2::systolic_entry(), &lws::wide::systolic_entry(), &lws::xwide::systolic_entry(), &lws::l7::systolic_entry(),
                                             // ... then the table-twiddle builds: Q = 3, and general weights of a hop that does not divide the frame
                                             &lws::tw_half::systolic_entry(), &lws::tw::systolic_entry(), &lws::tw_wide::systolic_entry(),
-                                            // (exactly 5 / 6 frames per stencil row: the builds with their own ring depth first; LWS_SYSTOLIC_NO_TWQ=1 skips them -- comparison runs)
+                                            // (exactly 5 / 6 frames per stencil row: the builds with their own ring depth first)
                                             &lws::tw_q5::systolic_entry(), &lws::tw_q6::systolic_entry(), &lws::tw_q8::systolic_entry()}) {
-            const bool is_short = b == &lws::quarter::systolic_entry() || b == &lws::half::systolic_entry() || b == &lws::quarter_q2::systolic_entry() ||
-                                  b == &lws::half_q2::systolic_entry() || b == &lws::tw_half::systolic_entry();
-            const bool is_twq = b == &lws::tw_q5::systolic_entry() || b == &lws::tw_q6::systolic_entry();
-            const bool is_tw = is_twq || b == &lws::tw_half::systolic_entry() || b == &lws::tw::systolic_entry() || b == &lws::tw_wide::systolic_entry() || b == &lws::tw_q8::systolic_entry();
-            if (is_twq && env_int("LWS_SYSTOLIC_NO_TWQ", 0)) continue;
-            if (is_tw && env_int("LWS_SYSTOLIC_NO_TW", 0)) continue;                                 // (comparison runs)
-            const bool is_r16 = b == &lws::q2::systolic_entry() || b == &lws::wide_q2::systolic_entry() || b == &lws::quarter_q2::systolic_entry() ||
-                                b == &lws::half_q2::systolic_entry();
-            if ((no_short && is_short) || (is_r16 && env_int("LWS_SYSTOLIC_NO_R16", 0))) continue;   // (comparison runs)
+            if (b->kind & skip) continue;
             if ((e = b->build(p->sys, F, L, Q, Qp, hw, h16)) != hipSuccess) break;
             // the build must take the tensor batch sweeps normally run on -- W, the first one present -- : a build that only takes
             // another of the plan's tensors (W_ai of a hop above half the frame has no neighbour-frame weights and fits any

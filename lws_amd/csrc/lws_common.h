@@ -4,22 +4,30 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <atomic>
 
 namespace lws {
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device; the launchers keep one bit per device in a function-local
-// atomic (lws_multi_* launches the same kernels from one host thread per device).  Returns true if this device still needs
-// the call; a lost race only repeats it.
-inline bool attr_needed(std::atomic<unsigned long long> &done, int *dev_out) {
+// The environment switches of the library (comparison runs and tests): the integer value of `name`, `dflt` if it is unset or empty.
+inline int env_int(const char *name, int dflt) {
+    const char *v = getenv(name);
+    return (v && *v) ? atoi(v) : dflt;
+}
+
+// Lets `Kernel` be launched with up to `bytes` of dynamic LDS.  The runtime's attribute is per kernel and per device: one bit per
+// device for each kernel, in an atomic (lws_multi_* launches the same kernels from one host thread per device); a
+// lost race only repeats the call.
+template <auto Kernel> hipError_t allow_dynamic_lds(int bytes) {
+    static std::atomic<unsigned long long> done{0};
     int dev = 0;
     (void)hipGetDevice(&dev);
-    *dev_out = dev;
-    return dev < 0 || dev >= 64 || !((done.load(std::memory_order_relaxed) >> dev) & 1ull);
-}
-inline void attr_done(std::atomic<unsigned long long> &done, int dev) {
-    if (dev >= 0 && dev < 64) done.fetch_or(1ull << dev, std::memory_order_relaxed);
+    const bool tracked = dev >= 0 && dev < 64;
+    if (tracked && ((done.load(std::memory_order_relaxed) >> dev) & 1ull)) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess && tracked) done.fetch_or(1ull << dev, std::memory_order_relaxed);
+    return e;
 }
 
 // records the text lws_last_error() returns and passes `code` through (lws_capi.hip)

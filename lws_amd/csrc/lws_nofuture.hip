@@ -312,22 +312,16 @@ __global__ void __launch_bounds__(SPLIT ? 1024 : 512) k_nofuture(NfArgsT<R> a) {
 
 template <int QT, int LT, bool COMPAT, bool SPLIT, typename R = float>
 hipError_t launch_ts(const NfArgsT<R> &a, int B, int threads, size_t lds, hipStream_t s) {
-    static std::atomic<unsigned long long> attr_set{0};   // one bit per device
-    int attr_dev;
-    if (lws::attr_needed(attr_set, &attr_dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_nofuture<QT, LT, COMPAT, SPLIT, R>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        lws::attr_done(attr_set, attr_dev);
-    }
+    const hipError_t e = lws::allow_dynamic_lds<&k_nofuture<QT, LT, COMPAT, SPLIT, R>>(160 * 1024);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_nofuture<QT, LT, COMPAT, SPLIT, R>), dim3(B), dim3(threads), lds, s, a);
     return hipGetLastError();
 }
 // threads: of the one-lane-per-bin variant; the eight-lane one takes up to 1024
 template <int QT, int LT, bool COMPAT>
 hipError_t launch_t(const NfArgs &a, int B, int threads, size_t lds, hipStream_t s) {
-    const char *ev = getenv("LWS_NOFUTURE_SERIAL_TAPS");   // verification only: one lane sums every tap, in the generic engine's order
-    if (ev && ev[0] == '1') return launch_ts<QT, LT, COMPAT, false>(a, B, threads, lds, s);
+    if (lws::env_int("LWS_NOFUTURE_SERIAL_TAPS", 0) == 1)   // verification only: one lane sums every tap, in the generic engine's order
+        return launch_ts<QT, LT, COMPAT, false>(a, B, threads, lds, s);
     int t8 = threads * 4;
     if (t8 > 1024) t8 = 1024;
     return launch_ts<QT, LT, COMPAT, true>(a, B, t8, lds, s);
@@ -347,8 +341,7 @@ NfShape shape_of(int F, int T, int L, int Q, int Qp, int rows, bool fp64 = false
     // three elements of a frame per thread at most (the prefetch of the next frame): the eight-lanes-per-bin variant runs up to
     // 1024 threads (frames of up to 3072 columns: 4096-point STFTs), the one-lane verification variant `threads`
     {
-        const char *ev = getenv("LWS_NOFUTURE_SERIAL_TAPS");
-        const int launched = (fp64 || (ev && ev[0] == '1')) ? sh.threads : (4 * sh.threads > 1024 ? 1024 : 4 * sh.threads);
+        const int launched = (fp64 || lws::env_int("LWS_NOFUTURE_SERIAL_TAPS", 0) == 1) ? sh.threads : (4 * sh.threads > 1024 ? 1024 : 4 * sh.threads);
         if (3 * launched < Np) return sh;
     }
     if (Q * (L + 1) > 64) return sh;     // one 64-bit participation mask per weight row

@@ -1558,14 +1558,8 @@ __global__ void __launch_bounds__(Online4Waves<Q>::N * 64) k_online4(OnlineArgs 
 }
 
 template <int Q, int L, bool SERIAL, int MAXT> hipError_t launch_qt(const OnlineArgs &a, int B, int threads, size_t lds, hipStream_t s) {
-    static std::atomic<unsigned long long> attr_set{0};   // one bit per device
-    int attr_dev;
-    if (lws::attr_needed(attr_set, &attr_dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_online<Q, L, SERIAL, MAXT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        lws::attr_done(attr_set, attr_dev);
-    }
+    const hipError_t e = lws::allow_dynamic_lds<&k_online<Q, L, SERIAL, MAXT>>(160 * 1024);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_online<Q, L, SERIAL, MAXT>), dim3(B), dim3(threads), lds, s, a);
     return hipGetLastError();
 }
@@ -1658,9 +1652,9 @@ Shape4 shape4_try(int F, int T, int Lu, int Q, int Qp, int LA, int n_thr, bool b
     const int need = (SKS * LA + NU + 2 + sh.NSW - 1) / sh.NSW;
     if (DS < need) DS = need;
     {
-        const char *ep = getenv("LWS_ONLINE_LAG_PLUS"), *es = getenv("LWS_ONLINE_SERIAL_TAPS");   // (the verification variant has no odd build)
-        if (ep && atoi(ep) > 0 && atoi(ep) <= 64) DS += atoi(ep);
-        const bool odd_ok = (PT > 0 || Q == 4 || Q == 2) && !(es && es[0] == '1');
+        const int plus = lws::env_int("LWS_ONLINE_LAG_PLUS", 0);
+        if (plus > 0 && plus <= 64) DS += plus;
+        const bool odd_ok = (PT > 0 || Q == 4 || Q == 2) && lws::env_int("LWS_ONLINE_SERIAL_TAPS", 0) != 1;   // (the verification variant has no odd build)
         if (!odd_ok) DS += DS & 1;
     }
     sh.DS = DS;
@@ -1684,42 +1678,36 @@ Shape4 shape4_try(int F, int T, int Lu, int Q, int Qp, int LA, int n_thr, bool b
     const int window = window_of(DS);
     r.NWR = window + 1 <= nwr_max ? window + 1 : window;
     // two workgroups fit a CU (half of its LDS each) without the spare ring frame but not with it: drop it -- batches of more
-    // spectrograms than CUs then run two chains per CU side by side (LWS_ONLINE_SPARE_FRAME=1 keeps it: comparison runs)
-    {
-        const char *ev = getenv("LWS_ONLINE_SPARE_FRAME");
-        if (r.NWR == window + 1 && lds_of(window + 1) > 80 * 1024 && lds_of(window) <= 80 * 1024 && !(ev && ev[0] == '1')) r.NWR = window;
-    }
+    // spectrograms than CUs then run two chains per CU side by side
+    if (r.NWR == window + 1 && lds_of(window + 1) > 80 * 1024 && lds_of(window) <= 80 * 1024) r.NWR = window;
     sh.lds = lds_of(r.NWR);
     if ((double)DS * T * per + (double)SKS * T + NU > 1.0e9) return r;
     sh.ok = true;
     return r;
 }
 Shape4 shape4_of(int F, int T, int Lu, int Q, int Qp, int LA, int n_thr, int PT = 0) {
-    if (PT > 0) {
-        const char *ev = getenv("LWS_ONLINE_SERIAL_TAPS");   // (no verification variant with table twiddles: generic engine)
-        return (ev && ev[0] == '1') ? Shape4{{0, 0, 0, 0, false}, 0, 0, false} : shape4_try(F, T, Lu, Q, Qp, LA, n_thr, false, PT);
-    }
+    const bool serial = lws::env_int("LWS_ONLINE_SERIAL_TAPS", 0) == 1;
+    if (PT > 0)   // (no verification variant with table twiddles: generic engine)
+        return serial ? Shape4{{0, 0, 0, 0, false}, 0, 0, false} : shape4_try(F, T, Lu, Q, Qp, LA, n_thr, false, PT);
     Shape4 r = shape4_try(F, T, Lu, Q, Qp, LA, n_thr, false);
-    const char *ev = getenv("LWS_ONLINE_SERIAL_TAPS");   // (the verification variant has no BIG build)
-    if (!r.sh.ok && !(ev && ev[0] == '1')) r = shape4_try(F, T, Lu, Q, Qp, LA, n_thr, true);
+    if (!r.sh.ok && !serial) r = shape4_try(F, T, Lu, Q, Qp, LA, n_thr, true);
     return r;
 }
 
 // which layout serves a shape: the wave-per-tap-group one unless it needs much more lag between sweeps (few slots: long
 // look-ahead) than the lane-group one; LWS_ONLINE_LAYOUT=2 / 3 forces one (tests)
 int pick_layout(const Shape &s2, const Shape &s3, const Shape &s4) {
-    const char *ev = getenv("LWS_ONLINE_LAYOUT");
-    if (ev && ev[0] == '2' && s2.ok) return 2;
-    if (ev && ev[0] == '3' && s3.ok) return 3;
-    if (ev && ev[0] == '4' && s4.ok) return 4;
+    const int forced = lws::env_int("LWS_ONLINE_LAYOUT", 0);
+    if (forced == 2 && s2.ok) return 2;
+    if (forced == 3 && s3.ok) return 3;
+    if (forced == 4 && s4.ok) return 4;
     if (s4.ok && (!s2.ok || 2 * s4.DS <= 3 * s2.DS)) return 4;
     if (s3.ok && (!s2.ok || 2 * s3.DS <= 3 * s2.DS)) return 3;
     return s2.ok ? 2 : 0;
 }
 
 template <int Q, int L, bool SERIAL, bool BIG, bool TWT, bool ODD> hipError_t launch_4p(const OnlineArgs &a, int B, size_t lds, hipStream_t s) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_online4<Q, L, SERIAL, BIG, TWT, ODD>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);   // (per device: not cached)
+    const hipError_t e = lws::allow_dynamic_lds<&k_online4<Q, L, SERIAL, BIG, TWT, ODD>>(160 * 1024);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_online4<Q, L, SERIAL, BIG, TWT, ODD>), dim3(B), dim3(Online4Waves<Q>::N * 64), lds, s, a);
     return hipGetLastError();
@@ -1733,14 +1721,8 @@ template <int Q, int L, bool SERIAL, bool BIG = false, bool TWT = false> hipErro
 }
 
 template <int Q, int L, bool SERIAL> hipError_t launch_3(const OnlineArgs &a, int B, size_t lds, hipStream_t s) {
-    static std::atomic<unsigned long long> attr_set{0};   // one bit per device
-    int attr_dev;
-    if (lws::attr_needed(attr_set, &attr_dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_online3<Q, L, SERIAL>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        lws::attr_done(attr_set, attr_dev);
-    }
+    const hipError_t e = lws::allow_dynamic_lds<&k_online3<Q, L, SERIAL>>(160 * 1024);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_online3<Q, L, SERIAL>), dim3(B), dim3(Online3Waves<Q>::N * 64), lds, s, a);
     return hipGetLastError();
 }
@@ -1751,8 +1733,7 @@ template <int Q, int L, bool SERIAL> hipError_t launch_3(const OnlineArgs &a, in
 // (general weights) are served through their first Q rows' base weights like summarised ones.
 // (LWS_ONLINE_TABLE_TWIDDLES=1, read when the plan is made: the table variant also where the static one would do -- comparison runs)
 bool online_static_twiddles(int Q, int tw_P, int tw_s) {
-    const char *ev = getenv("LWS_ONLINE_TABLE_TWIDDLES");
-    return tw_P == Q && tw_s == 1 && (Q == 2 || Q == 4 || Q == 8) && !(ev && ev[0] == '1');
+    return tw_P == Q && tw_s == 1 && (Q == 2 || Q == 4 || Q == 8) && lws::env_int("LWS_ONLINE_TABLE_TWIDDLES", 0) != 1;
 }
 // `table`: the plan's decision (latched when it was made: it uploaded the table or it did not), never re-read from the environment
 bool online_lds_supports(int F, int T, int L, int Q, int Qp, int LA, int n_thr, int update, int tw_P, int tw_s, bool table) {
@@ -1863,9 +1844,8 @@ hipError_t launch_online_lds(const GenericArgs<float> &g, int B, int tw_P, int t
     }
     a.F = g.F; a.T = g.T; a.n_thr = g.n_thr; a.LA = g.LA; a.NSW = sh.NSW; a.DS = sh.DS;
     a.NWR = sh4.NWR; a.NPS = sh4.NPS; a.Lu = g.L;
-    const char *ev = getenv("LWS_ONLINE_SERIAL_TAPS");   // verification only, see k_online
+    const bool serial = lws::env_int("LWS_ONLINE_SERIAL_TAPS", 0) == 1;   // verification only, see k_online
     if (layout == 4) {
-        const bool serial = ev && ev[0] == '1';
         if (sh4.big) {
             if (serial) return hipErrorInvalidValue;
             if (g.Q == 4) return launch_4<4, 5, false, true>(a, B, sh.lds, stream);
@@ -1877,12 +1857,11 @@ hipError_t launch_online_lds(const GenericArgs<float> &g, int B, int tw_P, int t
         return serial ? launch_4<8, 5, true>(a, B, sh.lds, stream) : launch_4<8, 5, false>(a, B, sh.lds, stream);
     }
     if (layout == 3) {
-        const bool serial = ev && ev[0] == '1';
         if (g.Q == 4) return serial ? launch_3<4, 5, true>(a, B, sh.lds, stream) : launch_3<4, 5, false>(a, B, sh.lds, stream);
         if (g.Q == 2) return serial ? launch_3<2, 5, true>(a, B, sh.lds, stream) : launch_3<2, 5, false>(a, B, sh.lds, stream);
         return serial ? launch_3<8, 5, true>(a, B, sh.lds, stream) : launch_3<8, 5, false>(a, B, sh.lds, stream);
     }
-    if (ev && ev[0] == '1') {
+    if (serial) {
         if (g.Q == 4) return launch_q<4, 5, true>(a, B, sh.threads, sh.lds, stream);
         if (g.Q == 2) return launch_q<2, 5, true>(a, B, sh.threads, sh.lds, stream);
         return launch_q<8, 5, true>(a, B, sh.threads, sh.lds, stream);

@@ -7,9 +7,8 @@ namespace lws {
 // true if launch_online64 can run this shape: summarised weights (Qp == Q, Q in {2, 3, 4, 8}), L = 5, update == 2, and the frames the
 // sweeps in flight need fit the LDS as fp64 rows (frames of up to ~600 bins); otherwise the caller uses the generic engine.
 bool online64_supports(int F, int T, int L, int Q, int Qp, int LA, int n_thr, int update);
-// Same contract and the same BITS as launch_generic<double> with mode == MODE_ONLINE.
-hipError_t launch_online64(const GenericArgs<double> &a, int B, hipStream_t stream);
-// "online_lds_fp64"; "online_lds_fp64_1w" when LWS_ONLINE64_ONE_WAVE selects the one-wave kernel (comparison runs; read on every launch)
-const char *online64_name();
+// Same contract and the same BITS as launch_generic<double> with mode == MODE_ONLINE.  one_wave: the one-wave kernel instead of the
+// two-wave one (comparison runs: LWS_ONLINE64_ONE_WAVE, read by the engine chooser)
+hipError_t launch_online64(const GenericArgs<double> &a, int B, bool one_wave, hipStream_t stream);
 
 }  // namespace lws

@@ -459,13 +459,13 @@ Shape64 shape64(int F, int T, int Lu, int Q, int Qp, int LA, int n_thr) {
 }
 
 template <int Q, bool AMP_LDS> hipError_t launch_qa(const Args64 &a, int B, size_t lds, hipStream_t s) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_online64<Q, AMP_LDS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    const hipError_t e = allow_dynamic_lds<&k_online64<Q, AMP_LDS>>(160 * 1024);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_online64<Q, AMP_LDS>), dim3(B), dim3(64), lds, s, a);
     return hipGetLastError();
 }
 template <int Q, bool AMP_LDS, int SPLIT, bool STRESS, int ONCH = 0> hipError_t launch_qps(const Args64 &a, int B, size_t lds, hipStream_t s) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_online64p<Q, AMP_LDS, SPLIT, STRESS, ONCH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    const hipError_t e = allow_dynamic_lds<&k_online64p<Q, AMP_LDS, SPLIT, STRESS, ONCH>>(160 * 1024);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_online64p<Q, AMP_LDS, SPLIT, STRESS, ONCH>), dim3(B), dim3(128), lds, s, a);
     return hipGetLastError();
@@ -481,23 +481,18 @@ template <int Q, bool AMP_LDS, int SPLIT, int ONCH> hipError_t launch_qp(const A
 // Q = 8 (77 pairs): three frames' pairs on the chain, 44 products held (256 + 200 registers): 980 -> 597 ms for 256 x 250 x 513; four / 33: 650.
 template <int Q> constexpr int onch_of() { return Q == 4 ? 1 : (Q == 8 ? 3 : 0); }
 template <int Q> constexpr int split_of() { return Q == 4 ? 11 : (Q == 8 ? 33 : ((Q - 1) * (2 * L + 1) > 16 ? ((Q - 1) * (2 * L + 1) - 16) / 2 : 0)); }
-template <int Q> hipError_t launch_q(const Args64 &a, int B, size_t lds, bool amp_lds, hipStream_t s) {
-    const bool one_wave = getenv("LWS_ONLINE64_ONE_WAVE") != nullptr;      // the one-wave kernel, for comparison (read on every launch: a test sets it between calls)
-    {
-        if (!one_wave) return amp_lds ? launch_qp<Q, true, split_of<Q>(), onch_of<Q>()>(a, B, lds, s) : launch_qp<Q, false, split_of<Q>(), onch_of<Q>()>(a, B, lds, s);
-    }
+template <int Q> hipError_t launch_q(const Args64 &a, int B, size_t lds, bool amp_lds, bool one_wave, hipStream_t s) {
+    if (!one_wave) return amp_lds ? launch_qp<Q, true, split_of<Q>(), onch_of<Q>()>(a, B, lds, s) : launch_qp<Q, false, split_of<Q>(), onch_of<Q>()>(a, B, lds, s);
     return amp_lds ? launch_qa<Q, true>(a, B, lds, s) : launch_qa<Q, false>(a, B, lds, s);
 }
 
 }  // namespace
 
-const char *online64_name() { return getenv("LWS_ONLINE64_ONE_WAVE") != nullptr ? "online_lds_fp64_1w" : "online_lds_fp64"; }
-
 bool online64_supports(int F, int T, int Lplan, int Q, int Qp, int LA, int n_thr, int update) {
     return update == 2 && shape64(F, T, Lplan, Q, Qp, LA, n_thr).ok;
 }
 
-hipError_t launch_online64(const GenericArgs<double> &g, int B, hipStream_t stream) {
+hipError_t launch_online64(const GenericArgs<double> &g, int B, bool one_wave, hipStream_t stream) {
     const Shape64 sh = shape64(g.F, g.T, g.L, g.Q, g.Qp, g.LA, g.n_thr);
     if (!sh.ok || g.update != 2 || g.mode != MODE_ONLINE) return hipErrorInvalidValue;
     if (B <= 0) return hipSuccess;
@@ -505,12 +500,12 @@ hipError_t launch_online64(const GenericArgs<double> &g, int B, hipStream_t stre
     a.state = g.state; a.amp = g.amp; a.thr = g.thr;
     for (int i = 0; i < 3; ++i) a.w[i] = g.w[i].w;
     a.F = g.F; a.T = g.T; a.n_thr = g.n_thr; a.LA = g.LA; a.NSW = sh.NSW; a.DS = sh.DS; a.NWR = sh.NWR; a.NPS = sh.NPS;
-    { const char *es = getenv("LWS_ONLINE64_STRESS"); a.stress = es ? atoi(es) : 0; }
+    a.stress = env_int("LWS_ONLINE64_STRESS", 0);
     switch (g.Q) {
-    case 2: return launch_q<2>(a, B, sh.lds, sh.amp_lds, stream);
-    case 3: return launch_q<3>(a, B, sh.lds, sh.amp_lds, stream);
-    case 4: return launch_q<4>(a, B, sh.lds, sh.amp_lds, stream);
-    default: return launch_q<8>(a, B, sh.lds, sh.amp_lds, stream);
+    case 2: return launch_q<2>(a, B, sh.lds, sh.amp_lds, one_wave, stream);
+    case 3: return launch_q<3>(a, B, sh.lds, sh.amp_lds, one_wave, stream);
+    case 4: return launch_q<4>(a, B, sh.lds, sh.amp_lds, one_wave, stream);
+    default: return launch_q<8>(a, B, sh.lds, sh.amp_lds, one_wave, stream);
     }
 }
 

@@ -219,15 +219,6 @@ int ctx_leave(DeviceCtx &c, hipStream_t s) {
 struct Factors { int odd, log2e; };
 Factors factor(int n) { Factors f{n, 0}; while (!(f.odd & 1)) { f.odd >>= 1; ++f.log2e; } return f; }
 size_t fft_lds_bytes(int N) { return (size_t)(factor(N).odd > 1 ? 3 : 2) * N * sizeof(float2); }
-// frames of more than 2048 points need more dynamic LDS than a kernel gets by default
-template <typename K> hipError_t allow_lds(K kernel) {
-    static std::atomic<unsigned long long> done{0};   // one bit per device
-    int dev;
-    if (!lws::attr_needed(done, &dev)) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * MAXN * (int)sizeof(float2));
-    if (e == hipSuccess) lws::attr_done(done, dev);
-    return e;
-}
 
 int check_shape(int device, int B, int M, int N, int hop) {
     if (device < 0 || device >= MAX_DEVICES) return lws::set_error(LWS_ERR_INVALID, "device index %d out of range", device);
@@ -236,9 +227,10 @@ int check_shape(int device, int B, int M, int N, int hop) {
     if (hop < 1 || hop > N) return lws::set_error(LWS_ERR_INVALID, "frame shift %d", hop);
     return LWS_OK;
 }
+// frames of more than 2048 points need more dynamic LDS than a kernel gets by default
 int allow_lds_all() {
-    STFT_TRY(allow_lds(k_stft_frames));
-    STFT_TRY(allow_lds(k_istft_frames));
+    STFT_TRY(lws::allow_dynamic_lds<&k_stft_frames>(3 * MAXN * (int)sizeof(float2)));
+    STFT_TRY(lws::allow_dynamic_lds<&k_istft_frames>(3 * MAXN * (int)sizeof(float2)));
     return LWS_OK;
 }
 

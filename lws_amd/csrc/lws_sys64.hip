@@ -49,8 +49,7 @@ constexpr int PFD = 4;       // steps a global load is issued ahead of its use (
 constexpr int LDS_ROWS = 160;
 // spectrograms that go through the skewed scratch at a time (config 2's frames: 7.6 GB for 1024); LWS_S64_CHUNK: for tests
 inline int chunk_size() {
-    const char *v = getenv("LWS_S64_CHUNK");
-    const int c = (v && *v) ? atoi(v) : 1024;
+    const int c = env_int("LWS_S64_CHUNK", 1024);
     return c >= 2 ? c & ~1 : 1024;   // (even: two spectrograms may share a workgroup)
 }
 constexpr uint64_t MASK_Q4 = 0xfd7fc3, MASK_Q2 = 0x5c3, MASK_ALL = ~0ull;   // non-zero weights of the default (sqrt-Hann) windows   // ring rows of 1 KB that fit the LDS
@@ -471,15 +470,10 @@ __global__ void k_s64_store(double2 *state, const double2 *G, int F, int Tp, int
 
 template <int Q, int NS, uint64_t MASK, int WPS = 1>
 hipError_t launch_pass(const S64Args &a, const BaseW<Q> &bw, int B, hipStream_t stream) {
-    static std::atomic<unsigned long long> done{0};
     constexpr int RW = NLN * WPS;
     const size_t lds = (size_t)NS * a.R * RW * sizeof(double2);
-    int dev = 0;
-    if (attr_needed(done, &dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sys64<Q, NS, MASK, WPS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_done(done, dev);
-    }
+    const hipError_t e = allow_dynamic_lds<&k_sys64<Q, NS, MASK, WPS>>(160 * 1024);
+    if (e != hipSuccess) return e;
     k_sys64<Q, NS, MASK, WPS><<<dim3((B + RW / a.nls - 1) / (RW / a.nls)), dim3(NLN * NS * WPS), lds, stream>>>(a, bw);
     return hipGetLastError();
 }

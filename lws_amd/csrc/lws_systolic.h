@@ -47,6 +47,15 @@ hipError_t systolic_io_load(SystolicPlan &sp, const float2 *in, int B, int T, in
 hipError_t systolic_io_run(SystolicPlan &sp, int wsel, const float *thr, const float2 *in, float2 *out, double *partial, int B,
                            int T, int iters, hipStream_t stream, int *launches, hipEvent_t ev0, hipEvent_t ev1);
 
+// What a build of lws_systolic.hip is, from its -D switches (plan creation skips some kinds on request: LWS_SYSTOLIC_NO_SHORT,
+// LWS_SYSTOLIC_NO_TW, LWS_SYSTOLIC_NO_R16 -- comparison runs)
+enum SystolicKind : unsigned {
+    SYSTOLIC_SHORT = 1,   // short frames: two / four sweep slots per wave (LWS_SPW = 2 / 4)
+    SYSTOLIC_TW = 2,      // twiddles from a table (LWS_TW)
+    SYSTOLIC_TWQ = 4,     // ... on the ring of exactly 5 / 6 frames per stencil row (LWS_TWQ)
+    SYSTOLIC_R16 = 8,     // Q = 2 on a 16-step ring (LWS_R16)
+};
+
 // One compilation of lws_systolic.hip, as a table: a plan is served by the first build whose systolic_build() accepts its
 // shape and weights (lws_capi.hip tries them in the order below).
 struct SystolicBuild {
@@ -59,6 +68,7 @@ struct SystolicBuild {
     decltype(&systolic_io_partials) io_partials;
     decltype(&systolic_io_load) io_load;
     decltype(&systolic_io_run) io_run;
+    unsigned kind;        // SystolicKind bits
 };
 const SystolicBuild &systolic_entry();                            // Q in {2, 4}, frames of up to 513 bins: 7 sweep slots
 namespace q8 { const SystolicBuild &systolic_entry(); }           // -DLWS_Q8=1: Q = 8, 64-step ring, 2 sweep slots

@@ -32,7 +32,7 @@
 // edge reads its image taps there.  The Nyquist bin (bin F-1) does not fit the 512-step frame period and is
 // computed by the service wave (one lane per sweep in flight), which also runs the loader.
 //
-// Scope of this file (one source, fifteen builds: the -D switches below): weights with the twiddle structure create_weights produces
+// Scope of this file (one source, seventeen builds: the -D switches below): weights with the twiddle structure create_weights produces
 // (lws.pyx:160-181: W[p][r][k] = W[0][r][k] exp(2j pi p r s / P), summarised or general tensors), fp32 arithmetic, fp32 or fp16
 // storage, F-1 even (a multiple of 8, or a frame end inside a block of 8 steps: one instantiation per phase, th0) and >= 16:
 //   static twiddles (P = Q, s = 1): Q in {2,4}, L <= 5, F-1 <= 512 (narrow; half / quarter: <= 256 / 128 with 2 / 4 sweep slots
@@ -41,7 +41,8 @@
 //   table twiddles: tw, tw_half, tw_wide -- Q in {3,4} with any P <= 128: Q = 3, and the general weights of a hop that does not
 //     divide the frame -- L <= 5, F-1 <= 1024; tw_q8 -- 5 to 8 frames per stencil row (Q in {5,6,7}, fractional Q above 4) on the
 //     Q = 8 build's geometry, L <= 5, F-1 <= 512.
-// Anything else (hop < frame / 8, L >= 8, F-1 > 2048, weights without the structure, fp64) is served by the generic engine.
+// Anything else (hop < frame / 8, L >= 8, F-1 > 2048, weights without the structure, fp64) goes to the engines after this one in
+// lws_capi.hip's choose_engine (band, sys64 for fp64 plans, the generic engine).
 #include "lws_common.h"
 #include "lws_systolic.h"
 
@@ -2483,14 +2484,8 @@ __global__ void __launch_bounds__(256) k_skew_to_out(float2 *out, const float2 *
 constexpr uint64_t mask_all(int Q, int L) { return (1ull << (Q * (L + 1))) - 1ull; }
 
 template <int Q, int L, uint64_t MASK, bool MULTI, bool H16, int RE> hipError_t launch_km(const SysArgs &a, int grid, hipStream_t s) {
-    static std::atomic<unsigned long long> attr_set{0};   // one bit per device
-    int attr_dev;
-    if (lws::attr_needed(attr_set, &attr_dev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_systolic<Q, L, MASK, MULTI, H16, RE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return e;
-        lws::attr_done(attr_set, attr_dev);
-    }
+    const hipError_t e = lws::allow_dynamic_lds<&k_systolic<Q, L, MASK, MULTI, H16, RE>>(LDS_BYTES);
+    if (e != hipSuccess) return e;
     if constexpr (MULTI) {
         // The workgroups of a spectrogram wait for each other: all of the grid must be resident at once.  prepare() sizes the
         // grid to at most one workgroup per CU; here the other half of that argument is checked against the runtime's own
@@ -2753,11 +2748,11 @@ hipError_t prepare(SystolicPlan &sp, int B, int T, int iters, Geom &g) {
     // each workgroup trails its producer by NSLOTS*LAG + 56 rows, and the first one starts its next pass G rows after
     // its previous one: the lags around the ring must fit into one pass
     const int ring_max = g.G / (NSLOTS * LAG + 96);
-    const char *ev = getenv("LWS_SYSTOLIC_NWG");
+    const int forced = lws::env_int("LWS_SYSTOLIC_NWG", 0);
     auto pick = [&](int nb) {
         int n = nb > 0 ? n_cu / nb : 1;
         if (n > n_pass_max) n = n_pass_max;
-        if (ev) { const int v = atoi(ev); if (v >= 1 && (long)v * nb <= n_cu) n = v; }
+        if (forced >= 1 && (long)forced * nb <= n_cu) n = forced;
         if (n > ring_max) n = ring_max;
         return n < 1 ? 1 : n;
     };
@@ -2810,14 +2805,9 @@ hipError_t launch_update(SystolicPlan &sp, const Geom &g, int wsel, const float 
     a.n_iters = n_it;
     a.T = T; a.Tp = g.Tp; a.TpPad = g.TpPad; a.Kr = g.Kr; a.G = g.G; a.C = F - 1;
     a.nwg = nwg; a.progress = progress; a.err = g.err; a.gate = gate;
-    {
-        const char *ev = getenv("LWS_SYSTOLIC_SPIN_LIMIT");   // polls (of ~0.2 us) before a workgroup gives up on its producer
-        a.spin_limit = ev ? atoi(ev) : (1 << 21);
-        const char *es = getenv("LWS_SYSTOLIC_STRESS");
-        a.stress = es ? atoi(es) : 0;
-        const char *er = getenv("LWS_SYSTOLIC_ROLEMAP");
-        a.rolemap = er ? atoi(er) : 0;
-    }
+    a.spin_limit = lws::env_int("LWS_SYSTOLIC_SPIN_LIMIT", 1 << 21);   // polls (of ~0.2 us) before a workgroup gives up on its producer
+    a.stress = lws::env_int("LWS_SYSTOLIC_STRESS", 0);
+    a.rolemap = lws::env_int("LWS_SYSTOLIC_ROLEMAP", 0);
     a.tw_table = tb->tw_dev; a.tw_P = tb->tw_P > 0 ? tb->tw_P : 1; a.tw_invP = 1.0f / (float)a.tw_P;
     for (int r = 0; r < 8; ++r) {
         unsigned ur, ui;
@@ -3051,7 +3041,9 @@ hipError_t systolic_io_run(SystolicPlan &sp, int wsel, const float *thr, const f
 
 const SystolicBuild &systolic_entry() {
     static const SystolicBuild b = {systolic_build, systolic_release, systolic_supports, systolic_reserve, systolic_name,
-                                    launch_systolic, systolic_io_partials, systolic_io_load, systolic_io_run};
+                                    launch_systolic, systolic_io_partials, systolic_io_load, systolic_io_run,
+                                    (LWS_SPW != 1 ? SYSTOLIC_SHORT : 0u) | (LWS_TW ? SYSTOLIC_TW : 0u) | (LWS_TWQ ? SYSTOLIC_TWQ : 0u) |
+                                        (LWS_R16 ? SYSTOLIC_R16 : 0u)};
     return b;
 }
 

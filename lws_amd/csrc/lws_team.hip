@@ -655,8 +655,8 @@ TeamGeom geometry(int mode, int F, int T, int L, int Q, int LA, int n_thr) {
     if (tg.nunits <= 0 || tg.nunits > 512) return TeamGeom{0, 0, 0};
     int G = pow2_floor(1024 / tg.nunits);
     if (G > 64) G = 64;
-    const char *ev = getenv("LWS_TEAM_LANES");   // comparison runs: at most this many lanes per bin (1: the generic engine's order of terms)
-    if (ev && atoi(ev) >= 1 && atoi(ev) < G) G = pow2_floor(atoi(ev));
+    const int lanes = env_int("LWS_TEAM_LANES", 0);   // comparison runs: at most this many lanes per bin (1: the generic engine's order of terms)
+    if (lanes >= 1 && lanes < G) G = pow2_floor(lanes);
     tg.G = G;
     return tg;
 }
@@ -683,21 +683,13 @@ RingGeom ring_geometry(const TeamGeom &tg, int F, int L, int Q, int Qp, int LA, 
     }
     rg.bytes = (unsigned)off;
     rg.fits = 1;                                                // (... whether or not LWS_TEAM_NO_RING sends the call to the other kernel)
-    const char *ev = getenv("LWS_TEAM_NO_RING");                // comparison runs: the state stays in memory
-    if (ev && atoi(ev)) rg.bytes = 0;
-    { const char *ep = getenv("LWS_TEAM_DBG_POISON"); rg.poison = (ep && atoi(ep) && rg.bytes && rg.bytes + 16384 <= cap) ? 1 : 0; }
+    if (env_int("LWS_TEAM_NO_RING", 0)) rg.bytes = 0;          // comparison runs: the state stays in memory
+    rg.poison = (env_int("LWS_TEAM_DBG_POISON", 0) && rg.bytes && rg.bytes + 16384 <= cap) ? 1 : 0;
     return rg;
-}
-
-// fp64 plans: the order-exact online kernel unless LWS_TEAM_FP64=1 asks for the re-associating ones; fp32 plans: with LWS_TEAM_ORDERED=1
-bool team_ordered(bool fp64) {
-    const char *eo = getenv("LWS_TEAM_ORDERED"), *ef = getenv("LWS_TEAM_FP64");
-    return fp64 ? !(ef && atoi(ef)) : (eo && atoi(eo));
 }
 
 }  // namespace
 
-bool team_online_is_ordered(bool fp64) { return team_ordered(fp64); }
 bool team_ordered_fits(int F, int T, int L, int Q, int LA, int n_thr, bool fp64) {
     const TeamGeom tg = geometry(MODE_ONLINE, F, T, L, Q, LA, n_thr);
     if (tg.G < 1) return false;
@@ -711,7 +703,7 @@ bool team_supports(int mode, int F, int T, int L, int Q, int Qp, int LA, int n_t
     if (F < 2 || T < 1 || L < 1 || Q < 2 || Q > 255 || Qp < 1 || n_thr < 1) return false;
     const int NT = L + (Q - 1) * (2 * L + 1);
     if ((size_t)NT * sizeof(Term) > 60 * 1024) return false;
-    return geometry(mode, F, T, L, Q, LA, n_thr).G >= (getenv("LWS_TEAM_LANES") ? 1 : 2);
+    return geometry(mode, F, T, L, Q, LA, n_thr).G >= (env_int("LWS_TEAM_LANES", 0) ? 1 : 2);
 }
 
 bool team_online_in_lds(bool fp64, int F, int T, int L, int Q, int Qp, int LA, int n_thr) {
@@ -723,8 +715,18 @@ bool team_online_in_lds(bool fp64, int F, int T, int L, int Q, int Qp, int LA, i
 
 int team_lanes(int mode, int F, int T, int L, int Q, int LA, int n_thr) { return geometry(mode, F, T, L, Q, LA, n_thr).G; }
 
+namespace {
+template <auto Kernel, typename real>
+hipError_t launch_ring(const GenericArgs<real> &a, const TeamGeom &tg, const RingGeom &rg, int B, int threads, hipStream_t stream) {
+    const hipError_t e = allow_dynamic_lds<Kernel>(160 * 1024);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(Kernel, dim3(B), dim3(threads), rg.bytes + (rg.poison ? 16384 : 0), stream, a, tg, rg);
+    return hipGetLastError();
+}
+}  // namespace
+
 template <typename real>
-hipError_t launch_team(const GenericArgs<real> &a, int B, hipStream_t stream) {
+hipError_t launch_team(const GenericArgs<real> &a, int B, bool ordered, hipStream_t stream) {
     if (B <= 0) return hipSuccess;
     TeamGeom tg = geometry(a.mode, a.F, a.T, a.L, a.Q, a.LA, a.n_thr);
     if (tg.G < 1) return hipErrorInvalidValue;
@@ -732,20 +734,15 @@ hipError_t launch_team(const GenericArgs<real> &a, int B, hipStream_t stream) {
     if (threads > 1024) threads = 1024;
     const int NT = a.L + (a.Q - 1) * (2 * a.L + 1);
     const size_t lds = (size_t)NT * sizeof(Term);
-    if (a.mode == MODE_ONLINE && team_ordered(sizeof(real) == 8)) {
+    if (a.mode == MODE_ONLINE && ordered) {
         // order-exact variant (fp64 plans by default; LWS_TEAM_ORDERED=1: fp32 plans too)
         const int NTP = (NT + 1) | 1;                                  // (odd row length: the bins' chains read different banks)
         auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
         const size_t off_inc = up16((size_t)NT * sizeof(Term)), off_unit = up16(off_inc + (size_t)tg.nunits * NTP * 2 * sizeof(real));
         const size_t bytes = off_unit + (size_t)tg.nunits * sizeof(OrdUnit<real>);
         if (bytes > 160 * 1024) return hipErrorInvalidValue;           // (team_supports said no)
-        static std::atomic<unsigned long long> done{0};
-        int dev;
-        if (attr_needed(done, &dev)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_team_online_ordered<real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            attr_done(done, dev);
-        }
+        const hipError_t e = allow_dynamic_lds<&k_team_online_ordered<real>>(160 * 1024);
+        if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_team_online_ordered<real>, dim3(B), dim3(threads), bytes, stream, a, tg, (unsigned)off_inc, (unsigned)off_unit, NTP);
         return hipGetLastError();
     }
@@ -756,10 +753,10 @@ hipError_t launch_team(const GenericArgs<real> &a, int B, hipStream_t stream) {
         // fp64), not the largest the workgroup has room for: lws(1024,256,L=8) 366 -> 298 ms with 8 lanes a bin instead of 16.  (The
         // kernel that leaves the state in memory runs with the same teams when it stands in for the ring kernel: same bits.)
         int nch = 2;
-        if (rg.fits && !getenv("LWS_TEAM_LANES")) {
+        if (rg.fits && !env_int("LWS_TEAM_LANES", 0)) {
             auto smallest = [&](int nc) { int gp = 1; while (gp * nc < NT) gp *= 2; return gp; };
             int gp = smallest(sizeof(real) == 8 ? 4 : 8);
-            if (sizeof(real) == 4 && !getenv("LWS_TEAM_NO_NCH3")) {            // (fp32: three chunks in registers if that halves the team
+            if (sizeof(real) == 4) {                                           // (fp32: three chunks in registers if that halves the team
                 const int g3 = smallest(12);                                      //  and the workgroup stays within 512 threads)
                 if (g3 < gp && g3 <= tg.G && tg.nunits * g3 <= 512) { gp = g3; nch = 3; }
             }
@@ -768,28 +765,19 @@ hipError_t launch_team(const GenericArgs<real> &a, int B, hipStream_t stream) {
                 threads = ((tg.nunits * tg.G + 63) / 64) * 64;
             } else nch = 2;
         }
-        { const char *e3 = getenv("LWS_TEAM_NCH3"); if (e3 && atoi(e3) && rg.fits && threads <= 512) nch = 3; }   // (tests: the three-chunk kernel whatever the team)
+        if (env_int("LWS_TEAM_NCH3", 0) && rg.fits && threads <= 512) nch = 3;   // (tests: the three-chunk kernel whatever the team)
         if (rg.bytes) {
-            auto launch = [&](auto kern) {
-                static std::atomic<unsigned long long> done{0};
-                int dev;
-                if (attr_needed(done, &dev)) {
-                    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                    if (e != hipSuccess) return e;
-                    attr_done(done, dev);
-                }
-                hipLaunchKernelGGL(kern, dim3(B), dim3(threads), rg.bytes + (rg.poison ? 16384 : 0), stream, a, tg, rg);
-                return hipGetLastError();
-            };
-            if (nch == 3) return rg.wl ? launch(&k_team_online_ring<real, true, 3>) : launch(&k_team_online_ring<real, false, 3>);
-            return rg.wl ? launch(&k_team_online_ring<real, true, 2>) : launch(&k_team_online_ring<real, false, 2>);
+            if (nch == 3) return rg.wl ? launch_ring<&k_team_online_ring<real, true, 3>>(a, tg, rg, B, threads, stream)
+                                       : launch_ring<&k_team_online_ring<real, false, 3>>(a, tg, rg, B, threads, stream);
+            return rg.wl ? launch_ring<&k_team_online_ring<real, true, 2>>(a, tg, rg, B, threads, stream)
+                         : launch_ring<&k_team_online_ring<real, false, 2>>(a, tg, rg, B, threads, stream);
         }
         hipLaunchKernelGGL(k_team_online<real>, dim3(B), dim3(threads), lds, stream, a, tg);
     } else hipLaunchKernelGGL(k_team_sweeps<real>, dim3(B), dim3(threads), lds, stream, a, tg);
     return hipGetLastError();
 }
 
-template hipError_t launch_team<float>(const GenericArgs<float> &, int, hipStream_t);
-template hipError_t launch_team<double>(const GenericArgs<double> &, int, hipStream_t);
+template hipError_t launch_team<float>(const GenericArgs<float> &, int, bool, hipStream_t);
+template hipError_t launch_team<double>(const GenericArgs<double> &, int, bool, hipStream_t);
 
 }  // namespace lws
