@@ -132,9 +132,14 @@ int lws_weights_structure(const double *W, int Q, int Qp, int L, int *period, in
 int lws_plan_reserve(lws_plan *plan, int B, int T, int max_iters);
 
 /* Consistency-residual proxy: for each spectrogram b
- *   out[2b]   = sum over bins of |acc + w00*S|^2   (acc = the LWS weighted sum, w00 = W[0][0][0])
+ *   out[2b]   = sum over bins of |acc + w00*S|^2   (acc = the LWS weighted sum of the bin without its centre tap,
+ *                                                   w00 = W[bin % Qp][0][0], which holds create_weights' -1)
  *   out[2b+1] = sum over bins of |S|^2
- * in fp64, on the device buffer `S_dev`.  out is a HOST array of 2*B doubles (synchronises). */
+ * in fp64, on the device buffer `S_dev` (complex64 for fp32 and fp16-storage plans, complex128 for fp64 plans; left unchanged).
+ * out is a HOST array of 2*B doubles (synchronises).  Every plan computes it with W (never W_ai / W_af) on the generic accumulate.
+ * Edge frames enter with the replicated neighbours of extspec (lws.pyx:146-157), as in a batch sweep.  On interior frames
+ * 10 log10(out[2b+1] / out[2b]) agrees with the true inconsistency sum |stft(istft(S)) - S|^2 to about 0.2 dB, but the L-bin
+ * truncation floors it near 40 dB at L = 5 (a consistent STFT reads ~40 dB, not ~300): it is not get_consistency. */
 int lws_residual_dev(lws_plan *plan, const void *S_dev, int B, int T, double *out, void *stream);
 /* The same for HOST spectrograms S[B][T][F] complex128. */
 int lws_residual(lws_plan *plan, const double *S, int B, int T, double *out);

@@ -221,6 +221,10 @@ def test_device_resident_entry_points():
     assert info["launches"] >= 1 and info["ms"] > 0
     res = p.plan().residual_dev(t.data_ptr(), 3, 16)
     assert res.shape == (3, 2) and (res > 0).all() and (res[:, 0] < res[:, 1]).all()
+    from residual_model import residual_pairs    # the fp64 restatement (tests/test_gpu_residual.py has the full sweep)
+    ref = residual_pairs(dev.astype(np.complex128), p.W)
+    np.testing.assert_allclose(res[:, 1], ref[:, 1], rtol=1e-12, atol=0)
+    np.testing.assert_allclose(res[:, 0], ref[:, 0], rtol=1e-4, atol=0)
 
 
 def test_config_scale_against_oracle_and_fingerprint(oracle):
