@@ -181,7 +181,7 @@ struct lws_plan {
     int band_tab_lt[3] = {0, 0, 0};
     HostPipe pipe;                 // host-array entry points: pinned staging, chunk buffers, streams
     lws::SystolicPlan sys;         // device tables of the systolic kernel (empty if not eligible)
-    const lws::SystolicBuild *sysb = nullptr;   // the build of it that serves this plan (narrow / Q = 8 / wide), if any
+    const lws::SystolicBuild *sysb = nullptr;   // the build of it that serves this plan (a row of lws_systolic_builds.h), if any
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     void *host_pool = nullptr;     // HostWorkers of the host-array entry points (kept between calls: 32 thread starts cost ~1 ms)
     int host_pool_n = 0;
@@ -1133,17 +1133,14 @@ int lws_plan_create(lws_plan **plan, int device, int F, int L, int Q, int Qp, co
                                p->have[2] ? p->hostW[2].data() : nullptr};
         const bool h16 = (flags & LWS_STORAGE_FP16) != 0;
         hipError_t e = hipSuccess;
-        // the first build that takes the shape: short frames (<= 129 / 257 bins: four / two sweep slots per wave), up to 513 bins,
-        // Q = 8, up to 1025 bins.  LWS_SYSTOLIC_NO_SHORT=1, _NO_TW=1, _NO_R16=1 skip kinds of builds (comparison runs)
+        // the first build that takes the shape, in the order of lws_systolic_builds.h.  LWS_SYSTOLIC_NO_SHORT=1, _NO_TW=1, _NO_R16=1 skip
+        // kinds of builds (comparison runs)
         const unsigned skip = (env_int("LWS_SYSTOLIC_NO_SHORT", 0) ? lws::SYSTOLIC_SHORT : 0u) | (env_int("LWS_SYSTOLIC_NO_TW", 0) ? lws::SYSTOLIC_TW : 0u) |
                               (env_int("LWS_SYSTOLIC_NO_R16", 0) ? lws::SYSTOLIC_R16 : 0u);
-        for (const lws::SystolicBuild *b : {&lws::quarter_q2::systolic_entry(), &lws::quarter::systolic_entry(), &lws::half_q2::systolic_entry(), &lws::half::systolic_entry(),
-                                            &lws::q2::systolic_entry(), &lws::systolic_entry(),
-                                            &lws::q8::systolic_entry(), &lws::wide_q2::systolic_entry(), &lws::wide::systolic_entry(), &lws::xwide::systolic_entry(), &lws::l7::systolic_entry(),
-                                            // ... then the table-twiddle builds: Q = 3, and general weights of a hop that does not divide the frame
-                                            &lws::tw_half::systolic_entry(), &lws::tw::systolic_entry(), &lws::tw_wide::systolic_entry(),
-                                            // (exactly 5 / 6 frames per stencil row: the builds with their own ring depth first)
-                                            &lws::tw_q5::systolic_entry(), &lws::tw_q6::systolic_entry(), &lws::tw_q8::systolic_entry()}) {
+        int n_builds = 0;
+        const lws::SystolicBuild *const *builds = lws::systolic_builds(&n_builds);
+        for (int i = 0; i < n_builds; ++i) {
+            const lws::SystolicBuild *b = builds[i];
             if (b->kind & skip) continue;
             if ((e = b->build(p->sys, F, L, Q, Qp, hw, h16)) != hipSuccess) break;
             // the build must take the tensor batch sweeps normally run on -- W, the first one present -- : a build that only takes

@@ -2,9 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-namespace lws {
+#include "lws_systolic_builds.h"
 
-constexpr int SYSTOLIC_MAX_ITERS = 440;  // thresholds of one launch live in LDS; longer schedules run as several launches
+namespace lws {
 
 struct SystolicPlan {
     bool ok[3] = {false, false, false};  // per weight tensor: kernel applicable
@@ -20,7 +20,7 @@ struct SystolicPlan {
                               // then re-run with one workgroup per spectrogram, on the device, before it completed)
     int last_nwg = 1;         // workgroups per spectrogram of the last launch
     bool h16 = false;         // fp16-complex storage of the skewed layout (LWS_STORAGE_FP16)
-    void *thr_chunk = nullptr;   // dense threshold table of one launch of a schedule longer than SYSTOLIC_MAX_ITERS
+    void *thr_chunk = nullptr;   // dense threshold table of one launch of a schedule longer than one launch holds (MAX_ITERS)
     size_t thr_chunk_cap = 0;
 };
 
@@ -47,7 +47,7 @@ hipError_t systolic_io_load(SystolicPlan &sp, const float2 *in, int B, int T, in
 hipError_t systolic_io_run(SystolicPlan &sp, int wsel, const float *thr, const float2 *in, float2 *out, double *partial, int B,
                            int T, int iters, hipStream_t stream, int *launches, hipEvent_t ev0, hipEvent_t ev1);
 
-// What a build of lws_systolic.hip is, from its -D switches (plan creation skips some kinds on request: LWS_SYSTOLIC_NO_SHORT,
+// What a build of lws_systolic.hip is, from its switches (plan creation skips some kinds on request: LWS_SYSTOLIC_NO_SHORT,
 // LWS_SYSTOLIC_NO_TW, LWS_SYSTOLIC_NO_R16 -- comparison runs)
 enum SystolicKind : unsigned {
     SYSTOLIC_SHORT = 1,   // short frames: two / four sweep slots per wave (LWS_SPW = 2 / 4)
@@ -56,8 +56,7 @@ enum SystolicKind : unsigned {
     SYSTOLIC_R16 = 8,     // Q = 2 on a 16-step ring (LWS_R16)
 };
 
-// One compilation of lws_systolic.hip, as a table: a plan is served by the first build whose systolic_build() accepts its
-// shape and weights (lws_capi.hip tries them in the order below).
+// One compilation of lws_systolic.hip (a row of lws_systolic_builds.h), as a table of its entry points.
 struct SystolicBuild {
     decltype(&systolic_build) build;
     decltype(&systolic_release) release;
@@ -70,23 +69,21 @@ struct SystolicBuild {
     decltype(&systolic_io_run) io_run;
     unsigned kind;        // SystolicKind bits
 };
-const SystolicBuild &systolic_entry();                            // Q in {2, 4}, frames of up to 513 bins: 7 sweep slots
-namespace q8 { const SystolicBuild &systolic_entry(); }           // -DLWS_Q8=1: Q = 8, 64-step ring, 2 sweep slots
-namespace wide { const SystolicBuild &systolic_entry(); }         // -DLWS_WIDE=1: frames of up to 1025 bins, two waves per sweep
-                                                                  // slot, 3 slots
-namespace xwide { const SystolicBuild &systolic_entry(); }        // -DLWS_WIDE=2: frames of up to 2049 bins, four waves per sweep slot, 1 slot
-namespace q2 { const SystolicBuild &systolic_entry(); }           // -DLWS_R16=1: Q = 2 with a 16-step ring: 15 sweep slots, frames <= 513 bins
-namespace wide_q2 { const SystolicBuild &systolic_entry(); }      // -DLWS_WIDE=1 -DLWS_R16=1: the same for frames of up to 1025 bins (7 slots of two waves)
-namespace half_q2 { const SystolicBuild &systolic_entry(); }      // -DLWS_SPW=2 -DLWS_R16=1: ... of up to 257 bins (26 slots on 13 waves)
-namespace quarter_q2 { const SystolicBuild &systolic_entry(); }   // -DLWS_SPW=4 -DLWS_R16=1: ... of up to 129 bins (44 slots on 11 waves)
-namespace l7 { const SystolicBuild &systolic_entry(); }           // -DLWS_L7=1: L = 6, 7 (frames 16 steps apart, 64-step ring, 3 slots), <= 513 bins
-namespace half { const SystolicBuild &systolic_entry(); }         // -DLWS_SPW=2: frames of up to 257 bins, two sweep slots per wave (14)
-namespace quarter { const SystolicBuild &systolic_entry(); }      // -DLWS_SPW=4: frames of up to 129 bins, four sweep slots per wave (24)
-namespace tw { const SystolicBuild &systolic_entry(); }           // -DLWS_TW=1: twiddles from a table -- Q = 3, general weights of a fractional Q (Q <= 4), <= 513 bins
-namespace tw_wide { const SystolicBuild &systolic_entry(); }      // -DLWS_TW=1 -DLWS_WIDE=1: the same for frames of up to 1025 bins (two waves per sweep slot)
-namespace tw_q8 { const SystolicBuild &systolic_entry(); }        // -DLWS_TW=1 -DLWS_Q8=1: table twiddles on the 64-step ring with helper waves: ceil(frame/hop) in 5..8
-namespace tw_q5 { const SystolicBuild &systolic_entry(); }        // ... -DLWS_TWQ=5: exactly 5 frames per stencil row on a 40-step ring: 3 sweep slots of a main and a helper wave
-namespace tw_q6 { const SystolicBuild &systolic_entry(); }        // ... -DLWS_TWQ=6: 6 frames per row, 48-step ring, 3 slots
-namespace tw_half { const SystolicBuild &systolic_entry(); }      // -DLWS_TW=1 -DLWS_SPW=2: the same for frames of up to 257 bins (25 ms / 10 ms speech framing)
 
+}  // namespace lws
+
+// every build's entry, in its namespace ...
+#define LWS_DECLARE_ENTRY(name) namespace LWS_ROW_FIELD(NS, name) { const lws::SystolicBuild &systolic_entry(); }
+LWS_SYSTOLIC_BUILDS(LWS_DECLARE_ENTRY)
+#undef LWS_DECLARE_ENTRY
+
+namespace lws {
+// ... and all of them in the order plan creation tries them (internal linkage: the library exports no symbol for it)
+static inline const SystolicBuild *const *systolic_builds(int *n) {
+#define LWS_ENTRY_PTR(name) &LWS_ROW_FIELD(NS, name)::systolic_entry(),
+    static const SystolicBuild *const builds[] = {LWS_SYSTOLIC_BUILDS(LWS_ENTRY_PTR)};
+#undef LWS_ENTRY_PTR
+    *n = (int)(sizeof builds / sizeof builds[0]);
+    return builds;
+}
 }  // namespace lws

@@ -32,7 +32,7 @@
 // edge reads its image taps there.  The Nyquist bin (bin F-1) does not fit the 512-step frame period and is
 // computed by the service wave (one lane per sweep in flight), which also runs the loader.
 //
-// Scope of this file (one source, seventeen builds: the -D switches below): weights with the twiddle structure create_weights produces
+// Scope of this file (one source, one build per row of lws_systolic_builds.h: the switches below): weights with the twiddle structure create_weights produces
 // (lws.pyx:160-181: W[p][r][k] = W[0][r][k] exp(2j pi p r s / P), summarised or general tensors), fp32 arithmetic, fp32 or fp16
 // storage, F-1 even (a multiple of 8, or a frame end inside a block of 8 steps: one instantiation per phase, th0) and >= 16:
 //   static twiddles (P = Q, s = 1): Q in {2,4}, L <= 5, F-1 <= 512 (narrow; half / quarter: <= 256 / 128 with 2 / 4 sweep slots
@@ -56,77 +56,64 @@
 #include <utility>
 #include <vector>
 
-// The file is compiled twice: as is (frames of up to 513 bins: a round of 64 frames, one wave per sweep slot, 7 sweep slots)
-// and with -DLWS_WIDE=1 into namespace lws::wide (frames of up to 1025 bins: a lane needs 1024 steps per frame, so a round
-// is 128 frames = TWO waves per sweep slot on a ring row of 128 lanes, with the same 8-step skew, 32-step lag and ring
-// depth; 3 sweep slots (6 compute waves) and two service waves, one per half of the row, fit the LDS).
-#ifndef LWS_WIDE
-#define LWS_WIDE 0
+// One source, one build per row of lws_systolic_builds.h (-DLWS_BUILD=<row>; none: narrow).  The row gives the namespace, the tag in the
+// kernel's name, the sweep slots and the switches below; the narrow build has them all off: frames of up to 513 bins, a round of 64
+// frames, one wave per sweep slot, 7 sweep slots.
+#ifndef LWS_BUILD
+#define LWS_BUILD narrow
 #endif
-// ... and a third time with -DLWS_Q8=1 into namespace lws::q8 for Q = 8 (hop = window / 8, frames of up to 513 bins): the
-// taps reach 7 frames either way, so the lag between sweeps and the ring are 64 steps deep (LAG > 8 (Q-1) + L), the halo is
-// 7 lanes, and 2 sweep slots (one wave each) fit the LDS.  Half of the twiddles exp(2j pi (bin % 8) r / 8) are odd eighth
-// turns: a second weight set, W[0][r][k] exp(j pi / 4), serves those, and the 96 weights live in VGPRs (three waves per
-// workgroup, one per SIMD: registers are plentiful, SGPRs are not).
-#ifndef LWS_Q8
-#define LWS_Q8 0
-#endif
+#define LWS_NS LWS_ROW_FIELD(NS, LWS_BUILD)
+#define LWS_NAME_TAG LWS_ROW_FIELD(TAG, LWS_BUILD)
+// LWS_WIDE = 1: frames of up to 1025 bins.  A lane needs 1024 steps per frame, so a round is 128 frames = TWO waves per sweep slot on
+// a ring row of 128 lanes, with the same 8-step skew, 32-step lag and ring depth; 3 sweep slots (6 compute waves) and two service
+// waves, one per half of the row, fit the LDS.  LWS_WIDE = 2: frames of up to 2049 bins, four waves per slot (WPS below).
+#define LWS_WIDE LWS_ROW_FIELD(WIDE, LWS_BUILD)
+// LWS_Q8: Q = 8 (hop = window / 8, frames of up to 513 bins).  The taps reach 7 frames either way, so the lag between sweeps and the
+// ring are 64 steps deep (LAG > 8 (Q-1) + L), the halo is 7 lanes, and 2 sweep slots (one wave each) fit the LDS.  Half of the
+// twiddles exp(2j pi (bin % 8) r / 8) are odd eighth turns: a second weight set, W[0][r][k] exp(j pi / 4), serves those, and the 96
+// weights live in VGPRs (three waves per workgroup, one per SIMD: registers are plentiful, SGPRs are not).
+#define LWS_Q8 LWS_ROW_FIELD(Q8, LWS_BUILD)
 #ifndef LWS_SPLIT_ROLES
 #define LWS_SPLIT_ROLES 1
 #endif
-// ... and with -DLWS_SPW=2 (namespace lws::half) / -DLWS_SPW=4 (lws::quarter) for SHORT frames, of up to 257 / 129 bins (512- and
-// 256-point STFTs: 16 kHz speech).  A lane of the narrow build needs 512 steps per frame whatever its length, so a 257-bin
-// frame left it idle half of the time.  Here a round is 32 (16) frames = 256 (128) steps, and a wave carries SPW sweep slots
-// side by side: lanes [32 s, 32 s + 32) of compute wave w are the 32 frames of sweep slot w SPW + s, which trails slot
-// w SPW + s - 1 -- its neighbours in the same wave, or the last slot of the wave before -- by the usual 32 steps.  Same skew,
-// lag, ring depth and per-bin code; 14 (24) sweep slots per pass over HBM instead of 7; the two halves of a wave are always
-// in the same pair, so the flow control between waves is unchanged.
-#ifndef LWS_SPW
-#define LWS_SPW 1
-#endif
-// ... and with -DLWS_L7=1 (namespace lws::l7) for stencils of half-width 6 and 7 (Q in {2, 4}, frames of up to 513 bins).  A lane
-// works on two bins per rendez-vous, so the newest tap of a pair's second bin, (m-1, c+1+L), must be two steps old when the
-// pair starts: with the usual skew of 8 steps between frames that holds for L <= 5 only.  Here frame m trails frame m-1 by
-// SKEW = 16 steps (two blocks): the tap is 8 steps old, no frame is "late", the lag between sweeps and the ring are 64 steps
-// (LAG > 16 (Q-1) + L), three sweep slots fit the LDS, and a lane's frame period is 1024 steps -- a lane is idle at least
-// half of the time.  A quarter of the narrow build's rate; the generic engine these shapes used to get is 5x slower still.
-#ifndef LWS_L7
-#define LWS_L7 0
-#endif
-// ... and with -DLWS_R16=1 (namespace lws::q2) for Q = 2 (hop = half a frame, the reference's LWSQ2; frames of up to 513 bins).  The
-// taps reach one frame either way, so a lag of 16 steps between sweeps is enough (LAG > 8 (Q-1) + L = 13) and the ring is 16
-// steps deep: sets of 9 KB instead of 18, FIFTEEN sweep slots in the same LDS -- one wave each, four waves per SIMD (the Q = 2
-// kernels need ~115 VGPRs).  Throughput follows the number of waves that run a dependent chain.
-#ifndef LWS_R16
-#define LWS_R16 0
-#endif
-// (LWS_R16 also combines with LWS_WIDE=1 -- namespace lws::wide_q2, frames of up to 1025 bins: seven sweep slots of two waves
-//  instead of three)
-// (... and with LWS_SPW=2 / 4 -- lws::half_q2, lws::quarter_q2, frames of up to 257 / 129 bins: 26 / 44 sweep slots)
-// ... and with -DLWS_TW=1 (namespace lws::tw; with -DLWS_SPW=2: lws::tw_half) for weights whose twiddle is NOT a multiple of an
-// eighth turn: Q = 3 (hop = a third of the frame), and the "general" weights create_weights builds for a hop that does not
-// divide the frame (lws.pyx:164-181: Q' = N rows, one per bin; e.g. 25 ms frames every 10 ms, lws(400, 160): Q = 3, Qfloat = 2.5),
-// the reference's LWSanyQ with Q = 3 and its LWSfractionalQ (lwslib.cpp:283-467).  Those tensors still are
+// LWS_SPW = 2 / 4: SHORT frames, of up to 257 / 129 bins (512- and 256-point STFTs: 16 kHz speech).  A lane of the narrow build needs
+// 512 steps per frame whatever its length, so a 257-bin frame left it idle half of the time.  Here a round is 32 (16) frames = 256
+// (128) steps, and a wave carries SPW sweep slots side by side: lanes [32 s, 32 s + 32) of compute wave w are the 32 frames of sweep
+// slot w SPW + s, which trails slot w SPW + s - 1 -- its neighbours in the same wave, or the last slot of the wave before -- by the
+// usual 32 steps.  Same skew, lag, ring depth and per-bin code; 14 (24) sweep slots per pass over HBM instead of 7; the two halves
+// of a wave are always in the same pair, so the flow control between waves is unchanged.
+#define LWS_SPW LWS_ROW_FIELD(SPW, LWS_BUILD)
+// LWS_L7: stencils of half-width 6 and 7 (Q in {2, 4}, frames of up to 513 bins).  A lane works on two bins per rendez-vous, so the
+// newest tap of a pair's second bin, (m-1, c+1+L), must be two steps old when the pair starts: with the usual skew of 8 steps between
+// frames that holds for L <= 5 only.  Here frame m trails frame m-1 by SKEW = 16 steps (two blocks): the tap is 8 steps old, no frame
+// is "late", the lag between sweeps and the ring are 64 steps (LAG > 16 (Q-1) + L), three sweep slots fit the LDS, and a lane's frame
+// period is 1024 steps -- a lane is idle at least half of the time.  A quarter of the narrow build's rate; the generic engine these
+// shapes used to get is 5x slower still.
+#define LWS_L7 LWS_ROW_FIELD(L7, LWS_BUILD)
+// LWS_R16: Q = 2 (hop = half a frame, the reference's LWSQ2).  The taps reach one frame either way, so a lag of 16 steps between
+// sweeps is enough (LAG > 8 (Q-1) + L = 13) and the ring is 16 steps deep: sets of 9 KB instead of 18, FIFTEEN sweep slots in the same
+// LDS -- one wave each, four waves per SIMD (the Q = 2 kernels need ~115 VGPRs).  Throughput follows the number of waves that run a
+// dependent chain.  Goes with LWS_WIDE = 1 (seven sweep slots of two waves instead of three) and with LWS_SPW (26 / 44 sweep slots).
+#define LWS_R16 LWS_ROW_FIELD(R16, LWS_BUILD)
+// LWS_TW: weights whose twiddle is NOT a multiple of an eighth turn: Q = 3 (hop = a third of the frame), and the "general" weights
+// create_weights builds for a hop that does not divide the frame (lws.pyx:164-181: Q' = N rows, one per bin; e.g. 25 ms frames every
+// 10 ms, lws(400, 160): Q = 3, Qfloat = 2.5), the reference's LWSanyQ with Q = 3 and its LWSfractionalQ (lwslib.cpp:283-467).  Those
+// tensors still are
 //     W[p][r][k] = W[0][r][k] tau_r(p),   tau_r(p) = exp(2 pi j p r s / P),   s / P = hop / frame in lowest terms,
 // so the kernel keeps the base weights W[0][r][k] in scalar registers as ever and takes tau_r(bin) -- now a per-lane value that
 // no unrolling of the step loop makes static -- from a table in LDS ((P + 8) rows of Q - 1 twiddles; a lane carries the row of
 // its block's first bin).  The taps of frames m-r and m+r are summed separately (U, D: every tap its own multiply-add, as
 // LWSanyQ does, instead of the grouped LWSQ4 form) and enter the bin's sum as tau U + conj(tau) D.  Same schedule, rings,
 // images and flow control as the narrow build; ~1.4x its instructions per tap.
-#ifndef LWS_TW
-#define LWS_TW 0
-#endif
-// (... and with LWS_Q8 -- namespace lws::tw_q8: the 64-step ring, halo of 7 and helper waves of the Q = 8 build with table twiddles, for
-//  ceil(frame/hop) in 5..8 with any twiddle: Q in {5,6,7}, and fractional Q above 4.  The kernel is the Q = 8 instantiation; the frame
-//  pairs the plan does not have are masked out at compile time, its pad frames and "real frame" tests follow the plan's Q, SysArgs::Qa)
-// (... and with LWS_Q8 and -DLWS_TWQ=5 / 6 -- namespaces lws::tw_q5 / lws::tw_q6 (round 5): the same kernel on the ring a plan of exactly 5 / 6
-//  frames per stencil row needs -- LAG > 8 (Q - 1) + L: 40 / 48 steps instead of 64 -- so that the LDS holds THREE sweep slots of a main
-//  and ONE helper wave (frames m-+1 and m-+(Q-1) stay with the main wave, the helper sums the two / three pairs in between) where
-//  lws::tw_q8 has two slots of a main and two helpers.  The ring is then 5 / 6 blocks of 8 steps: block indices are taken modulo NBLK
-//  (blk_mod), not masked.)
-#ifndef LWS_TWQ
-#define LWS_TWQ 0
-#endif
+// With LWS_Q8: the 64-step ring, halo of 7 and helper waves of the Q = 8 build with table twiddles, for ceil(frame/hop) in 5..8 with
+// any twiddle: Q in {5,6,7}, and fractional Q above 4.  The kernel is the Q = 8 instantiation; the frame pairs the plan does not have
+// are masked out at compile time, its pad frames and "real frame" tests follow the plan's Q, SysArgs::Qa.
+#define LWS_TW LWS_ROW_FIELD(TW, LWS_BUILD)
+// LWS_TWQ = 5 / 6 (with LWS_TW and LWS_Q8): the same kernel on the ring a plan of exactly 5 / 6 frames per stencil row needs -- LAG >
+// 8 (Q - 1) + L: 40 / 48 steps instead of 64 -- so that the LDS holds THREE sweep slots of a main and ONE helper wave (frames m-+1
+// and m-+(Q-1) stay with the main wave, the helper sums the two / three pairs in between) where LWS_TWQ = 0 has two slots of a main
+// and two helpers.  The ring is then 5 / 6 blocks of 8 steps: block indices are taken modulo NBLK (blk_mod), not masked.
+#define LWS_TWQ LWS_ROW_FIELD(TWQ, LWS_BUILD)
 #if LWS_TWQ && !(LWS_TW && LWS_Q8 && (LWS_TWQ == 5 || LWS_TWQ == 6))
 #error "LWS_TWQ = 5 or 6 goes with LWS_TW and LWS_Q8"
 #endif
@@ -139,64 +126,12 @@
 #if (LWS_WIDE && LWS_Q8) || ((LWS_SPW != 1 || LWS_L7) && (LWS_WIDE || LWS_Q8)) || (LWS_SPW != 1 && LWS_L7) || (LWS_R16 && (LWS_WIDE == 2 || LWS_Q8 || LWS_L7))
 #error "LWS_WIDE, LWS_Q8, LWS_SPW, LWS_L7 and LWS_R16 are separate builds (LWS_R16 goes with LWS_WIDE=1 or LWS_SPW)"
 #endif
-#if LWS_TWQ == 5
-#define LWS_NS_OPEN namespace lws { namespace tw_q5 {
-#define LWS_NS_CLOSE } }
-#elif LWS_TWQ == 6
-#define LWS_NS_OPEN namespace lws { namespace tw_q6 {
-#define LWS_NS_CLOSE } }
-#elif LWS_TW && LWS_Q8
-#define LWS_NS_OPEN namespace lws { namespace tw_q8 {
-#define LWS_NS_CLOSE } }
-#elif LWS_TW && LWS_SPW == 2
-#define LWS_NS_OPEN namespace lws { namespace tw_half {
-#define LWS_NS_CLOSE } }
-#elif LWS_TW && LWS_WIDE
-#define LWS_NS_OPEN namespace lws { namespace tw_wide {
-#define LWS_NS_CLOSE } }
-#elif LWS_TW
-#define LWS_NS_OPEN namespace lws { namespace tw {
-#define LWS_NS_CLOSE } }
-#elif LWS_R16 && LWS_WIDE
-#define LWS_NS_OPEN namespace lws { namespace wide_q2 {
-#define LWS_NS_CLOSE } }
-#elif LWS_R16 && LWS_SPW == 2
-#define LWS_NS_OPEN namespace lws { namespace half_q2 {
-#define LWS_NS_CLOSE } }
-#elif LWS_R16 && LWS_SPW == 4
-#define LWS_NS_OPEN namespace lws { namespace quarter_q2 {
-#define LWS_NS_CLOSE } }
-#elif LWS_R16
-#define LWS_NS_OPEN namespace lws { namespace q2 {
-#define LWS_NS_CLOSE } }
-#elif LWS_L7
-#define LWS_NS_OPEN namespace lws { namespace l7 {
-#define LWS_NS_CLOSE } }
-#elif LWS_SPW == 2
-#define LWS_NS_OPEN namespace lws { namespace half {
-#define LWS_NS_CLOSE } }
-#elif LWS_SPW == 4
-#define LWS_NS_OPEN namespace lws { namespace quarter {
-#define LWS_NS_CLOSE } }
-#elif LWS_WIDE == 2
-#define LWS_NS_OPEN namespace lws { namespace xwide {
-#define LWS_NS_CLOSE } }
-#elif LWS_WIDE
-#define LWS_NS_OPEN namespace lws { namespace wide {
-#define LWS_NS_CLOSE } }
-#elif LWS_Q8
-#define LWS_NS_OPEN namespace lws { namespace q8 {
-#define LWS_NS_CLOSE } }
-#else
-#define LWS_NS_OPEN namespace lws {
-#define LWS_NS_CLOSE }
-#endif
 
-LWS_NS_OPEN
+namespace LWS_NS {
 namespace {
 
 constexpr int LANES = 64;                                // lanes of a wave
-// (-DLWS_WIDE=2, namespace lws::xwide: frames of up to 2049 bins -- a 4096-point STFT -- on a ring row of 256 lanes = FOUR waves per
+// (LWS_WIDE = 2: frames of up to 2049 bins -- a 4096-point STFT -- on a ring row of 256 lanes = FOUR waves per
 //  sweep slot; the LDS holds the loader's set and one slot's, so every sweep is a pass over HBM, with four compute waves each
 //  alone on its SIMD beside a service wave: a quarter of the narrow build's rate per bin, four times the generic engine's)
 constexpr int WPS = LWS_WIDE == 2 ? 4 : (LWS_WIDE ? 2 : 1);   // waves per sweep slot
@@ -227,13 +162,13 @@ constexpr int PAIR_BYTES = (ROWL + 2 * HALO + 2) * LANE_B;   // two consecutive 
 constexpr int BLK_BYTES = 4 * PAIR_BYTES;                // one block of 8 steps
 constexpr int SET_BYTES = (RING / 2) * PAIR_BYTES;       // 18 KiB (wide: 34 KiB, Q = 8: 40 KiB)
 #ifndef LWS_NSLOTS
-#define LWS_NSLOTS ((LWS_R16 && LWS_WIDE) ? 7 : (LWS_R16 && LWS_SPW == 2) ? 26 : (LWS_R16 && LWS_SPW == 4) ? 44 : LWS_R16 ? 15 : LWS_L7 ? 3 : LWS_WIDE == 2 ? 1 : LWS_WIDE ? 3 : (LWS_TWQ ? 3 : LWS_Q8 ? 2 : (LWS_SPW == 4 ? 24 : 7 * LWS_SPW)))   // (SPW = 4: 25 ring sets of 6 KB are what the LDS holds -- six compute waves)
+#define LWS_NSLOTS LWS_ROW_FIELD(SLOTS, LWS_BUILD)
 #endif
 constexpr int NSLOTS = LWS_NSLOTS;                       // sweeps in flight (compute waves)
 constexpr int NSETS = NSLOTS + 1;
 constexpr int NYQ_OFF = NSETS * SET_BYTES;               // Nyquist values: [set][lane] float2
 constexpr int THR_OFF = NYQ_OFF + NSETS * SLOT_BYTES;    // effective thresholds: floats
-constexpr int MAX_ITERS = 440;
+constexpr int MAX_ITERS = 440;                           // sweeps of one launch (their thresholds live in LDS); longer schedules run as several launches
 constexpr int META_OFF = THR_OFF + MAX_ITERS * 4;        // n_eff
 constexpr int DONE_OFF = META_OFF + 16;               // per-wave count of completed steps (flow control)
 constexpr int DUMMY_OFF = DONE_OFF + 64;               // 64 x 8 B: where predicated-off lanes park their conditional writes
@@ -2687,7 +2622,7 @@ void systolic_release(SystolicPlan &sp) {
 }
 
 bool systolic_supports(const SystolicPlan &sp, int wsel, int T) {
-    return wsel >= 0 && wsel < 3 && sp.ok[wsel] && T >= 1;  // (any number of sweeps: more than SYSTOLIC_MAX_ITERS run as several launches)
+    return wsel >= 0 && wsel < 3 && sp.ok[wsel] && T >= 1;  // (any number of sweeps: more than MAX_ITERS run as several launches)
 }
 
 const char *systolic_name(const SystolicPlan &sp) { return sp.name; }
@@ -2874,7 +2809,7 @@ hipError_t launch_update(SystolicPlan &sp, const Geom &g, int wsel, const float 
         else e = launch_k<2, 5, mask_all(2, 5)>(a, grid, h, stream);
     }
 #endif
-    snprintf(sp.name_buf, sizeof sp.name_buf, "systolic%s_q%d_l%d_%s%s", (LWS_TW && SPW == 2) ? "_half" : (LWS_TW && LWS_WIDE) ? "_wide" : (LWS_TWQ == 5) ? "_r40" : (LWS_TWQ == 6) ? "_r48" : (LWS_TW && LWS_Q8) ? "_r64" : LWS_TW ? "" : (LWS_R16 && LWS_WIDE) ? "_wide_r16" : (LWS_R16 && SPW == 2) ? "_half_r16" : (LWS_R16 && SPW == 4) ? "_quarter_r16" : LWS_R16 ? "_r16" : LWS_WIDE == 2 ? "_xwide" : LWS_WIDE ? "_wide" : (SPW == 2 ? "_half" : (SPW == 4 ? "_quarter" : "")), Q, L, kind,
+    snprintf(sp.name_buf, sizeof sp.name_buf, "systolic%s_q%d_l%d_%s%s", LWS_NAME_TAG, Q, L, kind,
              h ? "_f16" : "");
     sp.name = sp.name_buf;
     return e;
@@ -3047,4 +2982,4 @@ const SystolicBuild &systolic_entry() {
     return b;
 }
 
-LWS_NS_CLOSE
+}  // namespace LWS_NS
