@@ -2,6 +2,7 @@
 #pragma once
 #include "lws_band_core.h"
 #include "lws_common.h"
+#include "lws_weights.h"
 
 #include <vector>
 
@@ -16,11 +17,11 @@ struct BandPlan {
     size_t state_bytes, amp_bytes;   // scratch: the time-skewed state of `chunk` spectrograms; the magnitudes
 };
 // What the band engine can run: MODE_BATCH, update == 2, 2 <= Q <= 16, L <= 10, F >= 2 LT + 7 (LT = 5 for L <= 5, else 10), a weight
-// tensor with create_weights' twiddle structure (lws.pyx:160-181; weights_twiddle(), any twiddle period whose table leaves room for a ring in the LDS -- for an fp64 plan
+// tensor with create_weights' twiddle structure (lws.pyx:160-181; WeightStructure::twiddle, any twiddle period whose table leaves room for a ring in the LDS -- for an fp64 plan
 // a summarised tensor (Qp == Q) whose rows are twiddle images of row 0 to 1e-13, so that the results are the reference's to rounding) and a frame short enough for one sweep
 // slot's ring in the LDS (Q F complex values: e.g. Q = 8 at 1025 bins, Q = 16 at 513 bins in fp32; half that in fp64).
-// W: the plan's tensor on the host (complex128 interleaved, [Qp][Q][L+1]).  False: the caller uses the generic engine.
-bool band_plan(bool fp64, int B, int F, int T, int L, int Q, int Qp, int update, int n_thr, const double *W, BandPlan *out);
+// ws: the analysis of the plan's tensor (lws_weights.h).  False: the caller uses the generic engine.
+bool band_plan(bool fp64, int B, int F, int T, int L, int Q, int Qp, int update, int n_thr, const WeightStructure &ws, BandPlan *out);
 const char *band_name(const BandPlan &bp);   // "band_fp32" / "band_fp64"
 // The two tables a kernel reads (lws_band_host.h: tables -- [Q][LT+1] weights, then [Pt][Q-1] twiddles), in the plan's arithmetic
 // type: what the caller keeps on the device for the plan's lifetime (they depend on W, LT and the precision only) and hands to

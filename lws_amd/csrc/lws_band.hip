@@ -240,28 +240,6 @@ inline int helpers_of(bool fp64, int LT, int Q) {
 }
 inline int max_threads(bool fp64, int LT, int QT, int helpers) { return fp64 ? 256 : ((helpers || (LT == 5 && QT == 8)) ? 512 : 256); }
 
-// Every row of W the twiddle image of row 0 to `tol` of the largest weight?  (weights_twiddle accepts 1e-9: enough to choose an
-// engine whose arithmetic is fp32; an fp64 plan promises the reference's values to rounding.)
-bool rows_are_twiddles(const double *W, int Q, int Qp, int L, int Pt, int s, double tol) {
-    const int K1 = L + 1;
-    double scale = 0;
-    for (size_t x = 0; x < (size_t)Qp * Q * K1; ++x) scale = std::max(scale, std::hypot(W[2 * x], W[2 * x + 1]));
-    auto at = [&](int p, int r, int k, int c) { return W[2 * (((size_t)p * Q + r) * K1 + k) + c]; };
-    for (int p = 0; p < Qp; ++p)
-        for (int r = 0; r < Q; ++r) {
-            double cr, ci;
-            unit((long long)p * r * s, Pt, &cr, &ci);
-            for (int k = 0; k < K1; ++k) {
-                if (r == 0 && k == 0) continue;
-                const double br = at(0, r, k, 0), bi = at(0, r, k, 1);
-                if (std::hypot(at(p, r, k, 0) - (br * cr - bi * ci), at(p, r, k, 1) - (br * ci + bi * cr)) > tol * scale) return false;
-                // the reference skips a weight by its own magnitude (lws.pyx:232); rows that disagree about that cannot share row 0
-                if ((std::hypot(at(p, r, k, 0), at(p, r, k, 1)) > 1e-12) != (std::hypot(br, bi) > 1e-12)) return false;
-            }
-        }
-    return true;
-}
-
 // relative time of a step by the waves that share a SIMD (the headline kernel's measurement: two waves stretch a step by 1.4)
 inline double step_cost(int waves) {
     const int k = (waves + 3) / 4;
@@ -270,21 +248,21 @@ inline double step_cost(int waves) {
 
 }  // namespace
 
-bool band_plan(bool fp64, int B, int F, int T, int L, int Q, int Qp, int update, int n_thr, const double *W, BandPlan *out) {
-    if (!W || update != 2 || T < 1 || n_thr < 1 || Q < 2 || Q > 16 || L < 1 || L > 10 || Qp < 1) return false;
+bool band_plan(bool fp64, int B, int F, int T, int L, int Q, int Qp, int update, int n_thr, const WeightStructure &ws, BandPlan *out) {
+    if (update != 2 || T < 1 || n_thr < 1 || Q < 2 || Q > 16 || L < 1 || L > 10 || Qp < 1) return false;
     // the stencil half-width the kernel is compiled for: 5, 10, and 8 for Q = 4 (`lws(1024,256,L=8)`: frames 10 steps apart instead of 12)
     const int LT = L <= 5 ? 5 : ((L <= 8 && Q == 4) ? 8 : 10), QT = Q <= 8 ? 8 : 16;
     if (F < 2 * LT + 7) return false;
     int Pt = 0, s = 0;
     // (any twiddle period whose table still leaves room for a ring: a hop with no common factor with the frame has Pt = the frame)
-    if (!weights_twiddle(W, Q, Qp, L, 4096, &Pt, &s)) return false;
+    if (!ws.twiddle(4096, &Pt, &s)) return false;
     if (Pt < 1) { Pt = 1; s = 0; }
     // (fp64: the rows must be the twiddle images of row 0 to rounding, or the results would not be the reference's.  The general
     //  tensors create_weights builds for a hop that does not divide the frame -- one row per bin, numpy's exp of an angle of up to N
     //  turns -- are 1e-13 to 1e-16 of a turn off, which a few sweeps amplify a thousandfold: fp64 plans with such tensors stay on the
     //  order-exact engine, whatever the check below would say)
     if (fp64 && Qp != Q) return false;
-    if (!rows_are_twiddles(W, Q, Qp, L, Pt, s, fp64 ? 1e-13 : 1e-9)) return false;
+    if (!(fp64 ? ws.band_rows_fp64 : ws.band_rows_fp32)) return false;
     const size_t csize = fp64 ? 16 : 8;
     // (LWS_BAND_NO_HELPERS=1: the exact builds' one-wave-per-slot variant -- comparison runs)
     const int helpers = env_int("LWS_BAND_NO_HELPERS", 0) ? 0 : helpers_of(fp64, LT, Q);

@@ -59,8 +59,8 @@ inline void unit(long long num, long long den, double *re, double *im) {
     *re = std::cos(ang); *im = std::sin(ang);
 }
 
-// W: the plan's tensor on the host (complex128 interleaved, [Qp][Q][L+1]) with the twiddle structure (Pt, s) weights_twiddle()
-// found.  wt: [Q][LT+1] complex (interleaved doubles): row 0 = W[0][0][k] (the frame's own taps; [0][0] is never read), row r =
+// W: the plan's tensor on the host (complex128 interleaved, [Qp][Q][L+1]) with the twiddle structure (Pt, s) its analysis
+// found (lws_weights.h).  wt: [Q][LT+1] complex (interleaved doubles): row 0 = W[0][0][k] (the frame's own taps; [0][0] is never read), row r =
 // V[r][k] = W[0][r][k] exp(2 pi j r s k / Pt); weights the reference skips (|w| <= 1e-12, lws.pyx:231-232) and columns k > L are 0.
 // tw: [Pt][Q-1]: exp(2 pi j p r s / Pt).
 inline void tables(const double *W, int Q, int L, int LT, int Pt, int s, std::vector<double> &wt, std::vector<double> &tw) {

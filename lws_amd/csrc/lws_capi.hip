@@ -169,11 +169,11 @@ struct lws_plan {
     unsigned flags = 0;
     bool fp64 = false;
     bool have[3] = {false, false, false};
-    int wperiod[3] = {0, 0, 0};    // period of the weight rows of each tensor (Q for a summarised one; 0: rows do not repeat)
     bool twiddle_all = false;      // W, W_ai and W_af all have create_weights' twiddle structure (the online LDS engine relies on it)
     int tw_P = 0, tw_s = 0;        // ... W[p][r][k] = W[0][r][k] exp(2 pi j p r tw_s / tw_P), the same for the three of them
     DevBuf online_tw;              // the online engine's twiddle table when those are not the static eighth turns of Q in {2,4,8}
-    std::vector<double> hostW[3];  // complex128 interleaved copies (eligibility analysis, systolic tables)
+    std::vector<double> hostW[3];  // complex128 interleaved copies (the engines' tables are built from them)
+    lws::WeightStructure wstruct[3];   // ... and what the engine guards ask about them (lws_weights.h), analysed once, here
     DevBuf w[3], wflag[3];
     DevBuf state, amp, row_sums, mean_amp, thr_host_copy, thr_scaled, stage, resid_rows, resid_out, resid_sum;
     DevBuf gsk_state, gsk_amp;     // time-skewed copy of the state for the generic engine's batch sweeps
@@ -221,6 +221,7 @@ int upload_weights(lws_plan *p, int which, const double *W) {
     HIP_TRY(hipMemcpy(p->w[which].p, w.data(), n * sizeof(C), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(p->wflag[which].p, f.data(), n, hipMemcpyHostToDevice));
     p->hostW[which].assign(W, W + 2 * n);
+    p->wstruct[which] = lws::analyse_weights(W, p->Q, p->Qp, p->L);
     p->have[which] = true;
     return LWS_OK;
 }
@@ -331,17 +332,17 @@ Route choose_engine(const lws_plan *p, const Stage &st, Engine from = Engine::Sy
         lws::online_lds_supports(F, T, L, Q, Qp, LA, n, 2, p->twiddle_all ? p->tw_P : 0, p->tw_s, p->online_tw.p != nullptr))
         return pick(Engine::OnlineLds);
     if (at(Engine::NofutureLds) && nofuture && !generic &&
-        (fp64 ? lws::nofuture_lds64_supports(F, T, L, Q, Qp, p->wperiod[st.wsel]) : lws::nofuture_lds_supports(F, T, L, Q, Qp, p->wperiod[st.wsel])))
+        (fp64 ? lws::nofuture_lds64_supports(F, T, L, Q, Qp, p->wstruct[st.wsel].row_period) : lws::nofuture_lds_supports(F, T, L, Q, Qp, p->wstruct[st.wsel].row_period)))
         return pick(Engine::NofutureLds);
     if (at(Engine::Online64) && fp64 && online && !generic && !q8_team() && lws::online64_supports(F, T, L, Q, Qp, LA, n, 2))
         return pick(Engine::Online64);
     // 3. batch sweeps no systolic build takes: the fp64 systolic engine, the band engine (weights with create_weights' twiddle
     //    structure, a sweep slot's ring in LDS), the generic engine on a time-skewed copy of the state (coalesced taps; same bits)
     if (at(Engine::Sys64) && fp64 && batch && !generic && !plain && !no_sys64 &&
-        lws::sys64_supports(F, T, L, Q, Qp, 2, p->have[st.wsel] ? p->hostW[st.wsel].data() : nullptr))
+        lws::sys64_supports(F, T, L, Q, 2, p->wstruct[st.wsel]))
         return pick(Engine::Sys64);
     if (at(Engine::Band) && batch && !generic && !plain && p->have[st.wsel] &&
-        lws::band_plan(fp64, st.B, F, T, L, Q, Qp, 2, n, p->hostW[st.wsel].data(), &r.bp))
+        lws::band_plan(fp64, st.B, F, T, L, Q, Qp, 2, n, p->wstruct[st.wsel], &r.bp))
         return pick(Engine::Band);
     if (at(Engine::GenericSkew) && batch && !plain) return pick(Engine::GenericSkew);
     // 4. online and no-future sweeps no LDS engine takes: the team engine (the generic engine's schedule, a bin's taps on a team of lanes)
@@ -411,8 +412,8 @@ int launch_route(lws_plan *p, const Route &r, const lws::GenericArgs<real> &a, i
         name = "online_lds_fp32", what = "online";
         break;
     case Engine::NofutureLds:
-        if constexpr (fp64) e = lws::launch_nofuture_lds64(a, B, p->wperiod[a.wsel], s);
-        else e = lws::launch_nofuture_lds(a, B, p->wperiod[a.wsel], s);
+        if constexpr (fp64) e = lws::launch_nofuture_lds64(a, B, p->wstruct[a.wsel].row_period, s);
+        else e = lws::launch_nofuture_lds(a, B, p->wstruct[a.wsel].row_period, s);
         name = fp64 ? (q4compat ? "nofuture_lds_q4compat_fp64" : "nofuture_lds_fp64") : (q4compat ? "nofuture_lds_q4compat_fp32" : "nofuture_lds_fp32");
         what = fp64 ? "fp64 no-future" : "no-future";
         break;
@@ -421,7 +422,7 @@ int launch_route(lws_plan *p, const Route &r, const lws::GenericArgs<real> &a, i
         name = r.one_wave ? "online_lds_fp64_1w" : "online_lds_fp64", what = "fp64 online";
         break;
     case Engine::Sys64:
-        if constexpr (fp64) e = lws::launch_sys64(a, p->hostW[a.wsel].data(), B, p->gsk_state.p, p->gsk_amp.p, s, &launches, p->ev0, p->ev1);
+        if constexpr (fp64) e = lws::launch_sys64(a, p->hostW[a.wsel].data(), p->wstruct[a.wsel], B, p->gsk_state.p, p->gsk_amp.p, s, &launches, p->ev0, p->ev1);
         name = lws::sys64_name(a.F, a.T, a.Q), what = "fp64 systolic";
         break;
     case Engine::Band:
@@ -1109,13 +1110,11 @@ int lws_plan_create(lws_plan **plan, int device, int F, int L, int Q, int Qp, co
         if (hipEventCreate(&p->ev0) != hipSuccess || hipEventCreate(&p->ev1) != hipSuccess)
             rc = fail(LWS_ERR_HIP, "hipEventCreate failed");
     }
-    for (int i = 0; i < 3; ++i)
-        p->wperiod[i] = !p->have[i] ? 0 : (Qp == Q ? Q : lws::weights_row_period(p->hostW[i].data(), Qp, Q, L, 256));
     p->twiddle_all = rc == LWS_OK && p->have[0] && p->have[1] && p->have[2];
     p->tw_P = 0;
     for (int i = 0; i < 3 && p->twiddle_all; ++i) {
         int P = 0, sg = 0;      // (P = 0: a tensor without neighbour-frame weights fits any twiddle)
-        p->twiddle_all = lws::weights_twiddle(p->hostW[i].data(), Q, Qp, L, 512, &P, &sg) && (P == 0 || p->tw_P == 0 || (P == p->tw_P && sg == p->tw_s));
+        p->twiddle_all = p->wstruct[i].twiddle(512, &P, &sg) && (P == 0 || p->tw_P == 0 || (P == p->tw_P && sg == p->tw_s));
         if (P > 0) { p->tw_P = P; p->tw_s = sg; }
     }
     if (p->twiddle_all && p->tw_P == 0) { p->tw_P = Q; p->tw_s = 1; }
@@ -1142,7 +1141,7 @@ int lws_plan_create(lws_plan **plan, int device, int F, int L, int Q, int Qp, co
         for (int i = 0; i < n_builds; ++i) {
             const lws::SystolicBuild *b = builds[i];
             if (b->kind & skip) continue;
-            if ((e = b->build(p->sys, F, L, Q, Qp, hw, h16)) != hipSuccess) break;
+            if ((e = b->build(p->sys, F, L, Q, Qp, hw, p->wstruct, h16)) != hipSuccess) break;
             // the build must take the tensor batch sweeps normally run on -- W, the first one present -- : a build that only takes
             // another of the plan's tensors (W_ai of a hop above half the frame has no neighbour-frame weights and fits any
             // twiddle) would leave the batch stage on the generic engine
@@ -1357,7 +1356,7 @@ nccl_allreduce_fn rccl_allreduce() {
 int lws_weights_structure(const double *W, int Q, int Qp, int L, int *period, int *step) {
     int P = 0, sg = 0;
     if (!W || !period || !step || Q < 2 || Qp < 1 || L < 0) return 0;
-    if (!lws::weights_twiddle(W, Q, Qp, L, 4096, &P, &sg)) return 0;
+    if (!lws::analyse_weights(W, Q, Qp, L).twiddle(4096, &P, &sg)) return 0;
     *period = P; *step = sg;
     return 1;
 }

@@ -358,28 +358,6 @@ bool nofuture_lds_supports(int F, int T, int L, int Q, int Qp, int rows) { retur
 // (summarised tensors only: the rows of a general tensor repeat to 1e-9, not to the bit)
 bool nofuture_lds64_supports(int F, int T, int L, int Q, int Qp, int rows) { return Qp == Q && shape_of(F, T, L, Q, Qp, rows, true).ok; }
 
-// Smallest P <= pmax dividing Qp such that the rows of W[Qp][Q][L+1] (complex128 interleaved) repeat with period P -- Q for a
-// summarised tensor (trivially), frame / gcd(frame, hop) for create_weights' general ones (lws.pyx:164-181) -- or 0.  The kernels
-// above then index row (bin mod P) where the reference indexes row bin (LWSfractionalQ, lwslib.cpp:393,408: mod = bin,
-// modneg = N - bin): the same weights to 1e-9 of the largest one (rounded to fp32 afterwards).
-int weights_row_period(const double *W, int Qp, int Q, int L, int pmax) {
-    if (!W || Qp < 1) return 0;
-    const size_t RQ = (size_t)Q * (L + 1);
-    double scale = 0;
-    for (size_t x = 0; x < (size_t)Qp * RQ; ++x) scale = std::fmax(scale, std::hypot(W[2 * x], W[2 * x + 1]));
-    for (int P = 1; P <= pmax && P <= Qp; ++P) {
-        if (Qp % P != 0) continue;
-        bool ok = true;
-        for (int p = P; p < Qp && ok; ++p)
-            for (size_t x = 0; x < RQ; ++x) {
-                const size_t i = (size_t)p * RQ + x, j = (size_t)(p % P) * RQ + x;
-                if (std::hypot(W[2 * i] - W[2 * j], W[2 * i + 1] - W[2 * j + 1]) > 1e-9 * scale) { ok = false; break; }
-            }
-        if (ok) return P;
-    }
-    return 0;
-}
-
 hipError_t launch_nofuture_lds(const GenericArgs<float> &g, int B, int rows, hipStream_t stream) {
     const NfShape sh = shape_of(g.F, g.T, g.L, g.Q, g.Qp, rows);
     if (!sh.ok) return hipErrorInvalidValue;

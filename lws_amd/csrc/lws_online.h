@@ -5,7 +5,7 @@
 namespace lws {
 
 // true if launch_online_lds can run this shape: all three tensors with the common twiddle structure (tw_P, tw_s) that
-// weights_twiddle finds -- static eighth turns (P = Q in {2,4,8}, s = 1: every layout) or a table (Q in 3..8, any P <= 512: the
+// WeightStructure::twiddle (lws_weights.h) finds -- static eighth turns (P = Q in {2,4,8}, s = 1: every layout) or a table (Q in 3..8, any P <= 512: the
 // fourth layout) -- L <= 5 (L = 5 for the first three layouts), the window of frames the sweeps in flight need fits the LDS ring;
 // otherwise the caller uses the generic engine.
 bool online_lds_supports(int F, int T, int L, int Q, int Qp, int LA, int n_thr, int update, int tw_P, int tw_s, bool table);

@@ -1745,57 +1745,6 @@ bool online_lds_supports(int F, int T, int L, int Q, int Qp, int LA, int n_thr, 
     return shape4_of(F, T, L, Q, Q, LA, n_thr, tw_P).sh.ok;
 }
 
-// Common twiddle structure of a weight tensor W[Qp][Q][L+1] (complex128 interleaved): W[p][r][k] == W[0][r][k] exp(2 pi j p r s / P)
-// for every row p (create_weights, lws.pyx:160-181: s / P = hop / frame in lowest terms; P = Q, s = 1 when the hop divides the frame).
-bool weights_twiddle(const double *W, int Q, int Qp, int L, int pmax, int *P_out, int *s_out) {
-    // (*P_out = 0: every weight with r >= 1 is zero -- a tensor that fits any twiddle, e.g. W_ai of hop = frame / 2)
-    if (!W || Q < 2 || Qp < 1) return false;
-    const int K1 = L + 1;
-    double scale = 0;
-    for (size_t x = 0; x < (size_t)Qp * Q * K1; ++x) scale = std::fmax(scale, std::hypot(W[2 * x], W[2 * x + 1]));
-    if (!(scale > 0)) return false;
-    auto at = [&](int p, int r, int k, int c) { return W[2 * (((size_t)p * Q + r) * K1 + k) + c]; };
-    auto verify = [&](int P, int sg) {
-        if (((long long)Qp * sg) % P != 0) return false;   // the rows a kernel reads besides p = bin: p = Qp - bin (modneg, lwslib.cpp:300,408)
-        for (int p = 0; p < Qp; ++p)
-            for (int r = 0; r < Q; ++r) {
-                const double ang = 2.0 * M_PI * (double)(((long long)p * r * sg) % P) / P;
-                const double cs = std::cos(ang), sn = std::sin(ang);
-                for (int k = 0; k < K1; ++k) {
-                    if (r == 0 && k == 0) continue;   // never read by the kernels
-                    const double br = at(0, r, k, 0), bi = at(0, r, k, 1);
-                    if (std::hypot(at(p, r, k, 0) - (br * cs - bi * sn), at(p, r, k, 1) - (br * sn + bi * cs)) > 1e-9 * scale) return false;
-                }
-            }
-        return true;
-    };
-    if (Qp == 1) { *P_out = 1; *s_out = 0; return true; }
-    // the turn per bin, theta = s / P, from row 1 against row 0 on the largest weight of the first frame offset r that has one:
-    // that gives r theta mod 1, i.e. r candidates for theta
-    int rb = 0, kb = 0;
-    for (int r = 1; r < Q && rb == 0; ++r)
-        for (int k = 0; k < K1; ++k)
-            if (std::hypot(at(0, r, k, 0), at(0, r, k, 1)) > std::fmax(1e-6 * scale, rb ? std::hypot(at(0, rb, kb, 0), at(0, rb, kb, 1)) : 0.0)) { rb = r; kb = k; }
-    if (rb == 0) {   // nothing but the centre frame: the rows must simply repeat row 0
-        if (!verify(1, 0)) return false;
-        *P_out = 0; *s_out = 0;
-        return true;
-    }
-    const double br = at(0, rb, kb, 0), bi = at(0, rb, kb, 1), wr = at(1, rb, kb, 0), wi = at(1, rb, kb, 1);
-    double tr = std::atan2(wi * br - wr * bi, wr * br + wi * bi) / (2.0 * M_PI);   // arg(w / b) in turns = rb theta mod 1
-    tr -= std::floor(tr);
-    for (int j = 0; j < rb; ++j) {
-        const double theta = (tr + j) / rb;
-        for (int P = 1; P <= pmax; ++P) {
-            const double sp = theta * P, sr = std::round(sp);
-            if (std::fabs(sp - sr) > 1e-7) continue;
-            const int sg = (int)sr % P;
-            if (verify(P, sg)) { *P_out = P; *s_out = sg; return true; }
-            break;                                        // (the smallest P of this candidate failed: multiples of it fail too)
-        }
-    }
-    return false;
-}
 // the table of k_online4<..., TWT>: [P + 3][TQ] float2, TQ = 4 for Q <= 4 else 8, row p: exp(2 pi j p r s / P), r = 0..TQ-1 (host side;
 // the plan uploads it)
 void online_twiddle_table(int P, int s, int Q, float *out) {

@@ -495,37 +495,19 @@ int slots_for(int Q, int R, int rw) {   // sweep slots per workgroup: what the L
     return 0;
 }
 
-// W (host, complex128 interleaved, [Qp][Q][L+1]): every row a quarter-turn image of row 0, to rounding?  Fills the row-0 weights.
-template <int Q> bool base_weights(const double *W, int Qp, BaseW<Q> *out) {
+// The row-0 weights of W (host, complex128 interleaved, [Qp][Q][L+1]), every row of which is a quarter-turn image of row 0
+// (WeightStructure::quarter_turns); the weights the reference skips are zeros.
+template <int Q> void base_weights(const double *W, BaseW<Q> *out) {
     const int K1 = SL + 1;
-    if (!W || Qp < 1 || Qp % Q != 0) return false;   // (Qp - row) mod Qp must be -row mod Q
-    auto at = [&](int p, int r, int k, int c) { return W[2 * (((size_t)p * Q + r) * K1 + k) + c]; };
-    double scale = 0;
-    for (size_t x = 0; x < (size_t)Qp * Q * K1; ++x) scale = std::max(scale, std::hypot(W[2 * x], W[2 * x + 1]));
-    if (!(scale > 0)) return false;
-    for (int p = 0; p < Qp; ++p)
-        for (int r = 0; r < Q; ++r)
-            for (int k = 0; k < K1; ++k) {
-                if (r == 0 && k == 0) continue;   // never read (update == 2)
-                const double br = at(0, r, k, 0), bi = at(0, r, k, 1);
-                const int n = quarter_turns<Q>(p, r);
-                const double er = n == 0 ? br : (n == 1 ? -bi : (n == 2 ? -br : bi));
-                const double ei = n == 0 ? bi : (n == 1 ? br : (n == 2 ? -bi : -br));
-                if (std::hypot(at(p, r, k, 0) - er, at(p, r, k, 1) - ei) > 1e-13 * scale) return false;
-                // the reference skips a weight by its own magnitude (lws.pyx:232); rows that disagree about that cannot share row 0
-                if ((std::hypot(at(p, r, k, 0), at(p, r, k, 1)) > 1e-12) != (std::hypot(br, bi) > 1e-12)) return false;
-            }
-    if (out) {
-        auto put = [&](double2 &d, int r, int k) {
-            const bool on = std::hypot(at(0, r, k, 0), at(0, r, k, 1)) > 1e-12;
-            d.x = on ? at(0, r, k, 0) : 0.0;
-            d.y = on ? at(0, r, k, 1) : 0.0;
-        };
-        for (int k = 1; k <= SL; ++k) put(out->c[k - 1], 0, k);
-        for (int r = 1; r < Q; ++r)
-            for (int k = 0; k <= SL; ++k) put(out->n[r - 1][k], r, k);
-    }
-    return true;
+    auto put = [&](double2 &d, int r, int k) {
+        const double re = W[2 * ((size_t)r * K1 + k)], im = W[2 * ((size_t)r * K1 + k) + 1];
+        const bool on = std::hypot(re, im) > 1e-12;
+        d.x = on ? re : 0.0;
+        d.y = on ? im : 0.0;
+    };
+    for (int k = 1; k <= SL; ++k) put(out->c[k - 1], 0, k);
+    for (int r = 1; r < Q; ++r)
+        for (int k = 0; k <= SL; ++k) put(out->n[r - 1][k], r, k);
 }
 
 // The geometry a call runs on: one spectrogram per workgroup, or two side by side when that takes fewer steps per spectrogram
@@ -560,7 +542,7 @@ Geom choose_geom(int F, int T, int Q, int *NS_out) {
 
 }  // namespace
 
-bool sys64_supports(int F, int T, int L, int Q, int Qp, int update, const double *W) {
+bool sys64_supports(int F, int T, int L, int Q, int update, const WeightStructure &ws) {
     if (L != SL || update != 2 || T < 1 || F < 2 * SL + 7) return false;
     if (Q != 2 && Q != 4) return false;
     // even F (a frame length that is 2 mod 4): the Nyquist bin would fall into an odd phase of the unrolled step, where its
@@ -569,7 +551,7 @@ bool sys64_supports(int F, int T, int L, int Q, int Qp, int update, const double
     int ns = 0;
     (void)choose_geom(F, T, Q, &ns);
     if (ns < 1) return false;
-    return Q == 4 ? base_weights<4>(W, Qp, nullptr) : base_weights<2>(W, Qp, nullptr);
+    return ws.quarter_turns;
 }
 
 size_t sys64_bytes(int B, int F, int T, int Q, size_t *amp_bytes) {
@@ -600,9 +582,9 @@ const char *sys64_name(int F, int T, int Q) {
 
 namespace {
 template <int Q>
-hipError_t run_passes(S64Args a, const double *W, int Qp, int NS, int wps, int n_thr, int B, hipStream_t stream, int *n_out) {
+hipError_t run_passes(S64Args a, const double *W, int NS, int wps, int n_thr, int B, hipStream_t stream, int *n_out) {
     BaseW<Q> bw;
-    if (!base_weights<Q>(W, Qp, &bw)) return hipErrorInvalidValue;
+    base_weights<Q>(W, &bw);
     // the build without the taps that the default windows' weights do not have, if this tensor has none of them either
     uint64_t mask = 0;
     for (int k = 1; k <= SL; ++k) mask |= (uint64_t)(bw.c[k - 1].x != 0 || bw.c[k - 1].y != 0) << k;
@@ -642,13 +624,13 @@ hipError_t run_passes(S64Args a, const double *W, int Qp, int NS, int wps, int n
 }
 }  // namespace
 
-hipError_t launch_sys64(const GenericArgs<double> &ga, const double *W_host, int B, void *gs, void *gamp, hipStream_t stream, int *launches,
+hipError_t launch_sys64(const GenericArgs<double> &ga, const double *W_host, const WeightStructure &ws, int B, void *gs, void *gamp, hipStream_t stream, int *launches,
                         hipEvent_t ev0, hipEvent_t ev1) {
     if (B <= 0 || ga.n_thr <= 0) return hipSuccess;
     const int F = ga.F, T = ga.T, Q = ga.Q, Tp = T + 2 * (Q - 1);
     int NS = 0;
     const Geom g = choose_geom(F, T, Q, &NS);
-    if (NS < 1 || ga.mode != MODE_BATCH || ga.L != SL) return hipErrorInvalidValue;
+    if (NS < 1 || ga.mode != MODE_BATCH || ga.L != SL || !W_host || !ws.quarter_turns) return hipErrorInvalidValue;
     double2 *G = static_cast<double2 *>(gs);
     double *A = static_cast<double *>(gamp);
     const long g_stride = g.rows * g.rw;
@@ -673,7 +655,7 @@ hipError_t launch_sys64(const GenericArgs<double> &ga, const double *W_host, int
         a.F = F; a.T = T; a.P = g.P; a.gap = g.gap; a.LAG = g.LAG; a.R = g.R; a.nblk = g.nblk; a.U = g.U;
         a.nls = g.nls; a.B = Bc;
         int n = 0;
-        e = Q == 4 ? run_passes<4>(a, W_host, ga.Qp, NS, g.rw / NLN, ga.n_thr, Bc, stream, &n) : run_passes<2>(a, W_host, ga.Qp, NS, g.rw / NLN, ga.n_thr, Bc, stream, &n);
+        e = Q == 4 ? run_passes<4>(a, W_host, NS, g.rw / NLN, ga.n_thr, Bc, stream, &n) : run_passes<2>(a, W_host, NS, g.rw / NLN, ga.n_thr, Bc, stream, &n);
         if (e != hipSuccess) return e;
         n_all += n;
         k_s64_store<<<dim3(Tp, Bc), 256, 0, stream>>>(state, G, F, Tp, g.P, g_stride, g.nls, g.rw);

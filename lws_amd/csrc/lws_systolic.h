@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lws_systolic_builds.h"
+#include "lws_weights.h"
 
 namespace lws {
 
@@ -24,9 +25,9 @@ struct SystolicPlan {
     size_t thr_chunk_cap = 0;
 };
 
-// Analyse the (host, complex128 interleaved) weight tensors and upload tables for the ones the
+// Upload tables for the (host, complex128 interleaved) weight tensors W, of the structure ws (lws_weights.h), that the
 // kernel can serve.  Never fails for "not applicable"; only for HIP errors.
-hipError_t systolic_build(SystolicPlan &sp, int F, int L, int Q, int Qp, const double *const W[3], bool fp16_storage);
+hipError_t systolic_build(SystolicPlan &sp, int F, int L, int Q, int Qp, const double *const W[3], const WeightStructure ws[3], bool fp16_storage);
 void systolic_release(SystolicPlan &sp);
 bool systolic_supports(const SystolicPlan &sp, int wsel, int T);
 // Allocates the skewed-layout scratch for calls of up to B spectrograms x T frames (so that later calls do not).

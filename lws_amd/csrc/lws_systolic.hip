@@ -2491,7 +2491,7 @@ struct Tables {
 // =============================================================================================
 // host side
 // =============================================================================================
-hipError_t systolic_build(SystolicPlan &sp, int F, int Lu, int Q, int Qp, const double *const W[3], bool fp16_storage) {
+hipError_t systolic_build(SystolicPlan &sp, int F, int Lu, int Q, int Qp, const double *const W[3], const WeightStructure ws[3], bool fp16_storage) {
     // Lu: the caller's stencil half-width (its weight tensors have Lu + 1 columns, its extended buffers 2 Lu pad columns);
     // L: that of the kernel build -- the next odd number, the extra tap with weight zero (its mask bit is clear: never fetched)
     const int L = (LWS_Q8 || LWS_TW) ? (Lu <= 5 ? 5 : Lu) : (Lu | 1), K1u = Lu + 1;   // (the Q = 8 and table-twiddle builds exist for L = 5 only: narrower stencils run on them)
@@ -2528,13 +2528,12 @@ hipError_t systolic_build(SystolicPlan &sp, int F, int Lu, int Q, int Qp, const 
     for (int i = 0; i < 3; ++i) {
         if (!W[i]) continue;
         // twiddle structure: W[p][r][k] == W[0][r][k] * exp(2j*pi*p*r*s/P) for every row p of the tensor
-        double scale = 0;
-        for (size_t x = 0; x < (size_t)Q * Q * K1u; ++x) scale = std::fmax(scale, std::hypot(W[i][2 * x], W[i][2 * x + 1]));
+        const double scale = ws[i].scale;
         // W[p][r][k] of the caller's tensor; zero for the tap an even Lu does not have
         auto wre = [&](int p, int r, int k) { return k <= Lu ? W[i][2 * ((p * Q + r) * K1u + k)] : 0.0; };
         auto wim = [&](int p, int r, int k) { return k <= Lu ? W[i][2 * ((p * Q + r) * K1u + k) + 1] : 0.0; };
         int twP = 0, twS = 0;
-        if (!lws::weights_twiddle(W[i], Q, Qp, Lu, TW ? TW_PMAX : Q, &twP, &twS)) continue;   // (lws_online.hip: every row p of the tensor, in fp64)
+        if (!ws[i].twiddle(TW ? TW_PMAX : Q, &twP, &twS)) continue;   // (lws_weights.h: every row p of the tensor, in fp64)
         if (twP == 0) { twP = Q; twS = 1; }   // (no neighbour-frame weights at all: any twiddle will do)
 #if LWS_TW
         // (tensors whose twiddles are the eighth turns of the static builds are theirs: tried before this one, lws_capi.hip)

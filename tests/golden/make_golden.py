@@ -326,6 +326,73 @@ def kernels():
     print("reference_kernels.npz", os.path.getsize(os.path.join(HERE, "reference_kernels.npz")))
 
 
+def weight_analysis(commit):
+    """What the host functions that analysed a weight tensor said before lws_amd/csrc/lws_weights.cpp replaced them:
+    weights_twiddle (lws_online.hip), weights_row_period (lws_nofuture.hip), rows_are_twiddles (lws_band.hip) and base_weights
+    (lws_sys64.hip) of `commit` -- the last one that has them, 5d9a139 -- on the tensors of tests/test_weight_analysis.py
+    (`python make_golden.py weight_analysis 5d9a139` writes only weight_analysis.json).  Their text is cut out of `git show` and
+    compiled with g++ in a temporary directory; nothing of it is kept."""
+    import ctypes as C
+    import json
+    import re
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_weight_analysis import CAPS, cases
+
+    def show(name):
+        return subprocess.run(["git", "show", "%s:lws_amd/csrc/%s" % (commit, name)], cwd=ROOT, check=True, capture_output=True, text=True).stdout
+
+    def cut(text, head):   # a definition at namespace level: from its first line to the closing brace in column 0
+        return re.search(r"^%s.*?^\}" % re.escape(head), text, re.M | re.S).group(0)
+
+    tmp = tempfile.mkdtemp(prefix="lws_weight_analysis_")
+    for h in ("lws_band_host.h", "lws_band_core.h"):
+        with open(os.path.join(tmp, h), "w") as f:
+            f.write(show(h))
+    sys64 = show("lws_sys64.hip")
+    src = "\n".join([
+        '#include <algorithm>', '#include <cmath>', '#include <cstddef>', '#include "lws_band_host.h"', '#define __host__', '#define __device__',
+        'struct double2 { double x, y; };', 'namespace lws {', 'using namespace band;', 'constexpr int SL = 5;',
+        cut(show("lws_online.hip"), "bool weights_twiddle("), cut(show("lws_nofuture.hip"), "int weights_row_period("),
+        cut(show("lws_band.hip"), "bool rows_are_twiddles("), cut(sys64, "template <int Q> struct BaseW {") + ";",
+        cut(sys64, "template <int Q> __host__ __device__ constexpr int quarter_turns("), cut(sys64, "template <int Q> bool base_weights("),
+        '}', 'extern "C" {',
+        'int twiddle(const double *W, int Q, int Qp, int L, int pmax, int *P, int *s) { return lws::weights_twiddle(W, Q, Qp, L, pmax, P, s); }',
+        'int row_period(const double *W, int Qp, int Q, int L, int pmax) { return lws::weights_row_period(W, Qp, Q, L, pmax); }',
+        'int rows(const double *W, int Q, int Qp, int L, int Pt, int s, double tol) { return lws::rows_are_twiddles(W, Q, Qp, L, Pt, s, tol); }',
+        'int base(const double *W, int Q, int Qp) { return Q == 4 ? lws::base_weights<4>(W, Qp, nullptr) : lws::base_weights<2>(W, Qp, nullptr); }',
+        '}', ''])
+    with open(os.path.join(tmp, "old.cpp"), "w") as f:
+        f.write(src)
+    so = os.path.join(tmp, "libold.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", os.path.join(tmp, "old.cpp"), "-o", so], check=True)
+    lib = C.CDLL(so)
+    lib.rows.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_double]
+    out = {}
+    for name, W in cases():
+        W = np.ascontiguousarray(W, dtype=np.complex128)
+        Qp, Q, K1 = W.shape
+        w, L = C.c_void_p(W.ctypes.data), K1 - 1
+        rec = {"shape": [Qp, Q, K1], "twiddle": {}}
+        for key, cap in [("Q", Q)] + [(str(c), c) for c in CAPS]:
+            P, s = C.c_int(-1), C.c_int(-1)
+            rec["twiddle"][key] = [P.value, s.value] if lib.twiddle(w, Q, Qp, L, cap, C.byref(P), C.byref(s)) else None
+        rec["row_period"] = lib.row_period(w, Qp, Q, L, 256)
+        fit = rec["twiddle"]["4096"]          # band_plan: cap 4096, "fits any twiddle" read as (1, 0)
+        if fit is not None:
+            Pt, s = fit if fit[0] >= 1 else (1, 0)
+            rec["rows_1e-13"], rec["rows_1e-9"] = bool(lib.rows(w, Q, Qp, L, Pt, s, 1e-13)), bool(lib.rows(w, Q, Qp, L, Pt, s, 1e-9))
+        else:
+            rec["rows_1e-13"] = rec["rows_1e-9"] = None
+        rec["base_weights"] = bool(lib.base(w, Q, Qp)) if Q in (2, 4) and K1 == 6 else None
+        assert name not in out, name
+        out[name] = rec
+    shutil.rmtree(tmp)
+    with open(os.path.join(HERE, "weight_analysis.json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("weight_analysis.json", os.path.getsize(os.path.join(HERE, "weight_analysis.json")), len(out), "tensors")
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "extra":
         extra()
@@ -333,5 +400,7 @@ if __name__ == "__main__":
         fftsize()
     elif len(sys.argv) > 1 and sys.argv[1] == "kernels":
         kernels()
+    elif len(sys.argv) > 2 and sys.argv[1] == "weight_analysis":
+        weight_analysis(sys.argv[2])
     else:
         main()
