@@ -197,6 +197,17 @@ int lws_stft_zp_dev(int device, const float *x_dev, int B, int len, int fsize, i
 int lws_consistency_dev(int device, const void *S_dev, int B, int M, int N, int fshift, const double *awin,
                         const double *swin, int perfectrec, double *out, void *stream);
 
+/* (Fast) Griffin-Lim refinement, device resident (lws_gla.hip; the reference has no counterpart).  With the projection
+ * P(c) = stft(istft(c)) -- the round trip of lws_consistency_dev, perfectrec included -- iteration i = 1..iters computes
+ * X = P(c), t_i = A X / |X| (A + 0j where |X| == 0), and c = t_i for i = 1, c = t_i + alpha (t_i - t_{i-1}) after that; alpha = 0 is
+ * plain Griffin-Lim.  C_dev[B][M][N/2+1] (complex64) holds c_0 on entry and t_iters -- whose magnitudes are A -- on return;
+ * iters == 0 leaves it unchanged.  A_dev[B][M][N/2+1] (float32) are the target magnitudes, NULL: |c_0|.  trace: NULL (the call
+ * only enqueues work on `stream`), or HOST, iters*B*2 doubles (synchronises): trace[(i-1)*B*2 + 2b] = sum |c_{i-1}|^2 and
+ * [.. + 1] = sum |P(c_{i-1}) - c_{i-1}|^2, the pair of lws_consistency_dev for the iterate entering step i.  float32 transforms,
+ * two frames per complex transform.  iters < 0 or alpha outside [0, 1): LWS_ERR_INVALID. */
+int lws_griffin_lim_dev(int device, void *C_dev, const float *A_dev, int B, int M, int N, int fshift, const double *awin,
+                        const double *swin, int perfectrec, int iters, double alpha, double *trace, void *stream);
+
 /* ---- host-side construction of windows, weights and schedules (lws.pyx:10-40,160-206), fp64, no device work: what a
  *      caller without numpy needs to build a plan.  Complex outputs are interleaved (re, im) doubles. ---- */
 

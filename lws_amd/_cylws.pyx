@@ -262,6 +262,17 @@ def lws_consistency_dev(int device, S_dev, int B, int M, int N, int fshift, awin
     return rc
 
 
+def lws_griffin_lim_dev(int device, C_dev, A_dev, int B, int M, int N, int fshift, awin, swin, int perfectrec, int iters, alpha_,
+                        trace, stream):
+    cdef uintptr_t cd = _addr(C_dev), ad = _addr(A_dev), a = _addr(awin), w = _addr(swin), t = _addr(trace), st = _addr(stream)
+    cdef double alpha = _dbl(alpha_)
+    cdef int rc
+    with nogil:
+        rc = c.lws_griffin_lim_dev(device, <void *>cd, <const float *>ad, B, M, N, fshift, <const double *>a, <const double *>w,
+                                   perfectrec, iters, alpha, <double *>t, <void *>st)
+    return rc
+
+
 def lws_hann(int n, int symmetric, int use_offset, out):
     cdef uintptr_t o = _addr(out)
     return c.lws_hann(n, symmetric, use_offset, <double *>o)

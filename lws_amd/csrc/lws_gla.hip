@@ -1,0 +1,249 @@
+// lws_gla.hip -- (Fast) Griffin-Lim refinement on the device, fused with its transforms.  One iteration projects the iterate
+// onto the consistent spectrograms, X = stft(istft(c)) -- the round trip lws_consistency_dev makes -- and rescales X to the
+// target magnitudes, t = A X / |X|, with the momentum of Fast Griffin-Lim, c = t + alpha (t - t_prev).
+//
+// Two launches per iteration, both one workgroup per PAIR of frames of one spectrogram (the transform of lws_fft.h, in LDS):
+//   k_gla_inverse : frames m, m+1 go through ONE N-point inverse transform as Z = X_m + j X_{m+1} on the Hermitian-completed
+//                   bins (real part: frame m, imaginary part: frame m+1), times the synthesis window, into the frame buffer;
+//   k_gla_forward : loads z = x_m + j x_{m+1} where each sample is the overlap-add of the windowed inverse frames that cover
+//                   it, gathered in ascending frame order (no signal buffer, no atomics), transforms once, separates
+//                   X_m[k] = (Z[k] + conj Z[N-k]) / 2, X_{m+1}[k] = (Z[k] - conj Z[N-k]) / 2j, and in its epilogue reads
+//                   c, A, t_prev and writes t, c and the per-frame fp64 sums (|c|^2, |X - c|^2) of the consistency pair.
+// An odd last frame pairs with zeros.  The iterate lives in the caller's buffer; the last iteration leaves t_n there.
+#include "../../include/lws_hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "lws_common.h"
+#include "lws_fft.h"
+
+namespace {
+
+__global__ void k_gla_abs(const float2 *C, float *A, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) A[i] = sqrtf(C[i].x * C[i].x + C[i].y * C[i].y);
+}
+
+// lws.pyx:118-128 for frames m0 = 2 blockIdx.x and m0 + 1.  np.real(ifft(Hermitian completion)) never sees the imaginary
+// parts of the bins 0 and N/2 (they transform to an imaginary signal), so they must not leak into the partner frame.
+__global__ void __launch_bounds__(FFT_THREADS) k_gla_inverse(const float2 *C, float *frames, const float *swin, int M, int N,
+                                                              int odd, int log2e) {
+    extern __shared__ float2 lds[];
+    const int m0 = 2 * blockIdx.x, b = blockIdx.y, F = N / 2 + 1;
+    const bool two = m0 + 1 < M;
+    const float2 *r0 = C + ((size_t)b * M + m0) * F, *r1 = r0 + F;
+    float2 *x = lds, *y = lds + N;
+    for (int k = threadIdx.x; k < N; k += blockDim.x) {
+        const int kk = k < F ? k : N - k;
+        float2 u = r0[kk], v = two ? r1[kk] : make_float2(0.f, 0.f);
+        if (k >= F) { u.y = -u.y; v.y = -v.y; }
+        if (kk == 0 || kk == N / 2) u.y = v.y = 0.f;
+        x[k] = make_float2(u.x - v.y, u.y + v.x);            // u + j v
+    }
+    __syncthreads();
+    const float2 *r = fft_lds(x, y, N, odd, log2e, 1.0f);
+    const float inv = 1.0f / (float)N;
+    float *o0 = frames + ((size_t)b * M + m0) * N, *o1 = o0 + N;
+    for (int n = threadIdx.x; n < N; n += blockDim.x) {
+        const float w = inv * swin[n];
+        o0[n] = r[n].x * w;
+        if (two) o1[n] = r[n].y * w;
+    }
+}
+
+// signal[t] of k_overlap_add, gathered: the frames s with 0 <= t - s hop < N, ascending; zero in the perfectrec cuts
+__device__ __forceinline__ float gla_sample(const float *f, int t, int M, int N, int hop, int zero_lo, int t_end) {
+    if (t < zero_lo || t >= t_end) return 0.f;
+    int s_hi = t / hop;
+    if (s_hi > M - 1) s_hi = M - 1;
+    const int s_lo = (t - N + 1 <= 0) ? 0 : (t - N + hop) / hop;
+    float acc = 0.f;
+    for (int s = s_lo; s <= s_hi; ++s) acc += f[(size_t)s * N + (t - s * hop)];
+    return acc;
+}
+
+struct GlaStep {
+    float alpha;      // momentum of this step (0: c = t)
+    int keep_t;       // write t to the t buffer (a later step has momentum)
+};
+
+// One bin of the epilogue: X the projection, c the iterate that entered the step.
+template <bool SUMS>
+__device__ __forceinline__ void gla_bin(float2 X, float2 *c, const float *A, float2 *T, size_t i, GlaStep st, double &p, double &e) {
+    const float2 s = c[i];
+    if (SUMS) {
+        const double dx = (double)X.x - s.x, dy = (double)X.y - s.y;
+        e += dx * dx + dy * dy;
+        p += (double)s.x * s.x + (double)s.y * s.y;
+    }
+    const float a = A[i], mag = sqrtf(X.x * X.x + X.y * X.y);
+    float2 t = make_float2(a, 0.f);
+    if (mag > 0.f) t = make_float2(a * (X.x / mag), a * (X.y / mag));
+    float2 cn = t;
+    if (st.alpha != 0.f) {
+        const float2 tp = T[i];
+        cn = make_float2(t.x + st.alpha * (t.x - tp.x), t.y + st.alpha * (t.y - tp.y));
+    }
+    if (st.keep_t) T[i] = t;
+    c[i] = cn;
+}
+
+// lws.pyx:82-88 for the frames m0, m0 + 1 of the overlap-added signal (length Tfull = hop (M - 1) + N, never stored), then the
+// magnitude projection.  rows (SUMS): [B][M][2] doubles, (sum |c|^2, sum |X - c|^2) of each frame, as k_stft_frames writes them.
+template <bool SUMS>
+__global__ void __launch_bounds__(FFT_THREADS) k_gla_forward(const float *frames, const float *awin, float2 *C, const float *A,
+                                                              float2 *T, double *rows, int M, int N, int odd, int log2e, int hop,
+                                                              int zero_lo, int zero_hi, GlaStep st) {
+    extern __shared__ float2 lds[];
+    __shared__ double red[SUMS ? 4 : 1][FFT_THREADS];
+    const int m0 = 2 * blockIdx.x, b = blockIdx.y, F = N / 2 + 1;
+    const bool two = m0 + 1 < M;
+    const int t_end = hop * (M - 1) + N - zero_hi;
+    const float *f = frames + (size_t)b * M * N;
+    float2 *xa = lds, *ya = lds + N;
+    for (int n = threadIdx.x; n < N; n += blockDim.x) {
+        const float w = awin[n];
+        const float re = gla_sample(f, m0 * hop + n, M, N, hop, zero_lo, t_end) * w;
+        const float im = two ? gla_sample(f, (m0 + 1) * hop + n, M, N, hop, zero_lo, t_end) * w : 0.f;
+        xa[n] = make_float2(re, im);
+    }
+    __syncthreads();
+    const float2 *r = fft_lds(xa, ya, N, odd, log2e, -1.0f);
+    const size_t base = ((size_t)b * M + m0) * F;
+    double p0 = 0, e0 = 0, p1 = 0, e1 = 0;
+    for (int k = threadIdx.x; k < F; k += blockDim.x) {
+        const float2 zk = r[k], zn = r[k == 0 ? 0 : N - k];
+        gla_bin<SUMS>(make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)), C, A, T, base + k, st, p0, e0);
+        if (two) gla_bin<SUMS>(make_float2(0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)), C, A, T, base + F + k, st, p1, e1);
+    }
+    if (SUMS) {
+        const int tid = threadIdx.x;
+        red[0][tid] = p0; red[1][tid] = e0; red[2][tid] = p1; red[3][tid] = e1;
+        __syncthreads();
+        for (int s2 = blockDim.x / 2; s2 > 0; s2 >>= 1) {
+            if (tid < s2)
+                for (int q = 0; q < 4; ++q) red[q][tid] += red[q][tid + s2];
+            __syncthreads();
+        }
+        if (tid < (two ? 4 : 2)) rows[((size_t)b * M + m0) * 2 + tid] = red[tid][0];
+    }
+}
+
+__global__ void k_gla_sum_rows(const double *rows, double *out, int M, int B) {   // one thread per spectrogram, fixed order
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double p = 0, e = 0;
+    for (int m = 0; m < M; ++m) { p += rows[((size_t)b * M + m) * 2]; e += rows[((size_t)b * M + m) * 2 + 1]; }
+    out[2 * b] = p;
+    out[2 * b + 1] = e;
+}
+
+// Windows and scratch of the iteration, one set per device, serialised on the device by the event scheme of lws_stft.hip.  The
+// windows stay on the device between calls: a call with the windows of the previous one uploads nothing.
+struct GlaCtx {
+    Scratch frames, t, a, rows, trace, win_a, win_s;
+    std::vector<double> host_a, host_s;   // what win_a / win_s hold
+    hipEvent_t last = nullptr;
+    bool busy = false;
+};
+std::mutex g_mu;
+GlaCtx g_ctx[MAX_DEVICES];
+
+int ctx_enter(GlaCtx &c, hipStream_t s) {
+    if (!c.last) STFT_TRY(hipEventCreateWithFlags(&c.last, hipEventDisableTiming));
+    if (c.busy) STFT_TRY(hipStreamWaitEvent(s, c.last, 0));
+    return LWS_OK;
+}
+int ctx_leave(GlaCtx &c, hipStream_t s) {
+    STFT_TRY(hipEventRecord(c.last, s));
+    c.busy = true;
+    return LWS_OK;
+}
+
+int upload_window(Scratch &dst, std::vector<double> &held, const double *w, int N, hipStream_t s) {
+    if ((int)held.size() == N && dst.p && !memcmp(held.data(), w, (size_t)N * sizeof(double))) return LWS_OK;
+    held.clear();
+    std::vector<float> f(N);
+    for (int i = 0; i < N; ++i) f[i] = (float)w[i];
+    int rc = dst.ensure((size_t)N * sizeof(float));
+    if (rc) return rc;
+    STFT_TRY(hipMemcpyAsync(dst.p, f.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice, s));
+    STFT_TRY(hipStreamSynchronize(s));   // f goes out of scope
+    held.assign(w, w + N);
+    return LWS_OK;
+}
+
+int allow_lds_all() {
+    const int bytes = 3 * MAXN * (int)sizeof(float2);
+    STFT_TRY(lws::allow_dynamic_lds<&k_gla_inverse>(bytes));
+    STFT_TRY(lws::allow_dynamic_lds<&k_gla_forward<true>>(bytes));
+    STFT_TRY(lws::allow_dynamic_lds<&k_gla_forward<false>>(bytes));
+    return LWS_OK;
+}
+
+}  // namespace
+
+extern "C" int lws_griffin_lim_dev(int device, void *C_dev, const float *A_dev, int B, int M, int N, int fshift,
+                                   const double *awin, const double *swin, int perfectrec, int iters, double alpha,
+                                   double *trace, void *stream) {
+    int rc = check_shape(device, B, M, N, fshift);
+    if (rc) return rc;
+    if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
+    if (!(alpha >= 0.0 && alpha < 1.0)) return lws::set_error(LWS_ERR_INVALID, "momentum %g outside [0, 1)", alpha);
+    if (!C_dev || !awin || !swin) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    if (B == 0 || iters == 0) return LWS_OK;
+    STFT_TRY(hipSetDevice(device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> lk(g_mu);
+    GlaCtx &c = g_ctx[device];
+    if ((rc = ctx_enter(c, s))) return rc;
+    if ((rc = allow_lds_all())) return rc;
+    if ((rc = upload_window(c.win_a, c.host_a, awin, N, s))) return rc;
+    if ((rc = upload_window(c.win_s, c.host_s, swin, N, s))) return rc;
+    const int F = N / 2 + 1;
+    const size_t bins = (size_t)B * M * F;
+    const bool momentum = alpha > 0.0 && iters > 2;   // the first step has none and the last leaves t_n, not c_n
+    if ((rc = c.frames.ensure((size_t)B * M * N * sizeof(float)))) return rc;
+    if (momentum && (rc = c.t.ensure(bins * sizeof(float2)))) return rc;
+    if (!A_dev && (rc = c.a.ensure(bins * sizeof(float)))) return rc;
+    if (trace && (rc = c.rows.ensure((size_t)B * M * 2 * sizeof(double)))) return rc;
+    if (trace && (rc = c.trace.ensure((size_t)iters * B * 2 * sizeof(double)))) return rc;
+    float2 *C = static_cast<float2 *>(C_dev), *T = static_cast<float2 *>(c.t.p);
+    float *frames = static_cast<float *>(c.frames.p);
+    const float *wa = static_cast<const float *>(c.win_a.p), *ws = static_cast<const float *>(c.win_s.p);
+    if (!A_dev) {
+        hipLaunchKernelGGL(k_gla_abs, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, s, C, static_cast<float *>(c.a.p), bins);
+        A_dev = static_cast<const float *>(c.a.p);
+    }
+    const Factors fc = factor(N);
+    const dim3 grid((M + 1) / 2, B);
+    const size_t lds = fft_lds_bytes(N);
+    // with perfectrec the reference cuts the first prepad and the last N - hop samples and the forward transform pads zeros
+    // back in their place (same frame count), as in lws_consistency_dev
+    const int zero_lo = perfectrec ? prepad(N, fshift) : 0, zero_hi = perfectrec ? N - fshift : 0;
+    for (int i = 1; i <= iters; ++i) {
+        const GlaStep st{(momentum && i >= 2 && i < iters) ? (float)alpha : 0.f, (momentum && i + 1 < iters) ? 1 : 0};
+        hipLaunchKernelGGL(k_gla_inverse, grid, dim3(FFT_THREADS), lds, s, C, frames, ws, M, N, fc.odd, fc.log2e);
+        if (trace) {
+            double *rows = static_cast<double *>(c.rows.p);
+            hipLaunchKernelGGL(k_gla_forward<true>, grid, dim3(FFT_THREADS), lds, s, frames, wa, C, A_dev, T, rows, M, N, fc.odd,
+                               fc.log2e, fshift, zero_lo, zero_hi, st);
+            hipLaunchKernelGGL(k_gla_sum_rows, dim3((B + 63) / 64), dim3(64), 0, s, rows,
+                               static_cast<double *>(c.trace.p) + (size_t)(i - 1) * B * 2, M, B);
+        } else {
+            hipLaunchKernelGGL(k_gla_forward<false>, grid, dim3(FFT_THREADS), lds, s, frames, wa, C, A_dev, T,
+                               static_cast<double *>(nullptr), M, N, fc.odd, fc.log2e, fshift, zero_lo, zero_hi, st);
+        }
+    }
+    STFT_TRY(hipGetLastError());
+    if (trace) {
+        STFT_TRY(hipMemcpyAsync(trace, c.trace.p, (size_t)iters * B * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+        STFT_TRY(hipStreamSynchronize(s));
+    }
+    return ctx_leave(c, s);
+}

@@ -178,6 +178,87 @@ def istft_dev(spec, fshift, swin, awin=None, fftsize=None, perfectrec=False, dev
     return out[0] if single else out
 
 
+# --------------------------------------------------------------------------------------------
+# Griffin-Lim refinement (no counterpart in the reference): host fp64 definition, and the device form (lws_gla.hip)
+# --------------------------------------------------------------------------------------------
+def _gla_args(iterations, alpha):
+    if int(iterations) != iterations or iterations < 0:
+        raise ValueError('iterations must be a non-negative integer, got %r' % (iterations,))
+    if not 0.0 <= float(alpha) < 1.0:
+        raise ValueError('alpha must be in [0, 1), got %r' % (alpha,))
+    return int(iterations), float(alpha)
+
+
+def griffin_lim(S, fsize, fshift, awin, swin, iterations, alpha=0.99, magnitudes=None, perfectrec=False, return_trace=False,
+                _perturb=None):
+    """(Fast) Griffin-Lim iterations from the start S, (T, F) or a stack (B, T, F), in fp64 on the host: the definition the
+    device form is held to.  With P(c) = stft(istft(c)) -- the round trip get_consistency makes -- step i = 1..iterations is
+    X = P(c), t_i = A X / |X| (A + 0j where |X| == 0), c = t_i for i = 1 and t_i + alpha (t_i - t_{i-1}) after that.  Returns
+    t_n (its magnitudes are A = `magnitudes`, by default |S|); zero iterations return S.  alpha = 0 is plain Griffin-Lim.
+    return_trace: also the consistency in dB, 10 log10(sum |c|^2 / sum |P(c) - c|^2), of the iterate entering each step,
+    shape (iterations,) / (iterations, B).  (_perturb(i, b, X) -> X: replaces each projection; the error model of the tests.)"""
+    n, alpha = _gla_args(iterations, alpha)
+    S = np.asarray(S)
+    if S.ndim not in (2, 3):
+        raise ValueError('expected a (T, F) spectrogram or a (B, T, F) stack')
+    A = np.abs(S) if magnitudes is None else np.asarray(magnitudes, dtype=np.float64)
+    if A.shape != S.shape:
+        raise ValueError('magnitudes of shape %s for a spectrogram of shape %s' % (A.shape, S.shape))
+    if n == 0:
+        return (S, np.zeros((0,) + S.shape[:-2])) if return_trace else S
+    S3, A3 = (S[None], A[None]) if S.ndim == 2 else (S, A)
+    out = np.empty(S3.shape, dtype=np.complex128)
+    db = np.empty((n, S3.shape[0]))
+    for b in range(S3.shape[0]):
+        c, t_prev = S3[b].astype(np.complex128), None
+        for i in range(1, n + 1):
+            X = stft(istft(c, fshift, swin, perfectrec=perfectrec), fsize, fshift, awin, perfectrec=perfectrec)
+            if X.shape != c.shape:
+                raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (c.shape[0], X.shape[0]))
+            if _perturb is not None:
+                X = _perturb(i, b, X)
+            db[i - 1, b] = 10 * np.log10(np.sum(np.abs(c) ** 2) / np.sum(np.abs(X - c) ** 2))
+            mag = np.abs(X)
+            t = np.where(mag > 0, A3[b] * X / np.where(mag > 0, mag, 1.0), A3[b] + 0j)
+            c = t if i == 1 else t + alpha * (t - t_prev)
+            t_prev = t
+        out[b] = t_prev
+    if S.ndim == 2:
+        out, db = out[0], db[:, 0]
+    return (out, db) if return_trace else out
+
+
+def griffin_lim_dev(S, fsize, fshift, awin, swin, iterations, alpha=0.99, magnitudes=None, perfectrec=False, return_trace=False,
+                    device=0):
+    """griffin_lim() above on the device (lws_gla.hip: float32, the transforms fused with the magnitude projection, two launches
+    per iteration): S (T, F) or (B, T, F), numpy or torch; returns a new complex64 torch tensor (S itself is not modified), and
+    with return_trace also the dB values as a numpy array.  Runs on the caller's current torch stream; without return_trace
+    the call only enqueues work."""
+    import torch
+    n, alpha = _gla_args(iterations, alpha)
+    t = _dev_tensor(S, torch.complex64, device)
+    if t.dim() not in (2, 3):
+        raise ValueError('expected a (T, F) spectrogram or a (B, T, F) stack')
+    single = t.dim() == 2
+    t3 = (t[None] if single else t).clone()
+    B, T, F = t3.shape
+    if F != fsize // 2 + 1:
+        raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
+    A = None
+    if magnitudes is not None:
+        A = _dev_tensor(magnitudes, torch.float32, device)
+        if A.shape != t.shape:
+            raise ValueError('magnitudes of shape %s for a spectrogram of shape %s' % (tuple(A.shape), tuple(t.shape)))
+    trace = _capi.griffin_lim_dev(t3.data_ptr(), None if A is None else A.data_ptr(), B, T, fsize, fshift, awin, swin, perfectrec,
+                                  n, alpha, want_trace=return_trace, device=int(device),
+                                  stream=torch.cuda.current_stream(t3.device).cuda_stream)
+    out = t3[0] if single else t3
+    if not return_trace:
+        return out
+    db = 10 * np.log10(trace[..., 0] / trace[..., 1])
+    return out, (db[:, 0] if single else db)
+
+
 def extspec(S, L, Q):
     """Extended spectrogram: L Hermitian columns each side, Q-1 repeated frames each end (lws.pyx:146-157)."""
     S = np.asarray(S)
@@ -502,6 +583,17 @@ class lws(object):
 
     def istft(self, S):
         return istft(S, self.fshift, self.swin, perfectrec=self.perfectrec)
+
+    # ---- Griffin-Lim refinement of a phase estimate, e.g. of what run_lws returned (no counterpart in the reference) ----
+    def griffin_lim(self, S, iterations, alpha=0.99, magnitudes=None, return_trace=False):
+        """Host fp64 form with this object's windows and perfectrec: see the module's griffin_lim."""
+        return griffin_lim(S, self.fsize, self.fshift, self.awin, self.swin, iterations, alpha=alpha, magnitudes=magnitudes,
+                           perfectrec=self.perfectrec, return_trace=return_trace)
+
+    def griffin_lim_dev(self, S, iterations, alpha=0.99, magnitudes=None, return_trace=False):
+        """Device form: a new complex64 torch tensor, see the module's griffin_lim_dev."""
+        return griffin_lim_dev(S, self.fsize, self.fshift, self.awin, self.swin, iterations, alpha=alpha, magnitudes=magnitudes,
+                               perfectrec=self.perfectrec, return_trace=return_trace, device=self.device)
 
     def nofuture_lws(self, S, iterations=None, thresholds=None):
         if iterations is None:
