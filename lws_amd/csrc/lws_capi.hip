@@ -287,6 +287,7 @@ struct Route {
     bool ordered = false;    // team engine: the online stage on its order-exact kernel
     bool one_wave = false;   // online64: the one-wave kernel
     lws::BandPlan bp{};      // band engine
+    lws::OnlinePlan op{};    // online LDS engine
 };
 
 // The engine of a stage: the first one, from `from` on, whose guard holds.  The routing switches (comparison runs) are read once per call:
@@ -329,7 +330,7 @@ Route choose_engine(const lws_plan *p, const Stage &st, Engine from = Engine::Sy
     if (at(Engine::TeamFirst) && team_first && (!fp64 || team_fp64 || online) && team()) return pick(Engine::TeamFirst);
     // 2. online and no-future sweeps: the moving window / the last Q + 1 frames in LDS (fp64: the generic engine's bits)
     if (at(Engine::OnlineLds) && !fp64 && online && !generic &&
-        lws::online_lds_supports(F, T, L, Q, Qp, LA, n, 2, p->twiddle_all ? p->tw_P : 0, p->tw_s, p->online_tw.p != nullptr))
+        (r.op = lws::online_plan(F, T, L, Q, Qp, LA, n, 2, p->twiddle_all ? p->tw_P : 0, p->tw_s, p->online_tw.p != nullptr)).ok)
         return pick(Engine::OnlineLds);
     if (at(Engine::NofutureLds) && nofuture && !generic &&
         (fp64 ? lws::nofuture_lds64_supports(F, T, L, Q, Qp, p->wstruct[st.wsel].row_period) : lws::nofuture_lds_supports(F, T, L, Q, Qp, p->wstruct[st.wsel].row_period)))
@@ -408,7 +409,7 @@ int launch_route(lws_plan *p, const Route &r, const lws::GenericArgs<real> &a, i
         what = "team engine";
         break;
     case Engine::OnlineLds:
-        if constexpr (!fp64) e = lws::launch_online_lds(a, B, p->tw_P, p->tw_s, static_cast<const float *>(p->online_tw.p), s);
+        if constexpr (!fp64) e = lws::launch_online_lds(r.op, a, B, p->tw_P, static_cast<const float *>(p->online_tw.p), s);
         name = "online_lds_fp32", what = "online";
         break;
     case Engine::NofutureLds:

@@ -35,6 +35,10 @@
 // full weight tensor and in the generic engine's order, which makes the result bit-identical to lws_generic.hip's fp32
 // online mode; tests use it to pin the schedule, frame window and slot logic at sizes where fp32-vs-fp64 comparisons
 // are dominated by the algorithm's own sensitivity.
+//
+// Two layouts share this schedule: k_online, the one described above (frames below 17 bins, long look-aheads), and k_online4
+// further down (one wave per tap group: the default where it fits).  online_plan chooses between them once per stage and
+// launch_online_lds runs what it chose.
 #include "lws_common.h"
 #include "lws_online.h"
 
@@ -44,7 +48,7 @@
 #include <utility>
 
 namespace lws {
-#ifdef LWS_LAB   // tools/online_budget.hip: per-wave phase stamps of k_online3 / k_online4 (block 0), clocks summed over the steps.
+#ifdef LWS_LAB   // tools/online_budget.hip: per-wave phase stamps of k_online4 (block 0), clocks summed over the steps.
 // s_memtime returns through the scalar-memory counter, so reading a stamp drains the wave's LDS operations too: level 1 puts
 // stamps only where the wave is about to wait for everything in flight anyway; level 2 (-DLWS_LAB=2) adds one in front of every
 // barrier (turning the projection wave's counted wait into a full one: who waits for whom, at the price of a longer step).
@@ -98,16 +102,9 @@ __device__ __forceinline__ void pair(float2 &a, float2 w, float2 b, float2 c) { 
     a.x += w.x * (b.x + c.x) - w.y * (b.y - c.y);
     a.y += w.x * (b.y + c.y) + w.y * (b.x - c.x);
 }
-__device__ __forceinline__ void cmac(float2 &a, float2 w, float2 v) {    // a += w * v
-    a.x = fmaf(-w.y, v.y, fmaf(w.x, v.x, a.x));
-    a.y = fmaf(w.y, v.x, fmaf(w.x, v.y, a.y));
-}
-__device__ __forceinline__ void cmacc(float2 &a, float2 w, float2 v) {   // a += conj(w) * v
-    a.x = fmaf(w.y, v.y, fmaf(w.x, v.x, a.x));
-    a.y = fmaf(-w.y, v.x, fmaf(w.x, v.y, a.y));
-}
 
-// The same two as packed instructions.  A complex value is an aligned register pair (re, im); "w times v" is
+// a += w * v (cmac_pk) and a += conj(w) * v (cmacc_pk) as packed instructions.  A complex value is an aligned register pair
+// (re, im); "w times v" is
 //   (re, im) += w.re * (v.re, v.im)     and     (re, im) += w.im * (-v.im, v.re)   [conj(w): (+v.im, -v.re)],
 // each ONE v_pk_fma_f32 when the half-swap and the sign are the instruction's own operand modifiers (op_sel / neg), which
 // the compiler does not derive from C++ (it builds the swapped operand with moves): 2 instructions per tap instead of 4-6.
@@ -399,418 +396,24 @@ __global__ void __launch_bounds__(MAXT) k_online(OnlineArgs a) {
 }
 
 // =====================================================================================================================
-// Third layout (k_online3): one WAVE per tap group, one lane per (sweep slot, frame position).
+// Fourth layout (k_online4; the default where it fits): one WAVE per tap group, one lane per (sweep slot, frame position).
 //
 // In the layout above every wave carries the whole dependent tail of a step -- cross-lane reduction, two re-projections,
 // the image upkeep -- for one lane in 2Q: ~2/3 of the instructions a step issues.  Here wave w < 2Q-1 sums the taps of ONE
-// frame offset (wave 0: the centre frame, waves 2r-1 / 2r: frames rho-r / rho+r) for all 64 (slot, position) units at once
-// and leaves the two partial sums of a unit in LDS; the last wave adds them up, re-projects and writes.  The tap waves work
-// ONE STEP AHEAD of it (double-buffered partial sums, one barrier per step), so the tail of step t overlaps the sums of step
-// t+1.  That is order-exact because the values a tap wave reads one step early are final already -- every writer is at
-// least L + 3 bins away from a window (2 DS >= SKB Q + 2 is required here) -- with three exceptions, which the tap waves
-// leave out (zero window slots) and the last wave adds itself:
+// frame offset (the centre frame, or frame rho-r / rho+r) for all 64 (slot, position) units at once and leaves the two
+// partial sums of a unit in LDS; the projection wave adds them up, re-projects and writes.  The tap waves work ONE STEP
+// AHEAD of it (double-buffered partial sums, one barrier per step), so the tail of step t overlaps the sums of step t+1.
+// That is order-exact because the values a tap wave reads one step early are final already -- every writer is at least
+// L + 3 bins away from a window (2 DS >= SKB Q + 2 is required here) -- with two exceptions, which the tap waves leave
+// out (zero window slots) and the projection wave adds itself:
 //   * frame rho-1 is SKB = L + 3 bins ahead: the last column of its window (bin c+1, tap +L) is being written;
 //   * the centre frame's own recent outputs: columns c-2, c-1 (previous step), c (this step's first bin, read by the
 //     second) and the Hermitian images of those three bins near the frame edges.  The centre wave reloads its window from
 //     LDS every step (the unit's own writes land inside it), minus those columns.
-// SERIAL (verification): the last wave sums every tap itself, from LDS, in the generic engine's order; same schedule.
-// Waves of k_online3: 2Q-1 tap waves and the projection wave; Q = 4 adds an idle ninth wave so that the projection wave --
-// the dependent chain every step waits for -- has a SIMD to itself (hardware waves w and w + 4 share one: it is wave 3, the
-// idle one wave 7).
-template <int Q> struct Online3Waves {
-    static constexpr int N = (Q == 4) ? 9 : 2 * Q;
-    static constexpr int PROJ = (Q == 8) ? 15 : 3, IDLE = (Q == 4) ? 7 : -1;
-    static __host__ __device__ constexpr int tap_of(int hw) { return hw - (hw > PROJ ? 1 : 0) - (IDLE >= 0 && hw > IDLE ? 1 : 0); }
-};
-
-template <int Q, int L, bool SERIAL>
-__global__ void __launch_bounds__(Online3Waves<Q>::N * 64) k_online3(OnlineArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int K1 = L + 1, WN = 2 * L + 2, NTW = 2 * Q - 1;                  // NTW tap waves, then the projection wave
-    constexpr int SKB = 2 * ((L + 3) / 2), SKS = SKB / 2;
-    static_assert(SKB >= L + 3, "the tap waves run one step ahead");
-    const int DS = a.DS;
-    const int F = a.F, T = a.T, LA = a.LA, NSW = a.NSW, Np = F + 2 * L, Tp = T + 2 * (Q - 1), N = F - 1;
-    const int NU = (F + 1) / 2;
-    const int rps = LA + 1, per = a.n_thr + 1;
-    const int nsweeps = T * per;
-    // step types of the centre frame's edge terms: 0 none, 1..NLO the steps u = 1..NLO after a frame start, then N - c = 0..NHI-1
-    constexpr int NLO = (L + 2) / 4, NHI = (L + 1) / 2 + 1, NST = 1 + NLO + NHI;
-    float4 *P = reinterpret_cast<float4 *>(smem);                               // [2][NTW][64]: (sum of bin c, of bin c+1)
-    float2 *ET = reinterpret_cast<float2 *>(P + 2 * NTW * 64);                  // [3][NST][6] (padded to 64 entries): edge-term weights
-    float2 *S = ET + 192 + 64;                                                  // [NW][Np] (+ 2); the 64 entries below it: where image stores
-                                                                                // of bins without an image go
-    float *A = reinterpret_cast<float *>(S + (size_t)NW * Np + 2);              // [NW][Np]
-    float2 *W = reinterpret_cast<float2 *>(A + (size_t)NW * Np + ((NW * Np) & 1));   // [3][Q][Q][K1]
-    float2 *TW = W + 3 * Q * Q * K1;                                            // [Q]
-    float *thr_s = reinterpret_cast<float *>(TW + Q);                           // [n_thr]
-    const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
-    const int hw_wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int wave = Online3Waves<Q>::tap_of(hw_wave);   // tap group of a tap wave
-    float2 *gS = a.state + (size_t)b * Tp * Np;
-    const float *gA = a.amp + (size_t)b * Tp * Np;
-
-    for (int i = tid; i < 3 * Q * Q * K1; i += nthr) {
-        const int x = i % (Q * Q * K1);
-        W[i] = (x % (Q * K1) == 0) ? make_float2(0.f, 0.f) : a.w[i / (Q * Q * K1)][x];
-    }
-    if (tid < Q) TW[tid] = a.tw[tid];
-    for (int i = tid; i < NW * Np + 2; i += nthr) S[i] = make_float2(0.f, 0.f);
-    for (int i = tid; i < 2 * NTW * 64; i += nthr) P[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    __syncthreads();
-    // Edge-term weights of the projection wave (see there): entry [wset][type][j], j = 0..2: what multiplies the conjugate of
-    // the current value of bin c-j in the sum of bin c; 3, 4: of bins c-1, c-2 in the sum of bin c+1; 5: of (the new) bin c in
-    // the sum of bin c+1.  Low edge (image column -y, tap k = c + y backwards): W[k]; high edge (column 2N - y, tap
-    // k = 2(N-c) + d forwards): conj W[k].  W_ai (wset 1) has no centre term.
-    if (tid < 3 * NST * 6) {
-        const int ws = tid / (NST * 6), st = (tid / 6) % NST, jj = tid % 6;
-        const float2 *wb = W + (ws * Q) * Q * K1;
-        const int d = jj < 3 ? jj : (jj < 5 ? jj - 2 : 0), shift = jj < 3 ? 0 : 1;   // shift: the tap index moves by one for bin c+1
-        float2 w = make_float2(0.f, 0.f);
-        if (ws != 1 && st >= 1 && st <= NLO) {
-            const int c = 2 * st, y = c - d, k = c + y + shift;
-            if (y >= 1 && k <= L) w = wb[k];
-        } else if (ws != 1 && st > NLO) {
-            const int g = st - NLO - 1, k = 2 * g + d - shift;
-            if (g + d >= 1 && g + d <= L && k >= 1 && k <= L) w = make_float2(wb[k].x, -wb[k].y);
-        }
-        ET[tid] = w;
-    }
-    if (tid < 64) S[-64 + tid] = make_float2(0.f, 0.f);
-    __syncthreads();
-    for (int i = tid; i < a.n_thr; i += nthr) thr_s[i] = a.thr[(size_t)b * a.n_thr + i];
-    int loaded = Q < T + Q - 1 ? Q : T + Q - 1;
-    for (int i = tid; i < loaded * Np; i += nthr) { S[i] = gS[i]; A[i] = gA[i]; }
-
-    // this lane's unit: frame position j of sweep slot sigma; this wave's tap group: frame offset r, side h
-    const int sigma = lane / rps, j = lane - sigma * rps;
-    const bool lane_used = sigma < NSW;
-    const bool is_proj = hw_wave == Online3Waves<Q>::PROJ, is_idle = hw_wave == Online3Waves<Q>::IDLE;
-    const int r = (wave + 1) >> 1, h = (wave == 0) ? 0 : ((wave + 1) & 1);
-    int s = sigma;
-    int rho = 0, tstart = 0, t_done = 0, ts = 1, wset = 0;
-    int fb = 0, ctb = 0, fbm1 = 0;
-    bool valid = false, centre = false;
-    float thr = 0.f;
-    v2f w0[K1];                         // tap waves: W[wset][0][r][k] (side 0) or its conjugate (side 1)
-    v2f twg[Q];                         // tap waves: gain * exp(2 pi j row r / Q) (conjugated on side 1), row = bin % Q
-    v2f wc[K1];                         // projection wave: centre weights W[wset][0][0][k] (zero if the centre frame takes no part)
-    v2f wlate = {0.f, 0.f};             // ... and conj W[wset][0][1][L]
-    auto setup = [&]() {
-        const int m = s / per, q = s - m * per;
-        const int first = m - LA > 0 ? m - LA : 0;
-        if (q == 0) { valid = (j == 0); rho = m; wset = 1; centre = false; ts = 1; thr = 0.f; }
-        else {
-            rho = first + j; valid = rho <= m; wset = (rho == m) ? 2 : 0; centre = true;
-            ts = m - rho + 1; if (ts > Q) ts = Q;
-            thr = thr_s[q - 1];
-        }
-        valid = valid && lane_used && s < nsweeps;
-        tstart = DS * s + SKS * rho;
-        t_done = DS * s + SKS * m + NU - 1;
-        const int e = rho + Q - 1;
-        fb = ((h ? e + r : e - r) & (NW - 1)) * Np;
-        ctb = (e & (NW - 1)) * Np;
-        fbm1 = ((e - 1) & (NW - 1)) * Np;
-        const float2 *wb = W + (wset * Q + 0) * Q * K1;
-        if (is_proj) {
-#pragma unroll
-            for (int k = 0; k <= L; ++k) wc[k] = centre ? as_v2f(wb[k]) : (v2f){0.f, 0.f};
-            const float2 wl_ = wb[1 * K1 + L];
-            wlate = (v2f){wl_.x, -wl_.y};
-        } else {
-            float gain;
-            if (h == 0) gain = (r == 0) ? (centre ? 1.f : 0.f) : 1.f;
-            else gain = (r != 0 && r < ts) ? 1.f : 0.f;
-#pragma unroll
-            for (int k = 0; k <= L; ++k) {
-                const float2 w = wb[r * K1 + k];
-                w0[k] = (v2f){w.x, h ? -w.y : w.y};
-            }
-#pragma unroll
-            for (int row = 0; row < Q; ++row) {
-                const float2 tw = TW[(row * r) & (Q - 1)];
-                twg[row] = (v2f){gain * tw.x, gain * (h ? -tw.y : tw.y)};
-            }
-        }
-    };
-    __syncthreads();
-    setup();
-
-    const int t_end = DS * (nsweeps - 1) + SKS * (T - 1) + NU;
-    int next_need = (loaded - (Q - 1)) * (DS * per + SKS);
-    // bring in the next frame before the iteration in which a tap wave first touches it (the step after next)
-    auto load_frames = [&](int t) {
-        while (loaded < T + Q - 1 && next_need <= t + 2) {
-            const int slot = (loaded & (NW - 1)) * Np;
-            const bool evict = loaded >= NW;
-            for (int i = tid; i < Np; i += nthr) {
-                if (evict) gS[(size_t)(loaded - NW) * Np + i] = S[slot + i];
-                S[slot + i] = gS[(size_t)loaded * Np + i];
-                A[slot + i] = gA[(size_t)loaded * Np + i];
-            }
-            ++loaded;
-            next_need += DS * per + SKS;
-        }
-    };
-
-    // the sums of one step of a tap wave; KIND 0: frames rho-+r; 1: frame rho-1 (the last column of its window is still being
-    // written: left out); 2: the centre frame (its unit's own recent outputs are left out)
-    auto tap_loop = [&](auto kind_c) __attribute__((always_inline)) {
-        constexpr int KIND = decltype(kind_c)::value;
-        v2f wl[WN];
-#pragma unroll
-        for (int i = 0; i < WN; ++i) wl[i] = (v2f){0.f, 0.f};
-        LAB(unsigned long long lab_acc[4] = {0, 0, 0, 0};)
-        for (int t = -1; t < t_end; ++t) {
-            const int tt = t + 1;               // the step these waves prepare
-            const int u = tt - tstart;
-            LAB(const unsigned long long lt0 = lab_now(); unsigned long long lt1 = lt0;)
-            if (!SERIAL && valid && u >= 0 && u < NU) {
-                const int c = 2 * u;
-                // the window, columns c-L .. c+L+1 of this wave's frame, fresh from LDS (whatever is written concurrently is
-                // among the columns left out)
-                const float2 *src = S + fb + c;
-                if (KIND == 2 || u == 0) {
-#pragma unroll
-                    for (int i = 0; i < WN; ++i) {
-                        const bool skip = (KIND == 1 && i == WN - 1) || (KIND == 2 && i >= L - 2 && i <= L);
-                        wl[i] = skip ? (v2f){0.f, 0.f} : as_v2f(src[i]);
-                    }
-                } else {   // the window slides by two columns per step (no writer comes near it: see the header)
-                    constexpr int LG = KIND == 1 ? 1 : 0;
-#pragma unroll
-                    for (int i = 0; i < WN - 2; ++i) wl[i] = wl[i + 2];
-                    wl[WN - 2 - LG] = as_v2f(src[WN - 2 - LG]);
-                    wl[WN - 1 - LG] = as_v2f(src[WN - 1 - LG]);
-                    if (LG) wl[WN - 1] = (v2f){0.f, 0.f};
-                }
-                if constexpr (KIND == 2) {
-                    // images of the bins y = c-d (d = 0, 1, 2) inside the window: column -y (1 <= y) at slot L - 2c + d, column
-                    // 2N - y (N-L <= y <= N-1) at slot L + 2(N-c) + d -- a handful of (step, slot) pairs, spelled out
-                    const int g = N - c;
-                    if (2 * c <= L + 2 || 2 * g <= L + 1) {
-                        static_for<(L + 2) / 4>([&](auto iu) {
-                            constexpr int U = decltype(iu)::value + 1, C = 2 * U;
-                            if (u == U) {
-                                static_for<3>([&](auto id) {
-                                    constexpr int D = decltype(id)::value, I = L - 2 * C + D;
-                                    if constexpr (C - D >= 1 && I >= 0 && I < WN) wl[I] = (v2f){0.f, 0.f};
-                                });
-                            }
-                        });
-                        static_for<(L + 1) / 2 + 1>([&](auto ig) {
-                            constexpr int G = decltype(ig)::value;
-                            if (g == G) {
-                                static_for<3>([&](auto id) {
-                                    constexpr int D = decltype(id)::value, I = L + 2 * G + D;
-                                    if constexpr (G + D >= 1 && G + D <= L && I < WN) wl[I] = (v2f){0.f, 0.f};
-                                });
-                            }
-                        });
-                    }
-                }
-                LAB(lt1 = lab_now();)
-                // sum w[k] X[c-k] + conj(w[k]) X[c+k] over this wave's frame X, for the bins c (a) and c+1 (b)
-                v2f a14 = {0.f, 0.f}, b14 = {0.f, 0.f};
-                if constexpr (KIND != 2) {       // (the centre frame's own bin is not a tap)
-                    cmac_pk(a14, w0[0], wl[L]);
-                    cmac_pk(b14, w0[0], wl[L + 1]);
-                }
-#pragma unroll
-                for (int k = 1; k <= L; ++k) {
-                    cmac_pk(a14, w0[k], wl[L - k]);  cmacc_pk(a14, w0[k], wl[L + k]);
-                    cmac_pk(b14, w0[k], wl[L + 1 - k]);  cmacc_pk(b14, w0[k], wl[L + 1 + k]);
-                }
-                v2f twa = twg[0], twb = twg[1 & (Q - 1)];
-#pragma unroll
-                for (int row = 2; row < Q; row += 2) {
-                    if ((c & (Q - 1)) == row) { twa = twg[row]; twb = twg[row + 1]; }
-                }
-                v2f pa = {0.f, 0.f}, pb = {0.f, 0.f};
-                cmac_pk(pa, twa, a14);
-                cmac_pk(pb, twb, b14);
-                P[((tt & 1) * NTW + wave) * 64 + lane] = make_float4(pa.x, pa.y, pb.x, pb.y);
-            }
-            LAB(const unsigned long long lt2 = lab_now();)
-            if (tt >= t_done) { s += NSW; setup(); }
-            load_frames(t);
-            LAB(const unsigned long long lt3 = lab_now();)
-            __syncthreads();
-            LAB(const unsigned long long lt4 = lab_now(); lab_acc[0] += lt1 - lt0; lab_acc[1] += lt2 - lt1; lab_acc[2] += lt3 - lt2; lab_acc[3] += lt4 - lt3;)
-        }
-        LAB(if (b == 0 && lane == 0) { for (int i = 0; i < 4; ++i) g_lab[8 + hw_wave * 8 + i] = lab_acc[i]; })
-    };
-    if (is_idle) {
-        for (int t = -1; t < t_end; ++t) { load_frames(t); __syncthreads(); }
-    } else if (!is_proj) {
-        if (wave == 0) tap_loop(std::integral_constant<int, 2>{});
-        else if (wave == 1) tap_loop(std::integral_constant<int, 1>{});
-        else tap_loop(std::integral_constant<int, 0>{});
-    } else {
-        // ------------------------------------------------------------------------------------------ projection wave
-        asm volatile("s_setprio 3");            // the dependent chain of a step: ahead of the tap waves of its SIMD
-        v2f p1 = {0.f, 0.f}, p2 = {0.f, 0.f};   // current values of columns c-1, c-2 of the unit's frame
-        LAB(unsigned long long lab_acc[4] = {0, 0, 0, 0};)
-        for (int t = -1; t < t_end; ++t) {
-            const int u = t - tstart;
-            LAB(const unsigned long long lt0 = lab_now(); unsigned long long lt1 = lt0;)
-            if (t >= 0 && valid && u >= 0 && u < NU) {
-                const int c = 2 * u, n = c + L;
-                const bool has_b = c + 1 < F;
-                const int li = ctb + n;
-                if constexpr (SERIAL) {
-                    const int e = rho + Q - 1;
-                    const float2 zero = make_float2(0.f, 0.f);
-#pragma unroll
-                    for (int bb = 0; bb < 2; ++bb) {
-                        const int cb = c + bb, nb = n + bb;
-                        if (cb >= F) break;
-                        const int row = cb % Q, rowneg = (Q - row) % Q;
-                        const float2 *wa = W + wset * Q * Q * K1 + row * Q * K1;
-                        float2 acc = zero;
-                        if (centre) {
-                            const float2 *ctr = S + ctb + nb;
-#pragma unroll
-                            for (int k = 1; k <= L; ++k) pair(acc, wa[k], ctr[-k], ctr[k]);
-                        }
-#pragma unroll
-                        for (int rr = 1; rr < Q; ++rr) {
-                            const float2 *lf = S + ((e - rr) & (NW - 1)) * Np + nb;
-                            const float2 *rt = S + ((e + rr) & (NW - 1)) * Np + nb;
-                            const float2 *wa_r = W + wset * Q * Q * K1 + (row * Q + rr) * K1;
-                            const float2 *wb_r = W + wset * Q * Q * K1 + (rowneg * Q + rr) * K1;
-                            const bool two = rr < ts;
-                            pair(acc, wa_r[0], lf[0], two ? rt[0] : zero);
-#pragma unroll
-                            for (int k = 1; k <= L; ++k) {
-                                pair(acc, wa_r[k], lf[-k], two ? rt[-k] : zero);
-                                pair(acc, wb_r[k], two ? rt[k] : zero, lf[k]);
-                            }
-                        }
-                        const int lj = ctb + nb;
-                        const float target = A[lj];
-                        if (target > thr) {
-                            const float mag = sqrtf(acc.x * acc.x + acc.y * acc.y);
-                            if (mag > 0.f) {
-                                const float2 v = make_float2(acc.x * target / mag, acc.y * target / mag);
-                                const float2 vc = make_float2(v.x, -v.y);
-                                S[lj] = v;
-                                const int nyq = F + L - 1;
-                                if (nb >= L + 1 && nb < 2 * L + 1) S[lj + 2 * (L - nb)] = vc;
-                                else if (nb >= F - 1 && nb < nyq) S[lj + 2 * (nyq - nb)] = vc;
-                            }
-                        }
-                    }
-                } else {
-                    // everything the step reads, up front: one wait
-                    const float4 *pp = P + (t & 1) * NTW * 64 + lane;
-                    float4 part[NTW];
-#pragma unroll
-                    for (int w = 0; w < NTW; ++w) part[w] = pp[w * 64];
-                    const v2f oldA = as_v2f(S[li]), oldB = as_v2f(S[li + 1]);
-                    const float target_a = A[li], target_b = A[li + 1];
-                    const v2f xlate = as_v2f(S[fbm1 + c + 1 + 2 * L]);
-                    const v2f twl = as_v2f(TW[(c + 1) & (Q - 1)]);
-                    const v2f im1 = as_v2f(S[ctb + L - 1]), im2 = as_v2f(S[ctb + L - 2]);   // columns -1, -2 (images): what a frame starts with
-                    const int g = N - c;
-                    const int stype = (u >= 1 && u <= NLO) ? u : (g < NHI ? NLO + 1 + g : 0);
-                    const float4 *et = reinterpret_cast<const float4 *>(ET + (wset * NST + stype) * 6);
-                    const float4 e01 = et[0], e23 = et[1], e45 = et[2];
-                    LAB(lt1 = lab_now();)
-                    if (u == 0) { p1 = im1; p2 = im2; }
-                    v2f accA = {part[0].x, part[0].y}, accB = {part[0].z, part[0].w};
-#pragma unroll
-                    for (int w = 1; w < NTW; ++w) {
-                        accA += (v2f){part[w].x, part[w].y};
-                        accB += (v2f){part[w].z, part[w].w};
-                    }
-                    // frame rho-1, bin c+1, tap +L: the column that was being written while the tap wave summed
-                    {
-                        v2f x = {0.f, 0.f};
-                        cmac_pk(x, wlate, xlate);
-                        cmac_pk(accB, twl, x);
-                    }
-                    // the centre frame's columns c-1, c-2 (and c, below): the unit's own last outputs
-                    cmac_pk(accA, wc[1], p1);
-                    cmac_pk(accA, wc[2], p2);
-                    cmac_pk(accB, wc[2], p1);
-                    if (L >= 3) cmac_pk(accB, wc[L >= 3 ? 3 : 0], p2);
-                    // ... and their Hermitian images near the frame edges: the image of bin y = c-d is column -y, tap k = c + y of
-                    // bin c (k + 1 of bin c+1), or column 2N - y, tap k = 2(N-c) + d forwards (k - 1 of bin c+1) -- a handful
-                    // of (step, tap) pairs.  Their weights come from a table indexed by the kind of step (zeros for all but ~4
-                    // steps of a frame), so that the chain every step waits for has no branch here.
-                    {
-                        const v2f cjA = {oldA.x, -oldA.y}, cj1 = {p1.x, -p1.y}, cj2 = {p2.x, -p2.y};
-                        cmac_pk(accA, (v2f){e01.x, e01.y}, cjA);
-                        cmac_pk(accA, (v2f){e01.z, e01.w}, cj1);
-                        cmac_pk(accA, (v2f){e23.x, e23.y}, cj2);
-                        cmac_pk(accB, (v2f){e23.z, e23.w}, cj1);
-                        cmac_pk(accB, (v2f){e45.x, e45.y}, cj2);
-                    }
-                    // ---- first bin
-                    v2f newA;
-                    {
-                        float m2 = accA.x * accA.x + accA.y * accA.y;
-                        v2f q = accA;
-                        if (m2 < 1e-30f) {           // too small to square in fp32 (or zero): rescale, so that "|acc| > 0" keeps its meaning
-                            q *= 0x1p60f;
-                            m2 = q.x * q.x + q.y * q.y;
-                        }
-                        const float sc = target_a * __frsqrt_rn(m2);
-                        const bool upd = target_a > thr && m2 > 0.f;
-                        newA = upd ? q * sc : oldA;
-                    }
-                    cmac_pk(accB, wc[1], newA);
-                    cmac_pk(accB, (v2f){e45.z, e45.w}, (v2f){newA.x, -newA.y});   // the image of bin c itself, as the second bin sees it
-                    // ---- second bin
-                    v2f newB;
-                    {
-                        float m2 = accB.x * accB.x + accB.y * accB.y;
-                        v2f q = accB;
-                        if (m2 < 1e-30f) {
-                            q *= 0x1p60f;
-                            m2 = q.x * q.x + q.y * q.y;
-                        }
-                        const float sc = target_b * __frsqrt_rn(m2);
-                        const bool upd = has_b && target_b > thr && m2 > 0.f;
-                        newB = upd ? q * sc : oldB;
-                    }
-                    // unchanged bins are written back as they were; Hermitian images in the pad columns (lwslib.cpp:362-367)
-                    // (a bin without an image stores into a spare slot: no branch)
-                    const int spare = lane - 64, cb = c + 1;
-                    const int ia = (c >= 1 && c <= L) ? li - 2 * c : ((c >= N - L && c <= N - 1) ? li + 2 * (N - c) : spare);
-                    const int ib = (cb <= L) ? li + 1 - 2 * cb : ((cb >= N - L && cb <= N - 1) ? li + 1 + 2 * (N - cb) : spare);
-                    S[li] = make_float2(newA.x, newA.y);
-                    S[has_b ? li + 1 : spare] = make_float2(newB.x, newB.y);
-                    S[ia] = make_float2(newA.x, -newA.y);
-                    S[ib] = make_float2(newB.x, -newB.y);
-                    p2 = newA;
-                    p1 = newB;
-                }
-            }
-            LAB(const unsigned long long lt2 = lab_now();)
-            if (t >= t_done) { s += NSW; setup(); }
-            load_frames(t);
-            LAB(const unsigned long long lt3 = lab_now();)
-            __syncthreads();
-            LAB(const unsigned long long lt4 = lab_now(); lab_acc[0] += lt1 - lt0; lab_acc[1] += lt2 - lt1; lab_acc[2] += lt3 - lt2; lab_acc[3] += lt4 - lt3;)
-        }
-        LAB(if (b == 0 && lane == 0) { for (int i = 0; i < 4; ++i) g_lab[8 + hw_wave * 8 + i] = lab_acc[i]; g_lab[0] = t_end + 1; })
-    }
-    const int first_row = loaded > NW ? loaded - NW : 0;
-    for (int e = first_row; e < loaded; ++e) {
-        const int slot = (e & (NW - 1)) * Np;
-        for (int i = tid; i < Np; i += nthr) gS[(size_t)e * Np + i] = S[slot + i];
-    }
-}
-
-
-// =====================================================================================================================
-// Fourth layout (k_online4; default when it fits).  k_online3 is bound by vector-ALU issue on the SIMD that carries three of
-// its seven tap waves (profiles/r03_pmc_sq_online*.json: 863 vector instructions per step and workgroup, of which 7 x 32 are
-// the register moves of the sliding windows and ~7 x 26 index / predicate arithmetic).  Same roles -- one wave per tap group,
-// one projection wave, tap waves one step ahead -- with the per-step overhead removed:
+// A first build of these roles (the third layout, retired: docs/DESIGN_APPENDIX.md) slid a one-step window through registers
+// and was bound by vector-ALU issue on the SIMD that carried three of its seven tap waves (profiles/r03_pmc_sq_online*.json:
+// 863 vector instructions per step and workgroup, of which 7 x 32 register moves of the sliding windows and ~7 x 26 index /
+// predicate arithmetic).  This one has that per-step overhead removed:
 //   * The step loop is unrolled by two and a neighbour-frame tap wave works on a TWO-step window of 2L + 4 columns whose
 //     register names are fixed: no window slides.  Rows of the LDS ring have an even stride, windows start at even columns:
 //     every window read is an aligned 16-byte cell.  At the end of a pair the next pair's first cells -- values the wave
@@ -827,7 +430,7 @@ __global__ void __launch_bounds__(Online3Waves<Q>::N * 64) k_online3(OnlineArgs 
 //   * tap waves carry no validity predicate: a lane without work computes on clamped addresses and nobody reads its sums.
 //   * 2Q waves, two per SIMD for Q = 4: the centre-frame wave shares the projection wave's SIMD (no idle wave).
 //   * the ring holds NWR frames (run-time, not a power of two), as many as the look-ahead needs: 2048-point frames fit.
-// SERIAL (verification): as in k_online3, the projection wave sums every tap itself in the generic engine's order.
+// SERIAL (verification): the projection wave sums every tap itself, from LDS, in the generic engine's order; same schedule.
 template <int Q> struct Online4Waves {
 #ifndef LWS_ONLINE4_IDLE_WAVE   // (tried: an idle wave on the projection wave's SIMD and the centre wave elsewhere: 57.8 vs 50.9 ms)
     static constexpr int N = 2 * Q;
@@ -1567,10 +1170,11 @@ template <int Q, int L, bool SERIAL> hipError_t launch_q(const OnlineArgs &a, in
     return threads <= 512 ? launch_qt<Q, L, SERIAL, 512>(a, B, threads, lds, s) : launch_qt<Q, L, SERIAL, 1024>(a, B, threads, lds, s);
 }
 
-struct Shape { int NSW, threads, DS; size_t lds; bool ok; };
-
-Shape shape_of(int F, int T, int L, int Q, int Qp, int LA, int n_thr) {
-    Shape sh{0, 0, 0, 0, false};
+// The shape helpers fill an OnlinePlan (lws_online.h) each for its own layout; online_plan picks one.  The environment switches
+// reach them as arguments: online_plan reads them.
+OnlinePlan shape_of(int F, int T, int L, int Q, int Qp, int LA, int n_thr) {
+    OnlinePlan sh{};
+    sh.layout = 2;
     if (Qp != Q || L != 5 || !(Q == 2 || Q == 4 || Q == 8) || LA < 0 || n_thr < 1 || T < 1) return sh;
     const int SKB = 2 * ((L + 3) / 2), SKS = SKB / 2, DS_MIN = ((SKB * (Q - 1) + L + 3) / 2), Np = F + 2 * L, per = n_thr + 1;
     const int NU = (F + 1) / 2;
@@ -1600,39 +1204,14 @@ Shape shape_of(int F, int T, int L, int Q, int Qp, int LA, int n_thr) {
     return sh;
 }
 
-// k_online3: 2Q waves, one lane per (sweep slot, frame position)
-Shape shape3_of(int F, int T, int L, int Q, int Qp, int LA, int n_thr) {
-    Shape sh{0, 0, 0, 0, false};
-    if (Qp != Q || L != 5 || !(Q == 2 || Q == 4 || Q == 8) || LA < 0 || LA > 63 || n_thr < 1 || T < 1) return sh;
-    const int SKB = 2 * ((L + 3) / 2), SKS = SKB / 2, DS_MIN = ((SKB * (Q - 1) + L + 3) / 2), Np = F + 2 * L, per = n_thr + 1;
-    const int NU = (F + 1) / 2;
-    sh.NSW = 64 / (LA + 1);
-    // order-exact lag; the tap waves run a step ahead: 2 DS >= SKB Q + 2; a slot is free again when its sweep is over:
-    // NSW DS >= SKS LA + NU
-    int DS = DS_MIN;
-    if (2 * DS < SKB * Q + 2) DS = (SKB * Q + 3) / 2;
-    const int need = (SKS * LA + NU + sh.NSW - 1) / sh.NSW;
-    if (DS < need) DS = need;
-    sh.DS = DS;
-    sh.threads = (Q == 4 ? 9 : 2 * Q) * 64;
-    const int window = (DS * (per - 1) + NU + 1) / (DS * per + SKS) + LA + Q;
-    if (window > NW) return sh;
-    if (F - 1 < 2 * (L + 3)) return sh;   // frame edges (Hermitian image terms) at least a few steps apart
-    sh.lds = (size_t)2 * (2 * Q - 1) * 64 * 16 + (192 + 64) * 8 + ((size_t)NW * Np + 2) * 8 + (size_t)NW * Np * 4 + 8 + (size_t)3 * Q * Q * (L + 1) * 8 +
-             (size_t)Q * 8 + (size_t)n_thr * 4;
-    if (sh.lds > 160 * 1024) return sh;
-    if ((double)DS * T * per + (double)SKS * T + NU > 1.0e9) return sh;
-    sh.ok = true;
-    return sh;
-}
-
 // k_online4: 2Q waves, one lane per (sweep slot, frame position), even lag, ring of NWR frames with an even row stride
-struct Shape4 { Shape sh; int NWR, NPS; bool big; };
 // big: the kernel's BIG variant (target magnitudes and step table not in LDS)
 // PT > 0: the table-twiddle variant (Q in 3..8, twiddle period PT bins: (PT + 3) x 32 (Q > 4: 64) bytes of LDS more)
-Shape4 shape4_try(int F, int T, int Lu, int Q, int Qp, int LA, int n_thr, bool big, int PT = 0) {
-    Shape4 r{{0, 0, 0, 0, false}, 0, 0, big};
-    Shape &sh = r.sh;
+// serial, lag_plus: LWS_ONLINE_SERIAL_TAPS=1, LWS_ONLINE_LAG_PLUS
+OnlinePlan shape4_try(int F, int T, int Lu, int Q, int Qp, int LA, int n_thr, bool big, int PT, bool serial, int lag_plus) {
+    OnlinePlan r{};
+    r.layout = 4;
+    r.big = big;
     // any stencil half-width up to the kernel's: narrower ones run as L = 5 with zero weights for the taps they do not have
     // (OnlineArgs::Lu) -- the same sums, on a schedule that is order-exact for the wider stencil
     if (Qp != Q || Lu < 1 || Lu > 5 || LA < 0 || LA > 63 || n_thr < 1 || T < 1) return r;
@@ -1640,7 +1219,7 @@ Shape4 shape4_try(int F, int T, int Lu, int Q, int Qp, int LA, int n_thr, bool b
     const int L = 5;
     const int SKB = 2 * ((L + 3) / 2), SKS = SKB / 2, DS_MIN = ((SKB * (Q - 1) + L + 3) / 2), Np = F + 2 * L, per = n_thr + 1;
     const int NU = (F + 1) / 2;
-    sh.NSW = 64 / (LA + 1);
+    r.NSW = 64 / (LA + 1);
     // order-exact lag with the tap waves a step ahead (2 DS >= SKB Q + 2: SKS Q + 1 steps.  One step less is order-exact too, but
     // frame rho+Q-1 of the previous sweep is then SKS steps ahead of a lane, as frame rho-1 is: its tap wave must read two cells
     // after the barrier instead of one and leave its last column to the projection wave -- built and measured in round 4: +12 %
@@ -1649,16 +1228,13 @@ Shape4 shape4_try(int F, int T, int Lu, int Q, int Qp, int LA, int n_thr, bool b
     // (comparison runs: schedules of different lags agree bit for bit).
     int DS = DS_MIN;
     if (2 * DS < SKB * Q + 2) DS = (SKB * Q + 3) / 2;
-    const int need = (SKS * LA + NU + 2 + sh.NSW - 1) / sh.NSW;
+    const int need = (SKS * LA + NU + 2 + r.NSW - 1) / r.NSW;
     if (DS < need) DS = need;
-    {
-        const int plus = lws::env_int("LWS_ONLINE_LAG_PLUS", 0);
-        if (plus > 0 && plus <= 64) DS += plus;
-        const bool odd_ok = (PT > 0 || Q == 4 || Q == 2) && lws::env_int("LWS_ONLINE_SERIAL_TAPS", 0) != 1;   // (the verification variant has no odd build)
-        if (!odd_ok) DS += DS & 1;
-    }
-    sh.DS = DS;
-    sh.threads = Online4Waves<4>::N == 9 && Q == 4 ? 9 * 64 : 2 * Q * 64;
+    if (lag_plus > 0 && lag_plus <= 64) DS += lag_plus;
+    const bool odd_ok = (PT > 0 || Q == 4 || Q == 2) && !serial;   // (the verification variant has no odd build)
+    if (!odd_ok) DS += DS & 1;
+    r.DS = DS;
+    r.threads = Online4Waves<4>::N == 9 && Q == 4 ? 9 * 64 : 2 * Q * 64;
     if (F - 1 < 2 * (L + 3)) return r;
     r.NPS = Np + (Np & 1);
     // (row strides of Np + 2 .. Np + 44 columns measured in round 5, as in round 3: 40.2-40.8 ms against 40.5 -- the window reads'
@@ -1672,38 +1248,33 @@ Shape4 shape4_try(int F, int T, int Lu, int Q, int Qp, int LA, int n_thr, bool b
     // Frames alive at once (see shape_of; frames are brought in three intervals before their first sweep).  Few iterations
     // per frame on a long frame mean many frames in flight: a longer lag between sweeps trades steps for ring space.
     auto window_of = [&](int ds) { return (ds * (per - 1) + NU + 3) / (ds * per + SKS) + LA + Q; };
-    while (window_of(DS) > nwr_max && DS < 16 * sh.DS) DS += 2;
+    while (window_of(DS) > nwr_max && DS < 16 * r.DS) DS += 2;
     if (window_of(DS) > nwr_max) return r;
-    sh.DS = DS;
+    r.DS = DS;
     const int window = window_of(DS);
     r.NWR = window + 1 <= nwr_max ? window + 1 : window;
     // two workgroups fit a CU (half of its LDS each) without the spare ring frame but not with it: drop it -- batches of more
     // spectrograms than CUs then run two chains per CU side by side
     if (r.NWR == window + 1 && lds_of(window + 1) > 80 * 1024 && lds_of(window) <= 80 * 1024) r.NWR = window;
-    sh.lds = lds_of(r.NWR);
+    r.lds = lds_of(r.NWR);
     if ((double)DS * T * per + (double)SKS * T + NU > 1.0e9) return r;
-    sh.ok = true;
+    r.ok = true;
     return r;
 }
-Shape4 shape4_of(int F, int T, int Lu, int Q, int Qp, int LA, int n_thr, int PT = 0) {
-    const bool serial = lws::env_int("LWS_ONLINE_SERIAL_TAPS", 0) == 1;
-    if (PT > 0)   // (no verification variant with table twiddles: generic engine)
-        return serial ? Shape4{{0, 0, 0, 0, false}, 0, 0, false} : shape4_try(F, T, Lu, Q, Qp, LA, n_thr, false, PT);
-    Shape4 r = shape4_try(F, T, Lu, Q, Qp, LA, n_thr, false);
-    if (!r.sh.ok && !serial) r = shape4_try(F, T, Lu, Q, Qp, LA, n_thr, true);
+OnlinePlan shape4_of(int F, int T, int Lu, int Q, int Qp, int LA, int n_thr, int PT, bool serial, int lag_plus) {
+    if (PT > 0 && serial) return OnlinePlan{};   // (no verification variant with table twiddles: generic engine)
+    OnlinePlan r = shape4_try(F, T, Lu, Q, Qp, LA, n_thr, false, PT, serial, lag_plus);
+    if (!r.ok && !serial && PT == 0) r = shape4_try(F, T, Lu, Q, Qp, LA, n_thr, true, 0, serial, lag_plus);
     return r;
 }
 
 // which layout serves a shape: the wave-per-tap-group one unless it needs much more lag between sweeps (few slots: long
-// look-ahead) than the lane-group one; LWS_ONLINE_LAYOUT=2 / 3 forces one (tests)
-int pick_layout(const Shape &s2, const Shape &s3, const Shape &s4) {
-    const int forced = lws::env_int("LWS_ONLINE_LAYOUT", 0);
-    if (forced == 2 && s2.ok) return 2;
-    if (forced == 3 && s3.ok) return 3;
-    if (forced == 4 && s4.ok) return 4;
-    if (s4.ok && (!s2.ok || 2 * s4.DS <= 3 * s2.DS)) return 4;
-    if (s3.ok && (!s2.ok || 2 * s3.DS <= 3 * s2.DS)) return 3;
-    return s2.ok ? 2 : 0;
+// look-ahead) than the lane-group one; forced: LWS_ONLINE_LAYOUT=2 / 4 forces one where it fits (tests).  Neither fits: !ok
+const OnlinePlan &pick_layout(const OnlinePlan &s2, const OnlinePlan &s4, int forced) {
+    if (forced == 2 && s2.ok) return s2;
+    if (forced == 4 && s4.ok) return s4;
+    if (s4.ok && (!s2.ok || 2 * s4.DS <= 3 * s2.DS)) return s4;
+    return s2;
 }
 
 template <int Q, int L, bool SERIAL, bool BIG, bool TWT, bool ODD> hipError_t launch_4p(const OnlineArgs &a, int B, size_t lds, hipStream_t s) {
@@ -1720,29 +1291,41 @@ template <int Q, int L, bool SERIAL, bool BIG = false, bool TWT = false> hipErro
     return launch_4p<Q, L, SERIAL, BIG, TWT, false>(a, B, lds, s);
 }
 
-template <int Q, int L, bool SERIAL> hipError_t launch_3(const OnlineArgs &a, int B, size_t lds, hipStream_t s) {
-    const hipError_t e = lws::allow_dynamic_lds<&k_online3<Q, L, SERIAL>>(160 * 1024);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_online3<Q, L, SERIAL>), dim3(B), dim3(Online3Waves<Q>::N * 64), lds, s, a);
-    return hipGetLastError();
+// the kernel of a plan, Q static: the table variant (Q = 2..8), else (Q = 2, 4, 8) the plan's layout, serial or production, BIG or not
+template <int Q> hipError_t launch_plan(const OnlinePlan &pl, const OnlineArgs &a, int B, hipStream_t s) {
+    if (pl.table) return launch_4<Q, 5, false, false, true>(a, B, pl.lds, s);
+    if constexpr (Q == 2 || Q == 4 || Q == 8) {
+        if (pl.layout == 2) return pl.serial ? launch_q<Q, 5, true>(a, B, pl.threads, pl.lds, s) : launch_q<Q, 5, false>(a, B, pl.threads, pl.lds, s);
+        if (pl.big) return pl.serial ? hipErrorInvalidValue : launch_4<Q, 5, false, true>(a, B, pl.lds, s);
+        return pl.serial ? launch_4<Q, 5, true>(a, B, pl.lds, s) : launch_4<Q, 5, false>(a, B, pl.lds, s);
+    }
+    return hipErrorInvalidValue;
 }
 
 }  // namespace
 
-// tw_P, tw_s: the common twiddle structure of the three tensors (online_twiddle), 0 if they have none.  Tensors of Qp = N rows
-// (general weights) are served through their first Q rows' base weights like summarised ones.
 // (LWS_ONLINE_TABLE_TWIDDLES=1, read when the plan is made: the table variant also where the static one would do -- comparison runs)
 bool online_static_twiddles(int Q, int tw_P, int tw_s) {
     return tw_P == Q && tw_s == 1 && (Q == 2 || Q == 4 || Q == 8) && lws::env_int("LWS_ONLINE_TABLE_TWIDDLES", 0) != 1;
 }
+
+// tw_P, tw_s: the common twiddle structure of the three tensors (online_twiddle), 0 if they have none.  Tensors of Qp = N rows
+// (general weights) are served through their first Q rows' base weights like summarised ones.
 // `table`: the plan's decision (latched when it was made: it uploaded the table or it did not), never re-read from the environment
-bool online_lds_supports(int F, int T, int L, int Q, int Qp, int LA, int n_thr, int update, int tw_P, int tw_s, bool table) {
-    if (update != 2 || tw_P < 1) return false;
+OnlinePlan online_plan(int F, int T, int L, int Q, int Qp, int LA, int n_thr, int update, int tw_P, int tw_s, bool table) {
+    // the switches of this engine, read here and nowhere else
+    const bool serial = lws::env_int("LWS_ONLINE_SERIAL_TAPS", 0) == 1;   // verification only, see k_online
+    const int lag_plus = lws::env_int("LWS_ONLINE_LAG_PLUS", 0), forced = lws::env_int("LWS_ONLINE_LAYOUT", 0);
     const bool eighth_turns = tw_P == Q && tw_s == 1 && (Q == 2 || Q == 4 || Q == 8);
-    if (!table && !eighth_turns) return false;     // (a structure that needs a table the plan does not have, e.g. Q > 8)
-    if (!table)
-        return shape_of(F, T, L, Q, Q, LA, n_thr).ok || shape3_of(F, T, L, Q, Q, LA, n_thr).ok || shape4_of(F, T, L, Q, Q, LA, n_thr).sh.ok;
-    return shape4_of(F, T, L, Q, Q, LA, n_thr, tw_P).sh.ok;
+    // (no structure; or one that needs a table the plan does not have, e.g. Q > 8)
+    if (update != 2 || tw_P < 1 || (!table && !eighth_turns)) return OnlinePlan{};
+    // table twiddles (the plan uploaded one): the fourth layout only
+    const OnlinePlan s2 = table ? OnlinePlan{} : shape_of(F, T, L, Q, Q, LA, n_thr);
+    const OnlinePlan s4 = shape4_of(F, T, L, Q, Q, LA, n_thr, table ? tw_P : 0, serial, lag_plus);
+    OnlinePlan pl = pick_layout(s2, s4, forced);
+    pl.serial = serial;
+    pl.table = table;
+    return pl;
 }
 
 // the table of k_online4<..., TWT>: [P + 3][TQ] float2, TQ = 4 for Q <= 4 else 8, row p: exp(2 pi j p r s / P), r = 0..TQ-1 (host side;
@@ -1757,67 +1340,32 @@ void online_twiddle_table(int P, int s, int Q, float *out) {
         }
 }
 
-hipError_t launch_online_lds(const GenericArgs<float> &g, int B, int tw_P, int tw_s, const float *tw_table_dev, hipStream_t stream) {
+hipError_t launch_online_lds(const OnlinePlan &pl, const GenericArgs<float> &g, int B, int tw_P, const float *tw_table_dev, hipStream_t stream) {
+    if (!pl.ok || pl.table != (tw_table_dev != nullptr)) return hipErrorInvalidValue;
     OnlineArgs a;
     a.state = g.state; a.amp = g.amp; a.thr = g.thr;
     for (int i = 0; i < 3; ++i) a.w[i] = g.w[i].w;
     a.twt = reinterpret_cast<const float2 *>(tw_table_dev); a.PT = tw_P;
-    if (tw_table_dev) {                            // table twiddles (the plan uploaded one): the fourth layout only
-        const Shape4 t4 = shape4_of(g.F, g.T, g.L, g.Q, g.Q, g.LA, g.n_thr, tw_P);
-        if (!t4.sh.ok) return hipErrorInvalidValue;
-        for (int q = 0; q < 8; ++q) a.tw[q] = make_float2(1.f, 0.f);   // (unused)
-        a.F = g.F; a.T = g.T; a.n_thr = g.n_thr; a.LA = g.LA; a.NSW = t4.sh.NSW; a.DS = t4.sh.DS;
-        a.NWR = t4.NWR; a.NPS = t4.NPS; a.Lu = g.L;
-        switch (g.Q) {
-        case 2: return launch_4<2, 5, false, false, true>(a, B, t4.sh.lds, stream);
-        case 3: return launch_4<3, 5, false, false, true>(a, B, t4.sh.lds, stream);
-        case 4: return launch_4<4, 5, false, false, true>(a, B, t4.sh.lds, stream);
-        case 5: return launch_4<5, 5, false, false, true>(a, B, t4.sh.lds, stream);
-        case 6: return launch_4<6, 5, false, false, true>(a, B, t4.sh.lds, stream);
-        case 7: return launch_4<7, 5, false, false, true>(a, B, t4.sh.lds, stream);
-        default: return launch_4<8, 5, false, false, true>(a, B, t4.sh.lds, stream);
-        }
-    }
-    const Shape sh2 = shape_of(g.F, g.T, g.L, g.Q, g.Q, g.LA, g.n_thr), sh3 = shape3_of(g.F, g.T, g.L, g.Q, g.Q, g.LA, g.n_thr);
-    const Shape4 sh4 = shape4_of(g.F, g.T, g.L, g.Q, g.Q, g.LA, g.n_thr);
-    const int layout = pick_layout(sh2, sh3, sh4.sh);
-    if (layout == 0) return hipErrorInvalidValue;
-    const Shape sh = layout == 4 ? sh4.sh : (layout == 3 ? sh3 : sh2);
     for (int q = 0; q < 8; ++q) {
         const double ang = 2.0 * M_PI * q / g.Q;
         // (exact zeros and ones at the quarter turns: the products with them must not pick up rounding)
         double cr = std::cos(ang), sr = std::sin(ang);
         if (std::fabs(cr) < 1e-15) cr = 0;
         if (std::fabs(sr) < 1e-15) sr = 0;
-        a.tw[q] = make_float2((float)cr, (float)sr);
+        a.tw[q] = pl.table ? make_float2(1.f, 0.f) : make_float2((float)cr, (float)sr);   // (table variant: unused)
     }
-    a.F = g.F; a.T = g.T; a.n_thr = g.n_thr; a.LA = g.LA; a.NSW = sh.NSW; a.DS = sh.DS;
-    a.NWR = sh4.NWR; a.NPS = sh4.NPS; a.Lu = g.L;
-    const bool serial = lws::env_int("LWS_ONLINE_SERIAL_TAPS", 0) == 1;   // verification only, see k_online
-    if (layout == 4) {
-        if (sh4.big) {
-            if (serial) return hipErrorInvalidValue;
-            if (g.Q == 4) return launch_4<4, 5, false, true>(a, B, sh.lds, stream);
-            if (g.Q == 2) return launch_4<2, 5, false, true>(a, B, sh.lds, stream);
-            return launch_4<8, 5, false, true>(a, B, sh.lds, stream);
-        }
-        if (g.Q == 4) return serial ? launch_4<4, 5, true>(a, B, sh.lds, stream) : launch_4<4, 5, false>(a, B, sh.lds, stream);
-        if (g.Q == 2) return serial ? launch_4<2, 5, true>(a, B, sh.lds, stream) : launch_4<2, 5, false>(a, B, sh.lds, stream);
-        return serial ? launch_4<8, 5, true>(a, B, sh.lds, stream) : launch_4<8, 5, false>(a, B, sh.lds, stream);
+    a.F = g.F; a.T = g.T; a.n_thr = g.n_thr; a.LA = g.LA; a.NSW = pl.NSW; a.DS = pl.DS;
+    a.NWR = pl.NWR; a.NPS = pl.NPS; a.Lu = g.L;
+    switch (g.Q) {
+    case 2: return launch_plan<2>(pl, a, B, stream);
+    case 3: return launch_plan<3>(pl, a, B, stream);
+    case 4: return launch_plan<4>(pl, a, B, stream);
+    case 5: return launch_plan<5>(pl, a, B, stream);
+    case 6: return launch_plan<6>(pl, a, B, stream);
+    case 7: return launch_plan<7>(pl, a, B, stream);
+    case 8: return launch_plan<8>(pl, a, B, stream);
+    default: return hipErrorInvalidValue;
     }
-    if (layout == 3) {
-        if (g.Q == 4) return serial ? launch_3<4, 5, true>(a, B, sh.lds, stream) : launch_3<4, 5, false>(a, B, sh.lds, stream);
-        if (g.Q == 2) return serial ? launch_3<2, 5, true>(a, B, sh.lds, stream) : launch_3<2, 5, false>(a, B, sh.lds, stream);
-        return serial ? launch_3<8, 5, true>(a, B, sh.lds, stream) : launch_3<8, 5, false>(a, B, sh.lds, stream);
-    }
-    if (serial) {
-        if (g.Q == 4) return launch_q<4, 5, true>(a, B, sh.threads, sh.lds, stream);
-        if (g.Q == 2) return launch_q<2, 5, true>(a, B, sh.threads, sh.lds, stream);
-        return launch_q<8, 5, true>(a, B, sh.threads, sh.lds, stream);
-    }
-    if (g.Q == 4) return launch_q<4, 5, false>(a, B, sh.threads, sh.lds, stream);
-    if (g.Q == 2) return launch_q<2, 5, false>(a, B, sh.threads, sh.lds, stream);
-    return launch_q<8, 5, false>(a, B, sh.threads, sh.lds, stream);
 }
 
 }  // namespace lws

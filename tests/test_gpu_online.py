@@ -38,11 +38,11 @@ def _online(F, W, S, thr, LA, qdiv, **kw):
     (256, 64, 1, 3, 2, 1),         # a single frame
     (512, 128, 40, 9, 2, 1),       # long look-ahead: few sweep slots among the 64 lanes of the wave-per-tap-group layout
 ])
-@pytest.mark.parametrize("layout", ["2", "3", "4"])
+@pytest.mark.parametrize("layout", ["2", "4"])
 def test_serial_variant_is_bit_identical_to_generic(fsize, fshift, T, LA, iters, B, layout, monkeypatch):
-    """The lane layouts of the LDS engine (2: 2Q lanes per bin; 3: one wave per tap group with the projection wave a step behind;
-    4: the same roles on two-step windows of aligned cells, even lag, run-time ring -- the default; LWS_ONLINE_LAYOUT forces one
-    where it fits, else another runs)."""
+    """The lane layouts of the LDS engine (2: 2Q lanes per bin; 4: one wave per tap group with the projection wave a step behind,
+    on two-step windows of aligned cells, run-time ring -- the default; LWS_ONLINE_LAYOUT forces one where it fits, else the
+    other runs)."""
     monkeypatch.setenv("LWS_ONLINE_LAYOUT", layout)
     rng = np.random.default_rng(fsize + T)
     p = lws_amd.lws(fsize, fshift, mode="music")
@@ -70,6 +70,8 @@ def test_serial_variant_is_bit_identical_to_generic(fsize, fshift, T, LA, iters,
 @pytest.mark.parametrize("LA", [0, 1, 3, 5])
 @pytest.mark.parametrize("layout", ["2", "3", "4"])
 def test_small_shapes_vs_oracle(tag, T, LA, layout, oracle, monkeypatch):
+    """Each layout forced, and "3" -- the number of the retired third layout, now a value like any other that names no layout:
+    nothing is forced and the default rule picks."""
     monkeypatch.setenv("LWS_ONLINE_LAYOUT", layout)
     h, g = load_golden("helpers.npz"), load_golden("wrappers.npz")
     W = (h[f"W_{tag}"], h[f"W_ai_{tag}"], h[f"W_af_{tag}"])
@@ -88,7 +90,7 @@ def test_small_shapes_vs_oracle(tag, T, LA, layout, oracle, monkeypatch):
 
 @pytest.mark.parametrize("fsize,fshift,T,LA,iters", [(1024, 256, 10, 3, 2), (1024, 256, 16, 3, 3), (512, 128, 12, 3, 3),
                                                     (1024, 512, 12, 3, 3), (512, 64, 10, 2, 2)])
-@pytest.mark.parametrize("layout", ["2", "3", "4"])
+@pytest.mark.parametrize("layout", ["2", "4"])
 def test_production_variant_vs_oracle_at_full_frame_sizes(fsize, fshift, T, LA, iters, layout, oracle, monkeypatch):
     """The production tap order (per-lane / per-wave partial sums, windows in registers, the projection wave's late terms)
     against the fp64 oracle at the frame sizes of the BASELINE configs, on runs short enough (a dozen frames, 2-3
@@ -105,6 +107,37 @@ def test_production_variant_vs_oracle_at_full_frame_sizes(fsize, fshift, T, LA, 
     err, scale = np.abs(out - ref), np.mean(np.abs(S))
     assert np.median(err) < 1e-6 * scale and np.linalg.norm(err) < 2e-4 * np.linalg.norm(ref)
     assert np.abs(np.abs(out) - np.abs(ref)).max() < 2e-6 * np.abs(S).max()
+
+
+@pytest.mark.parametrize("fsize,fshift,LA", [(56, 28, 11), (1516, 758, 1)])
+def test_shapes_the_retired_layout_used_to_take(fsize, fshift, LA, oracle, monkeypatch):
+    """The shapes whose route moved when the third layout (one wave per tap group on one-step windows) was retired: its lag
+    sat exactly on the chooser's 2 DS <= 3 DS(layout 2) boundary (12 against 8 for Q = 2, 24 against 16 for Q = 4) and the fourth
+    layout's, one step longer, falls over it, so they now run on the lane-group layout.  tools/online_layout_model.py lists
+    them; these are the one with the shortest and the one with the longest frame at three iterations.  By default, no layout
+    forced: serial-taps variant bit-identical to the generic engine, production variant the same magnitudes and the fp64
+    oracle's values to the bars of test_small_shapes_vs_oracle."""
+    T, iters = 12, 3
+    rng = np.random.default_rng(fsize + LA)
+    p = lws_amd.lws(fsize, fshift, mode="music")
+    F = fsize // 2 + 1
+    S = rng.standard_normal((T, F)) + 1j * rng.standard_normal((T, F))
+    thr = lws_amd.get_thresholds(iters, 1.0, 0.1, 1)
+    W = (p.W, p.W_ai, p.W_af)
+    gen, name = _online(F, W, S, thr, LA, fsize / fshift, force_generic=True)
+    assert name == "generic_fp32"
+    monkeypatch.setenv("LWS_ONLINE_SERIAL_TAPS", "1")
+    ser, name = _online(F, W, S, thr, LA, fsize / fshift)
+    assert name == "online_lds_fp32"
+    assert np.array_equal(ser, gen)
+    monkeypatch.delenv("LWS_ONLINE_SERIAL_TAPS")
+    prod, name = _online(F, W, S, thr, LA, fsize / fshift)
+    assert name == "online_lds_fp32"
+    assert np.abs(np.abs(prod) - np.abs(gen)).max() < 2e-6 * np.abs(S).max()
+    ref = oracle.online_lws(S, *W, thr, LA, fshift)
+    err, scale = np.abs(prod - ref), np.mean(np.abs(S))
+    print("median err / scale %.3e, rel-L2 %.3e" % (np.median(err) / scale, np.linalg.norm(err) / np.linalg.norm(ref)))
+    assert np.median(err) < 2e-6 * scale and np.linalg.norm(err) < 5e-3 * np.linalg.norm(ref)
 
 
 @pytest.mark.parametrize("fsize,fshift,L,T,LA,iters,B", [(1024, 256, 3, 60, 3, 6, 2), (512, 128, 1, 40, 3, 4, 1),
@@ -196,8 +229,8 @@ def test_more_than_eight_frames_per_row_go_to_the_team_engine(monkeypatch):
 @pytest.mark.parametrize("iters,T", [(1, 30), (3, 14), (10, 8)])
 def test_wide_frames_stay_on_the_lds_engine(iters, T, oracle, monkeypatch):
     """2048-point frames (BASELINE config 5's frame size, lws(2048,512, mode='music')): the run-time ring of the fourth layout
-    holds them -- with one iteration per frame by lengthening the lag between sweeps -- where the 16-frame rings of the other
-    layouts sent them to the generic engine.  Serial-taps variant bit-identical to the generic engine, production variant
+    holds them -- with one iteration per frame by lengthening the lag between sweeps -- where the 16-frame ring of the other
+    layout sends them to the generic engine.  Serial-taps variant bit-identical to the generic engine, production variant
     against the fp64 oracle (short runs: values)."""
     rng = np.random.default_rng(iters)
     p = lws_amd.lws(2048, 512, mode="music")
