@@ -208,6 +208,20 @@ int lws_consistency_dev(int device, const void *S_dev, int B, int M, int N, int 
 int lws_griffin_lim_dev(int device, void *C_dev, const float *A_dev, int B, int M, int N, int fshift, const double *awin,
                         const double *swin, int perfectrec, int iters, double alpha, double *trace, void *stream);
 
+/* MISI (Multiple Input Spectrogram Inversion, Gunawan & Sen 2010), device resident (lws_gla.hip; the reference has no counterpart):
+ * Griffin-Lim on the K sources of each of B mixtures, coupled through the known mixture y.  Iteration i = 1..iters computes
+ * x_k = istft(c_k), e = y - sum_k x_k (k ascending), X_k = stft(x_k + e / K), c_k = A X_k / |X_k| (A + 0j where |X_k| == 0); no
+ * momentum.  C_dev[B][K][M][N/2+1] (complex64) holds c_0 on entry and c_iters -- whose magnitudes are A -- on return; iters == 0
+ * leaves it unchanged.  A_dev[B][K][M][N/2+1] (float32) are the target magnitudes, NULL: |c_0|.  y_dev[B][len] (float32), len =
+ * lws_istft_length(M, ...), are the mixtures.  x_dev: NULL, or [B][K][len] (float32) for the signals of the returned spectrograms
+ * with their own residual shared out, s_k = istft(c_k) + (y - sum_j istft(c_j)) / K, which sum to y (also with iters == 0).
+ * trace: NULL (the call only enqueues work on `stream`), or HOST, iters*B*2 doubles (synchronises): trace[(i-1)*B*2 + 2b] =
+ * sum y^2 and [.. + 1] = sum e^2 of the iterate entering step i (fp64 sums; 10 log10 of their ratio is the mixture consistency
+ * in dB).  K < 1, iters < 0, a null C_dev / y_dev / window, or an M the round trip stft(istft(.)) does not keep (too few frames
+ * for perfectrec): LWS_ERR_INVALID; frame sizes outside the device transform: as lws_griffin_lim_dev. */
+int lws_misi_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, int B, int K, int M, int N, int fshift,
+                 const double *awin, const double *swin, int perfectrec, int iters, float *x_dev, double *trace, void *stream);
+
 /* ---- host-side construction of windows, weights and schedules (lws.pyx:10-40,160-206), fp64, no device work: what a
  *      caller without numpy needs to build a plan.  Complex outputs are interleaved (re, im) doubles. ---- */
 

@@ -30,7 +30,7 @@ EXPORTS = (
     "lws_batch_lws", "lws_nofuture_lws", "lws_online_lws", "lws_run_lws", "lws_batch_lws_dev",
     "lws_nofuture_lws_dev", "lws_online_lws_dev", "lws_residual_dev", "lws_last_kernel_time",
     "lws_last_kernel_name", "lws_generic_stage", "lws_stft_frames", "lws_istft_length", "lws_stft_dev", "lws_istft_dev", "lws_stft_zp_dev",
-    "lws_consistency_dev", "lws_griffin_lim_dev", "lws_hann", "lws_synthwin", "lws_weights_shape", "lws_create_weights",
+    "lws_consistency_dev", "lws_griffin_lim_dev", "lws_misi_dev", "lws_hann", "lws_synthwin", "lws_weights_shape", "lws_create_weights",
     "lws_build_asymmetric_windows", "lws_get_thresholds", "lws_plan_create_from_windows", "lws_stream_copy",
     "lws_run_lws_dev", "lws_plan_reserve", "lws_residual", "lws_residual_allreduce_dev", "lws_weights_structure", "lws_multi_plan_create", "lws_multi_plan_destroy",
     "lws_multi_plan_shards", "lws_multi_batch_lws", "lws_multi_run_lws", "lws_multi_residual",
@@ -103,6 +103,7 @@ def load():
     lib.lws_consistency_dev.argtypes = [ip, vp, ip, ip, ip, ip, vp, vp, ip, vp, vp]
     dp = C.c_double
     lib.lws_griffin_lim_dev.argtypes = [ip, vp, vp, ip, ip, ip, ip, vp, vp, ip, ip, dp, vp, vp]
+    lib.lws_misi_dev.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, vp, vp, vp]
     lib.lws_hann.argtypes = [ip, ip, ip, vp]
     lib.lws_synthwin.argtypes = [vp, ip, ip, vp, vp]
     lib.lws_weights_shape.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
@@ -472,4 +473,20 @@ def griffin_lim_dev(C_ptr, A_ptr, B, frames, fsize, fshift, awin, swin, perfectr
     check(load().lws_griffin_lim_dev(int(device), C_ptr, A_ptr, int(B), int(frames), int(fsize), int(fshift), a.ctypes.data,
                                      w.ctypes.data, int(bool(perfectrec)), int(iterations), float(alpha),
                                      trace.ctypes.data if (want_trace and trace.size) else None, stream))
+    return trace
+
+
+def misi_dev(C_ptr, A_ptr, y_ptr, B, K, frames, fsize, fshift, awin, swin, perfectrec, iterations, x_ptr=None, want_trace=False,
+             device=0, stream=None):
+    """MISI iterations in place on C_ptr (device complex64 [B][K][frames][fsize//2+1]); A_ptr: device float32 target magnitudes
+    or None (|c_0|); y_ptr: device float32 mixtures [B][istft_length(...)]; x_ptr: None or device float32 [B][K][length] for the
+    signals.  want_trace: returns the host array (iterations, B, 2) of [sum y^2, sum e^2] of the iterate entering each step
+    (synchronises); otherwise the call only enqueues and returns None."""
+    a, w = _win(awin), _win(swin)
+    if a.shape != (int(fsize),) or w.shape != (int(fsize),):
+        raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
+    trace = np.empty((max(int(iterations), 0), int(B), 2), dtype=np.float64) if want_trace else None
+    check(load().lws_misi_dev(int(device), C_ptr, A_ptr, y_ptr, int(B), int(K), int(frames), int(fsize), int(fshift), a.ctypes.data,
+                              w.ctypes.data, int(bool(perfectrec)), int(iterations), x_ptr,
+                              trace.ctypes.data if (want_trace and trace.size) else None, stream))
     return trace

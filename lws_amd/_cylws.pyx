@@ -273,6 +273,17 @@ def lws_griffin_lim_dev(int device, C_dev, A_dev, int B, int M, int N, int fshif
     return rc
 
 
+def lws_misi_dev(int device, C_dev, A_dev, y_dev, int B, int K, int M, int N, int fshift, awin, swin, int perfectrec, int iters,
+                 x_dev, trace, stream):
+    cdef uintptr_t cd = _addr(C_dev), ad = _addr(A_dev), yd = _addr(y_dev), a = _addr(awin), w = _addr(swin), xd = _addr(x_dev)
+    cdef uintptr_t t = _addr(trace), st = _addr(stream)
+    cdef int rc
+    with nogil:
+        rc = c.lws_misi_dev(device, <void *>cd, <const float *>ad, <const float *>yd, B, K, M, N, fshift, <const double *>a,
+                            <const double *>w, perfectrec, iters, <float *>xd, <double *>t, <void *>st)
+    return rc
+
+
 def lws_hann(int n, int symmetric, int use_offset, out):
     cdef uintptr_t o = _addr(out)
     return c.lws_hann(n, symmetric, use_offset, <double *>o)

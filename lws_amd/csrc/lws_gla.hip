@@ -143,10 +143,92 @@ __global__ void k_gla_sum_rows(const double *rows, double *out, int M, int B) { 
     out[2 * b + 1] = e;
 }
 
+// ---- MISI: K sources coupled through their mixture y.  Per iteration: k_gla_inverse over the B K spectrograms, k_misi_residual,
+// k_misi_forward.  The timeline is the uncut one of gla_sample (length Tfull = hop (M - 1) + N); y[b][j] sits at t = zero_lo + j.
+
+// delta[b][t] = (y - sum_k OLA_k(t)) / K, k ascending (each OLA_k gathered in ascending frame order: a fixed order, no atomics),
+// zero in the perfectrec cuts.  sig: [B][K][Tfull], the K overlap-added signals, which the forward load and k_misi_signals read
+// back instead of gathering them again.  TRACE: part[b][blockIdx.x] = fp64 (sum y^2, sum e^2) of this block's samples, for k_gla_sum_rows.
+template <bool TRACE>
+__global__ void __launch_bounds__(256) k_misi_residual(const float *frames, const float *y, float *delta, float *sig, double *part,
+                                                       int K, int M, int N, int hop, int zero_lo, int zero_hi) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    const int Tfull = hop * (M - 1) + N, t_end = Tfull - zero_hi;
+    double y2 = 0, e2 = 0;
+    if (t < Tfull) {
+        float d = 0.f;
+        const bool kept = t >= zero_lo && t < t_end;
+        float acc = 0.f;
+        for (int k = 0; k < K; ++k) {
+            const size_t bk = (size_t)b * K + k;
+            const float x = gla_sample(frames + bk * M * N, t, M, N, hop, zero_lo, t_end);
+            sig[bk * Tfull + t] = x;
+            acc = k ? acc + x : x;
+        }
+        if (kept) {
+            const float yv = y[(size_t)b * (t_end - zero_lo) + (t - zero_lo)], e = yv - acc;
+            d = e / (float)K;
+            if (TRACE) { y2 = (double)yv * yv; e2 = (double)e * e; }
+        }
+        delta[(size_t)b * Tfull + t] = d;
+    }
+    if constexpr (TRACE) {
+        __shared__ double red[2][256];
+        const int tid = threadIdx.x;
+        red[0][tid] = y2; red[1][tid] = e2;
+        __syncthreads();
+        for (int s2 = blockDim.x / 2; s2 > 0; s2 >>= 1) {
+            if (tid < s2) { red[0][tid] += red[0][tid + s2]; red[1][tid] += red[1][tid + s2]; }
+            __syncthreads();
+        }
+        if (tid < 2) part[((size_t)b * gridDim.x + blockIdx.x) * 2 + tid] = red[tid][0];
+    }
+}
+
+// k_gla_forward for source blockIdx.y % K of mixture blockIdx.y / K with the shared mixture error in its load,
+// (OLA_k(t) + delta[t]) awin[n], OLA_k as k_misi_residual stored it; the epilogue is the magnitude projection alone (gla_bin without
+// momentum or sums).
+__global__ void __launch_bounds__(FFT_THREADS) k_misi_forward(const float *sig, const float *delta, const float *awin, float2 *C,
+                                                               const float *A, int K, int M, int N, int odd, int log2e, int hop) {
+    extern __shared__ float2 lds[];
+    const int m0 = 2 * blockIdx.x, bk = blockIdx.y, F = N / 2 + 1;
+    const bool two = m0 + 1 < M;
+    const int Tfull = hop * (M - 1) + N;
+    const float *sg = sig + (size_t)bk * Tfull, *dl = delta + (size_t)(bk / K) * Tfull;
+    float2 *xa = lds, *ya = lds + N;
+    for (int n = threadIdx.x; n < N; n += blockDim.x) {
+        const float w = awin[n];
+        const int t0 = m0 * hop + n, t1 = t0 + hop;
+        const float re = (sg[t0] + dl[t0]) * w;
+        const float im = two ? (sg[t1] + dl[t1]) * w : 0.f;
+        xa[n] = make_float2(re, im);
+    }
+    __syncthreads();
+    const float2 *r = fft_lds(xa, ya, N, odd, log2e, -1.0f);
+    const size_t base = ((size_t)bk * M + m0) * F;
+    const GlaStep st{0.f, 0};
+    double p = 0, e = 0;
+    for (int k = threadIdx.x; k < F; k += blockDim.x) {
+        const float2 zk = r[k], zn = r[k == 0 ? 0 : N - k];
+        gla_bin<false>(make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)), C, A, nullptr, base + k, st, p, e);
+        if (two) gla_bin<false>(make_float2(0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)), C, A, nullptr, base + F + k, st, p, e);
+    }
+}
+
+// s_k = OLA_k + delta on the kept samples: x[b][k][len], len = Tfull - zero_lo - zero_hi
+__global__ void __launch_bounds__(256) k_misi_signals(const float *sig, const float *delta, float *x, int K, int Tfull, int zero_lo,
+                                                      int len) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x, bk = blockIdx.y;
+    if (j >= len) return;
+    const int t = zero_lo + j;
+    x[(size_t)bk * len + j] = sig[(size_t)bk * Tfull + t] + delta[(size_t)(bk / K) * Tfull + t];
+}
+
 // Windows and scratch of the iteration, one set per device, serialised on the device by the event scheme of lws_stft.hip.  The
 // windows stay on the device between calls: a call with the windows of the previous one uploads nothing.
 struct GlaCtx {
     Scratch frames, t, a, rows, trace, win_a, win_s;
+    Scratch delta, sig;                   // MISI: the shared mixture error, and the K overlap-added signals
     std::vector<double> host_a, host_s;   // what win_a / win_s hold
     hipEvent_t last = nullptr;
     bool busy = false;
@@ -183,6 +265,7 @@ int allow_lds_all() {
     STFT_TRY(lws::allow_dynamic_lds<&k_gla_inverse>(bytes));
     STFT_TRY(lws::allow_dynamic_lds<&k_gla_forward<true>>(bytes));
     STFT_TRY(lws::allow_dynamic_lds<&k_gla_forward<false>>(bytes));
+    STFT_TRY(lws::allow_dynamic_lds<&k_misi_forward>(bytes));
     return LWS_OK;
 }
 
@@ -242,6 +325,76 @@ extern "C" int lws_griffin_lim_dev(int device, void *C_dev, const float *A_dev, 
     }
     STFT_TRY(hipGetLastError());
     if (trace) {
+        STFT_TRY(hipMemcpyAsync(trace, c.trace.p, (size_t)iters * B * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+        STFT_TRY(hipStreamSynchronize(s));
+    }
+    return ctx_leave(c, s);
+}
+
+extern "C" int lws_misi_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, int B, int K, int M, int N, int fshift,
+                            const double *awin, const double *swin, int perfectrec, int iters, float *x_dev, double *trace,
+                            void *stream) {
+    int rc = check_shape(device, B, M, N, fshift);
+    if (rc) return rc;
+    if (K < 1) return lws::set_error(LWS_ERR_INVALID, "%d sources", K);
+    if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
+    if (!C_dev || !y_dev || !awin || !swin) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    if ((long long)B * K > 65535) return lws::set_error(LWS_ERR_UNSUPPORTED, "%d x %d spectrograms in one call (at most 65535)", B, K);
+    const int len = lws_istft_length(M, N, fshift, perfectrec);
+    if (len < 1) return lws::set_error(LWS_ERR_INVALID, "%d frames leave no samples", M);
+    if (iters > 0 && lws_stft_frames(len, N, fshift, perfectrec) != M)
+        return lws::set_error(LWS_ERR_INVALID, "the round trip does not keep %d frames (too few frames for perfectrec)", M);
+    if (B == 0 || (iters == 0 && !x_dev)) return LWS_OK;
+    STFT_TRY(hipSetDevice(device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> lk(g_mu);
+    GlaCtx &c = g_ctx[device];
+    if ((rc = ctx_enter(c, s))) return rc;
+    if ((rc = allow_lds_all())) return rc;
+    if ((rc = upload_window(c.win_a, c.host_a, awin, N, s))) return rc;
+    if ((rc = upload_window(c.win_s, c.host_s, swin, N, s))) return rc;
+    const int F = N / 2 + 1, BK = B * K, Tfull = fshift * (M - 1) + N, nblk = (Tfull + 255) / 256;
+    const size_t bins = (size_t)BK * M * F;
+    const bool want_trace = trace && iters > 0;
+    if ((rc = c.frames.ensure((size_t)BK * M * N * sizeof(float)))) return rc;
+    if ((rc = c.delta.ensure((size_t)B * Tfull * sizeof(float)))) return rc;
+    if ((rc = c.sig.ensure((size_t)BK * Tfull * sizeof(float)))) return rc;
+    if (!A_dev && iters > 0 && (rc = c.a.ensure(bins * sizeof(float)))) return rc;
+    if (want_trace && (rc = c.rows.ensure((size_t)B * nblk * 2 * sizeof(double)))) return rc;
+    if (want_trace && (rc = c.trace.ensure((size_t)iters * B * 2 * sizeof(double)))) return rc;
+    float2 *C = static_cast<float2 *>(C_dev);
+    float *frames = static_cast<float *>(c.frames.p), *delta = static_cast<float *>(c.delta.p);
+    float *sig = static_cast<float *>(c.sig.p);
+    double *rows = static_cast<double *>(c.rows.p);
+    const float *wa = static_cast<const float *>(c.win_a.p), *ws = static_cast<const float *>(c.win_s.p);
+    if (!A_dev && iters > 0) {
+        hipLaunchKernelGGL(k_gla_abs, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, s, C, static_cast<float *>(c.a.p), bins);
+        A_dev = static_cast<const float *>(c.a.p);
+    }
+    const Factors fc = factor(N);
+    const dim3 grid((M + 1) / 2, BK), rgrid(nblk, B);
+    const size_t lds = fft_lds_bytes(N);
+    const int zero_lo = perfectrec ? prepad(N, fshift) : 0, zero_hi = perfectrec ? N - fshift : 0;   // as in lws_griffin_lim_dev
+    for (int i = 1; i <= iters; ++i) {
+        hipLaunchKernelGGL(k_gla_inverse, grid, dim3(FFT_THREADS), lds, s, C, frames, ws, M, N, fc.odd, fc.log2e);
+        if (want_trace) {
+            hipLaunchKernelGGL(k_misi_residual<true>, rgrid, dim3(256), 0, s, frames, y_dev, delta, sig, rows, K, M, N, fshift, zero_lo, zero_hi);
+            hipLaunchKernelGGL(k_gla_sum_rows, dim3((B + 63) / 64), dim3(64), 0, s, rows,
+                               static_cast<double *>(c.trace.p) + (size_t)(i - 1) * B * 2, nblk, B);
+        } else {
+            hipLaunchKernelGGL(k_misi_residual<false>, rgrid, dim3(256), 0, s, frames, y_dev, delta, sig, static_cast<double *>(nullptr), K,
+                               M, N, fshift, zero_lo, zero_hi);
+        }
+        hipLaunchKernelGGL(k_misi_forward, grid, dim3(FFT_THREADS), lds, s, sig, delta, wa, C, A_dev, K, M, N, fc.odd, fc.log2e, fshift);
+    }
+    if (x_dev) {   // the signals of the final iterate, with their own residual shared out
+        hipLaunchKernelGGL(k_gla_inverse, grid, dim3(FFT_THREADS), lds, s, C, frames, ws, M, N, fc.odd, fc.log2e);
+        hipLaunchKernelGGL(k_misi_residual<false>, rgrid, dim3(256), 0, s, frames, y_dev, delta, sig, static_cast<double *>(nullptr), K,
+                           M, N, fshift, zero_lo, zero_hi);
+        hipLaunchKernelGGL(k_misi_signals, dim3((len + 255) / 256, BK), dim3(256), 0, s, sig, delta, x_dev, K, Tfull, zero_lo, len);
+    }
+    STFT_TRY(hipGetLastError());
+    if (want_trace) {
         STFT_TRY(hipMemcpyAsync(trace, c.trace.p, (size_t)iters * B * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
         STFT_TRY(hipStreamSynchronize(s));
     }

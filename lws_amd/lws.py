@@ -259,6 +259,122 @@ def griffin_lim_dev(S, fsize, fshift, awin, swin, iterations, alpha=0.99, magnit
     return out, (db[:, 0] if single else db)
 
 
+# --------------------------------------------------------------------------------------------
+# MISI (Gunawan & Sen 2010; no counterpart in the reference): Griffin-Lim on K sources coupled through their known mixture
+# --------------------------------------------------------------------------------------------
+def _misi_returns(out, db, sig, return_trace, return_signals):
+    res = (out,) + ((db,) if return_trace else ()) + ((sig,) if return_signals else ())
+    return res[0] if len(res) == 1 else res
+
+
+def _misi_share(x, y):
+    """The K signals x (K, len) with the mixture error e = y - sum_k x_k (k ascending) shared out equally; also e."""
+    tot = x[0].copy()
+    for k in range(1, x.shape[0]):
+        tot += x[k]
+    e = y - tot
+    return x + e / x.shape[0], e
+
+
+def misi(S, mixture, fsize, fshift, awin, swin, iterations, magnitudes=None, perfectrec=False, return_trace=False,
+         return_signals=False, _perturb=None):
+    """Multiple Input Spectrogram Inversion from the starts S, (K, T, F) or a stack (B, K, T, F), and the real mixture(s)
+    `mixture`, (len,) / (B, len) with len that of istft(S[k]), in fp64 on the host: the definition the device form is held to.
+    Step i = 1..iterations is x_k = istft(c_k), e = y - sum_k x_k (k ascending), X_k = stft(x_k + e / K), c_k = A_k X_k / |X_k|
+    (A_k + 0j where |X_k| == 0); no momentum.  Returns c after the last step (its magnitudes are A = `magnitudes`, by default
+    |S|); zero iterations return S.  return_trace: also 10 log10(sum y^2 / sum e^2) of the iterate entering each step, shape
+    (iterations,) / (iterations, B).  return_signals: also s_k = istft(out_k) + (y - sum_j istft(out_j)) / K, (K, len) /
+    (B, K, len), which sum to the mixture.  Order of the extras: trace, signals.  (_perturb(i, b, k, X) -> X: replaces each
+    projection; the error model of the tests.)"""
+    n, _ = _gla_args(iterations, 0.0)
+    S = np.asarray(S)
+    if S.ndim not in (3, 4):
+        raise ValueError('expected (K, T, F) spectrograms of the sources or a (B, K, T, F) stack')
+    A = np.abs(S) if magnitudes is None else np.asarray(magnitudes, dtype=np.float64)
+    if A.shape != S.shape:
+        raise ValueError('magnitudes of shape %s for spectrograms of shape %s' % (A.shape, S.shape))
+    y = np.asarray(mixture, dtype=np.float64)
+    S4, A4, y2 = (S[None], A[None], y[None]) if S.ndim == 3 else (S, A, y)
+    B, K, T, F = S4.shape
+    if K < 1:
+        raise ValueError('no sources')
+    length = len(istft(np.zeros((T, F), complex), fshift, swin, perfectrec=perfectrec))
+    if y.ndim != S.ndim - 2 or y2.shape != (B, length):
+        raise ValueError('mixture of shape %s for %s spectrograms of %d frames: expected %s' %
+                         (y.shape, S.shape[:-2], T, S.shape[:-3] + (length,)))
+    out = S4.astype(np.complex128)
+    db = np.empty((n, B))
+    sig = np.empty((B, K, length))
+    for b in range(B):
+        c = out[b]
+        for i in range(1, n + 1):
+            x, e = _misi_share(np.stack([istft(c[k], fshift, swin, perfectrec=perfectrec) for k in range(K)]), y2[b])
+            with np.errstate(divide='ignore', invalid='ignore'):
+                db[i - 1, b] = 10 * np.log10(np.sum(y2[b] ** 2) / np.sum(e ** 2))
+            for k in range(K):
+                X = stft(x[k], fsize, fshift, awin, perfectrec=perfectrec)
+                if X.shape != c[k].shape:
+                    raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, X.shape[0]))
+                if _perturb is not None:
+                    X = _perturb(i, b, k, X)
+                mag = np.abs(X)
+                c[k] = np.where(mag > 0, A4[b, k] * X / np.where(mag > 0, mag, 1.0), A4[b, k] + 0j)
+        if return_signals:
+            sig[b] = _misi_share(np.stack([istft(c[k], fshift, swin, perfectrec=perfectrec) for k in range(K)]), y2[b])[0]
+    if n == 0:
+        out = S4
+    if S.ndim == 3:
+        out, db, sig = out[0], db[:, 0], sig[0]
+    return _misi_returns(out, db, sig, return_trace, return_signals)
+
+
+def misi_dev(S, mixture, fsize, fshift, awin, swin, iterations, magnitudes=None, perfectrec=False, return_trace=False,
+             return_signals=False, device=0):
+    """misi() above on the device (lws_gla.hip: float32; per iteration one inverse launch over all sources, one residual launch
+    and one forward launch whose load adds the shared mixture error and whose epilogue is the magnitude projection): S (K, T, F)
+    or (B, K, T, F) and mixture (len,) / (B, len), numpy or torch; returns a new complex64 torch tensor (S itself is not
+    modified), with return_trace also the dB values as a numpy array, with return_signals also the signals as a float32 torch
+    tensor (in that order).  Runs on the caller's current torch stream; without return_trace the call only enqueues work."""
+    import torch
+    n, _ = _gla_args(iterations, 0.0)
+    t = _dev_tensor(S, torch.complex64, device)
+    if t.dim() not in (3, 4):
+        raise ValueError('expected (K, T, F) spectrograms of the sources or a (B, K, T, F) stack')
+    single = t.dim() == 3
+    if isinstance(S, torch.Tensor) and t.data_ptr() == S.data_ptr():
+        t = t.clone()                              # the iteration is in place: never on the caller's storage
+    t4 = t[None] if single else t
+    B, K, T, F = t4.shape
+    if K < 1:
+        raise ValueError('no sources')
+    if F != fsize // 2 + 1:
+        raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
+    A = None
+    if magnitudes is not None:
+        A = _dev_tensor(magnitudes, torch.float32, device)
+        if A.shape != t.shape:
+            raise ValueError('magnitudes of shape %s for spectrograms of shape %s' % (tuple(A.shape), tuple(t.shape)))
+    y = _dev_tensor(mixture, torch.float32, device)
+    length = _capi.istft_length(T, fsize, fshift, perfectrec)
+    if y.dim() != t.dim() - 2 or tuple(y.shape)[-1:] != (length,) or (not single and y.shape[0] != B):
+        raise ValueError('mixture of shape %s for %s spectrograms of %d frames: expected %s' %
+                         (tuple(y.shape), tuple(t.shape[:-2]), T, tuple(t.shape[:-3]) + (length,)))
+    if n > 0 and _capi.stft_frames(length, fsize, fshift, perfectrec) != T:
+        raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' %
+                         (T, _capi.stft_frames(length, fsize, fshift, perfectrec)))
+    sig = torch.empty((B, K, length), dtype=torch.float32, device=t4.device) if return_signals else None
+    trace = _capi.misi_dev(t4.data_ptr(), None if A is None else A.data_ptr(), y.data_ptr(), B, K, T, fsize, fshift, awin, swin,
+                           perfectrec, n, None if sig is None else sig.data_ptr(), want_trace=return_trace, device=int(device),
+                           stream=torch.cuda.current_stream(t4.device).cuda_stream)
+    db = None
+    if return_trace:
+        with np.errstate(divide='ignore', invalid='ignore'):
+            db = 10 * np.log10(trace[..., 0] / trace[..., 1])
+    if single:
+        t4, db, sig = t4[0], (None if db is None else db[:, 0]), (None if sig is None else sig[0])
+    return _misi_returns(t4, db, sig, return_trace, return_signals)
+
+
 def extspec(S, L, Q):
     """Extended spectrogram: L Hermitian columns each side, Q-1 repeated frames each end (lws.pyx:146-157)."""
     S = np.asarray(S)
@@ -594,6 +710,17 @@ class lws(object):
         """Device form: a new complex64 torch tensor, see the module's griffin_lim_dev."""
         return griffin_lim_dev(S, self.fsize, self.fshift, self.awin, self.swin, iterations, alpha=alpha, magnitudes=magnitudes,
                                perfectrec=self.perfectrec, return_trace=return_trace, device=self.device)
+
+    # ---- MISI: the phases of K sources under the constraint that they add up to a known mixture ----
+    def misi(self, S, mixture, iterations, magnitudes=None, return_trace=False, return_signals=False):
+        """Host fp64 form with this object's windows and perfectrec: see the module's misi."""
+        return misi(S, mixture, self.fsize, self.fshift, self.awin, self.swin, iterations, magnitudes=magnitudes,
+                    perfectrec=self.perfectrec, return_trace=return_trace, return_signals=return_signals)
+
+    def misi_dev(self, S, mixture, iterations, magnitudes=None, return_trace=False, return_signals=False):
+        """Device form: a new complex64 torch tensor, see the module's misi_dev."""
+        return misi_dev(S, mixture, self.fsize, self.fshift, self.awin, self.swin, iterations, magnitudes=magnitudes,
+                        perfectrec=self.perfectrec, return_trace=return_trace, return_signals=return_signals, device=self.device)
 
     def nofuture_lws(self, S, iterations=None, thresholds=None):
         if iterations is None:
