@@ -175,14 +175,21 @@ const char *lws_generic_stage(lws_plan *plan);
  *      -- an odd factor times a power of two: radix-2 stages and one stage of odd-point DFTs; fftsize == fsize unless said otherwise).  Windows are host arrays of N doubles, already normalised the way the caller
  *      wants them (class lws: awin and synthwin(awin, fshift)).  perfectrec as in lws.pyx:55-67,130-137. ---- */
 
-/* Frames stft() produces for a signal of `len` samples (lws.pyx:55-76); < 1 if the signal is too short. */
+/* Frames stft() produces for a signal of `len` samples (lws.pyx:55-76): never negative; 0 without perfectrec for a signal that is
+ * shorter than one frame even when padded to the frame-shift grid (the host returns an empty spectrogram); -1 for len < 0,
+ * N < 1 or fshift < 1. */
 int lws_stft_frames(int len, int N, int fshift, int perfectrec);
-/* Samples istft() returns for M frames (lws.pyx:121,130-137). */
+/* Samples istft() returns for M frames (lws.pyx:121,130-137): never negative.  With perfectrec it is what the slice
+ * signal[prepad : fshift - N] keeps of fshift (M - 1) + N samples -- nothing of fewer than about N / fshift frames, and nothing
+ * of any number of frames with fshift == N (an end index of 0 is the start of the array). */
 int lws_istft_length(int M, int N, int fshift, int perfectrec);
-/* stft (lws.pyx:43-90) of B signals x_dev[B][len] (float32) into S_dev[B][M][N/2+1] (complex64), M = lws_stft_frames(). */
+/* stft (lws.pyx:43-90) of B signals x_dev[B][len] (float32) into S_dev[B][M][N/2+1] (complex64), M = lws_stft_frames().
+ * M == 0: LWS_OK, nothing is enqueued and neither pointer is used.  (The same holds for lws_stft_zp_dev.) */
 int lws_stft_dev(int device, const float *x_dev, int B, int len, int N, int fshift, const double *awin,
                  int perfectrec, void *S_dev, void *stream);
-/* istft (lws.pyx:93-137) of S_dev[B][M][N/2+1] (complex64) into x_dev[B][lws_istft_length()] (float32). */
+/* istft (lws.pyx:93-137) of S_dev[B][M][N/2+1] (complex64) into x_dev[B][lws_istft_length()] (float32).  M < 1: LWS_ERR_INVALID;
+ * lws_istft_length() == 0 (perfectrec cuts away all that so few frames cover): LWS_OK, nothing is enqueued and neither pointer
+ * is used. */
 int lws_istft_dev(int device, const void *S_dev, int B, int M, int N, int fshift, const double *swin,
                   int perfectrec, float *x_dev, void *stream);
 /* stft with a transform longer than the frame (lws.pyx:49-50,85: np.fft.fft(frame, n = fftsize) of the fsize windowed samples,
@@ -193,7 +200,9 @@ int lws_stft_zp_dev(int device, const float *x_dev, int B, int len, int fsize, i
                     int perfectrec, void *S_dev, void *stream);
 /* get_consistency (lws.pyx:140-144) per spectrogram: out[2b] = sum |S|^2, out[2b+1] = sum |stft(istft(S)) - S|^2
  * (fp64 sums of the fp32 transform); consistency in dB = 10 log10(out[2b] / out[2b+1]).  out: HOST, 2*B doubles
- * (synchronises).  Sums of several spectrograms / ranks add up to the batch consistency. */
+ * (synchronises).  Sums of several spectrograms / ranks add up to the batch consistency.  With perfectrec, an M the round trip
+ * stft(istft(.)) does not keep -- lws_stft_frames(lws_istft_length(M, ...), ...) != M: too few frames -- is LWS_ERR_INVALID, before
+ * anything is enqueued (the host's get_consistency fails to subtract spectrograms of two shapes there). */
 int lws_consistency_dev(int device, const void *S_dev, int B, int M, int N, int fshift, const double *awin,
                         const double *swin, int perfectrec, double *out, void *stream);
 
@@ -204,7 +213,8 @@ int lws_consistency_dev(int device, const void *S_dev, int B, int M, int N, int 
  * iters == 0 leaves it unchanged.  A_dev[B][M][N/2+1] (float32) are the target magnitudes, NULL: |c_0|.  trace: NULL (the call
  * only enqueues work on `stream`), or HOST, iters*B*2 doubles (synchronises): trace[(i-1)*B*2 + 2b] = sum |c_{i-1}|^2 and
  * [.. + 1] = sum |P(c_{i-1}) - c_{i-1}|^2, the pair of lws_consistency_dev for the iterate entering step i.  float32 transforms,
- * two frames per complex transform.  iters < 0 or alpha outside [0, 1): LWS_ERR_INVALID. */
+ * two frames per complex transform.  iters < 0, alpha outside [0, 1), or, with iters > 0 and perfectrec, an M the round trip does
+ * not keep (too few frames for perfectrec, as lws_consistency_dev): LWS_ERR_INVALID, before anything is enqueued. */
 int lws_griffin_lim_dev(int device, void *C_dev, const float *A_dev, int B, int M, int N, int fshift, const double *awin,
                         const double *swin, int perfectrec, int iters, double alpha, double *trace, void *stream);
 

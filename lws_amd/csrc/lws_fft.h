@@ -26,11 +26,17 @@ __device__ float2 *fft_lds(float2 *x, float2 *y, int n, int m, int a, float sign
     const int n2 = n / m;                                // 2^a
     float2 *tw = y + n;
     if (m > 1) {
-        // exp(sign 2 pi j i / n), and the m interleaved subsequences side by side: y[r n2 + j] = x[m j + r]
+        // exp(sign 2 pi j i / n), and the m interleaved subsequences side by side: y[r n2 + j] = x[m j + r].  The angle is reduced in
+        // integers to the nearest quarter turn, 4 i = q n + rem with |rem| <= n / 2, so that the rounded quotient is at most 1/4:
+        // 2 i / n rounded as it stands is off by up to 2^-24 of a half turn near i = n, six times the rounding of the twiddle itself,
+        // and the m terms of an output bin see those errors coherently (an impulse's flat spectrum most of all)
         for (int i = tid; i < n; i += nthr) {
+            const int q = (4 * i + (n >> 1)) / n, rem = 4 * i - q * n;
             float sn, cs;
-            sincospif(2.0f * (float)i / (float)n, &sn, &cs);
-            tw[i] = make_float2(cs, sign * sn);
+            sincospif((float)rem / (float)(2 * n), &sn, &cs);
+            const float c = (q & 1) ? ((q & 2) ? sn : -sn) : ((q & 2) ? -cs : cs);
+            const float s = (q & 1) ? ((q & 2) ? -cs : cs) : ((q & 2) ? -sn : sn);
+            tw[i] = make_float2(c, sign * s);
             const int j = i / m, r = i - j * m;
             y[r * n2 + j] = x[i];
         }
@@ -97,13 +103,21 @@ Factors factor(int n) { Factors f{n, 0}; while (!(f.odd & 1)) { f.odd >>= 1; ++f
 size_t fft_lds_bytes(int N) { return (size_t)(factor(N).odd > 1 ? 3 : 2) * N * sizeof(float2); }
 
 constexpr int MAX_DEVICES = 64;
-int check_shape(int device, int B, int M, int N, int hop) {
+int check_shape(int device, int B, int M, int N, int hop, int min_frames = 1) {
     if (device < 0 || device >= MAX_DEVICES) return lws::set_error(LWS_ERR_INVALID, "device index %d out of range", device);
-    if (B < 0 || M < 1) return lws::set_error(LWS_ERR_INVALID, "empty batch or no frames");
+    if (B < 0 || M < min_frames) return lws::set_error(LWS_ERR_INVALID, "empty batch or no frames");
     if (N < MINN || N > MAXN || (N & 1)) return lws::set_error(LWS_ERR_UNSUPPORTED, "frame size %d: the device transform serves even sizes in [%d, %d]", N, MINN, MAXN);
     if (hop < 1 || hop > N) return lws::set_error(LWS_ERR_INVALID, "frame shift %d", hop);
     return LWS_OK;
 }
 int prepad(int N, int hop) { const int r = N % hop; return r == 0 ? N - hop : N - r; }   // lws.pyx:55-60
+
+// stft(istft(.)) of M frames must give M frames again for the round trip to be a projection: with perfectrec the cuts of
+// lws.pyx:130-137 leave too little of fewer than about N / hop frames (and nothing at all of hop == N)
+int check_round_trip(int M, int N, int hop, int perfectrec) {
+    if (perfectrec && lws_stft_frames(lws_istft_length(M, N, hop, perfectrec), N, hop, perfectrec) != M)
+        return lws::set_error(LWS_ERR_INVALID, "the round trip does not keep %d frames (too few frames for perfectrec)", M);
+    return LWS_OK;
+}
 
 }  // namespace

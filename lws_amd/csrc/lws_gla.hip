@@ -279,6 +279,7 @@ extern "C" int lws_griffin_lim_dev(int device, void *C_dev, const float *A_dev, 
     if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
     if (!(alpha >= 0.0 && alpha < 1.0)) return lws::set_error(LWS_ERR_INVALID, "momentum %g outside [0, 1)", alpha);
     if (!C_dev || !awin || !swin) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    if (iters > 0 && (rc = check_round_trip(M, N, fshift, perfectrec))) return rc;
     if (B == 0 || iters == 0) return LWS_OK;
     STFT_TRY(hipSetDevice(device));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -342,8 +343,7 @@ extern "C" int lws_misi_dev(int device, void *C_dev, const float *A_dev, const f
     if ((long long)B * K > 65535) return lws::set_error(LWS_ERR_UNSUPPORTED, "%d x %d spectrograms in one call (at most 65535)", B, K);
     const int len = lws_istft_length(M, N, fshift, perfectrec);
     if (len < 1) return lws::set_error(LWS_ERR_INVALID, "%d frames leave no samples", M);
-    if (iters > 0 && lws_stft_frames(len, N, fshift, perfectrec) != M)
-        return lws::set_error(LWS_ERR_INVALID, "the round trip does not keep %d frames (too few frames for perfectrec)", M);
+    if (iters > 0 && (rc = check_round_trip(M, N, fshift, perfectrec))) return rc;
     if (B == 0 || (iters == 0 && !x_dev)) return LWS_OK;
     STFT_TRY(hipSetDevice(device));
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -164,21 +164,28 @@ int lws_stft_frames(int len, int N, int fshift, int perfectrec) {
     }
     const long r = ((long)len - N) % fshift;
     const long padded = len + ((fshift - (r < 0 ? r + fshift : r)) % fshift);
+    if (padded < N) return 0;   // still shorter than one frame: an empty spectrogram (np.arange of a count <= 0, lws.pyx:76-84)
     return (int)((padded - N) / fshift + 1);
 }
 
 int lws_istft_length(int M, int N, int fshift, int perfectrec) {
     const int Tfull = fshift * (M - 1) + N;
-    return perfectrec ? Tfull - prepad(N, fshift) - (N - fshift) : Tfull;
+    if (M < 1 || N < 1 || fshift < 1) return 0;
+    if (!perfectrec) return Tfull;
+    // signal[pre : hop - N] (lws.pyx:135): an end of 0 is the START of the array, so hop == N keeps nothing, and a slice whose
+    // end lies before its beginning is empty
+    const int kept = fshift >= N ? 0 : Tfull - prepad(N, fshift) - (N - fshift);
+    return kept > 0 ? kept : 0;
 }
 
 // fs: samples per frame (the window's length), N >= fs: points of the transform (fs..N-1 are zeros)
 static int stft_impl(int device, const float *x_dev, int B, int len, int fs, int N, int fshift, const double *awin, int perfectrec,
                      void *S_dev, void *stream) {
     const int M = lws_stft_frames(len, fs, fshift, perfectrec);
-    int rc = check_shape(device, B, M, N, fshift);
+    int rc = check_shape(device, B, M, N, fshift, 0);
     if (rc) return rc;
     if (fs < 2 || fs > N || (fs & 1) || fshift > fs) return lws::set_error(LWS_ERR_INVALID, "frame of %d samples, transform of %d points, shift %d", fs, N, fshift);
+    if (M == 0) return LWS_OK;   // a signal shorter than one frame, without perfectrec: the spectrogram is empty, nothing to write
     if (!x_dev || !S_dev) return lws::set_error(LWS_ERR_INVALID, "null device pointer");
     if (B == 0) return LWS_OK;
     STFT_TRY(hipSetDevice(device));
@@ -199,6 +206,8 @@ int lws_istft_dev(int device, const void *S_dev, int B, int M, int N, int fshift
                   float *x_dev, void *stream) {
     int rc = check_shape(device, B, M, N, fshift);
     if (rc) return rc;
+    const int Tfull = fshift * (M - 1) + N, out_len = lws_istft_length(M, N, fshift, perfectrec);
+    if (out_len == 0) return LWS_OK;   // perfectrec cuts away all that so few frames cover: the signal is empty, nothing to write
     if (!x_dev || !S_dev) return lws::set_error(LWS_ERR_INVALID, "null device pointer");
     if (B == 0) return LWS_OK;
     STFT_TRY(hipSetDevice(device));
@@ -208,7 +217,6 @@ int lws_istft_dev(int device, const void *S_dev, int B, int M, int N, int fshift
     if ((rc = ctx_enter(c, s))) return rc;
     if ((rc = allow_lds_all())) return rc;
     if ((rc = upload_window(c.win_s, swin, N, s))) return rc;
-    const int Tfull = fshift * (M - 1) + N, out_len = lws_istft_length(M, N, fshift, perfectrec);
     if ((rc = c.frames.ensure((size_t)B * M * N * sizeof(float)))) return rc;
     if ((rc = c.signal.ensure((size_t)B * Tfull * sizeof(float)))) return rc;
     hipLaunchKernelGGL(k_istft_frames, dim3(M, B), dim3(FFT_THREADS), fft_lds_bytes(N), s,
@@ -238,6 +246,7 @@ int lws_consistency_dev(int device, const void *S_dev, int B, int M, int N, int 
                         const double *swin, int perfectrec, double *out, void *stream) {
     int rc = check_shape(device, B, M, N, fshift);
     if (rc) return rc;
+    if ((rc = check_round_trip(M, N, fshift, perfectrec))) return rc;
     if (!S_dev || !out) return lws::set_error(LWS_ERR_INVALID, "null pointer");
     if (B == 0) return LWS_OK;
     STFT_TRY(hipSetDevice(device));

@@ -132,7 +132,8 @@ def _dev_tensor(a, dtype, device):
 def stft_dev(x, fsize, fshift, awin, fftsize=None, perfectrec=False, device=0):
     """stft() above on the device (lws_stft.hip, float32): x a signal (len,) or a stack (B, len), numpy or torch; returns a complex64
     torch tensor (T, fftsize//2+1) / (B, T, ...).  fftsize > fsize: the fsize windowed samples followed by zeros, as
-    np.fft.fft(frame, n=fftsize) does (lws.pyx:49-50,85); any even fftsize in [32, 4096]."""
+    np.fft.fft(frame, n=fftsize) does (lws.pyx:49-50,85); any even fftsize in [32, 4096].  A signal too short for one frame gives an
+    empty (0, F) / (B, 0, F) tensor, as stft() gives an empty array."""
     import torch
     if fftsize is None:
         fftsize = fsize
@@ -154,7 +155,8 @@ def stft_dev(x, fsize, fshift, awin, fftsize=None, perfectrec=False, device=0):
 
 def istft_dev(spec, fshift, swin, awin=None, fftsize=None, perfectrec=False, device=0):
     """istft() above on the device: spec (T, F) or (B, T, F), numpy or torch; returns a float32 torch tensor (len,) / (B, len).
-    As in the reference (lws.pyx:107-126) the frame is 2 (F - 1) samples and any other fftsize / window length is a ValueError."""
+    As in the reference (lws.pyx:107-126) the frame is 2 (F - 1) samples and any other fftsize / window length is a ValueError.
+    Frames of which perfectrec keeps no sample give an empty (0,) / (B, 0) tensor, as istft() gives an empty array."""
     import torch
     t = _dev_tensor(spec, torch.complex64, device)
     if t.dim() not in (2, 3):
@@ -233,7 +235,7 @@ def griffin_lim_dev(S, fsize, fshift, awin, swin, iterations, alpha=0.99, magnit
     """griffin_lim() above on the device (lws_gla.hip: float32, the transforms fused with the magnitude projection, two launches
     per iteration): S (T, F) or (B, T, F), numpy or torch; returns a new complex64 torch tensor (S itself is not modified), and
     with return_trace also the dB values as a numpy array.  Runs on the caller's current torch stream; without return_trace
-    the call only enqueues work."""
+    the call only enqueues work.  Raises ValueError, as griffin_lim() does, for a frame count the round trip does not keep."""
     import torch
     n, alpha = _gla_args(iterations, alpha)
     t = _dev_tensor(S, torch.complex64, device)
@@ -244,6 +246,9 @@ def griffin_lim_dev(S, fsize, fshift, awin, swin, iterations, alpha=0.99, magnit
     B, T, F = t3.shape
     if F != fsize // 2 + 1:
         raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
+    back = _capi.stft_frames(_capi.istft_length(T, fsize, fshift, perfectrec), fsize, fshift, perfectrec)
+    if n > 0 and back != T:
+        raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
     A = None
     if magnitudes is not None:
         A = _dev_tensor(magnitudes, torch.float32, device)
