@@ -91,6 +91,13 @@ __device__ __forceinline__ void band_helper(const BArgs<real> &a, typename cx<re
     }
 }
 
+// 1 for a largest magnitude within 2^-24 .. 2^24 (and for zero, denormals, infinities), else the power of two that brings it to [1, 2)
+__device__ __forceinline__ float band_weight_scale(float amax) {
+    const int e = (int)((__float_as_uint(amax) >> 23) & 0xffu);
+    if (e == 0 || e == 0xff || (e >= 127 - 24 && e <= 127 + 24)) return 1.0f;
+    return __uint_as_float((unsigned)(e >= 254 ? 1 : 254 - e) << 23);
+}
+
 template <typename real, int LT, int QT, bool EXACT, int NH, int MAXT>
 __global__ void __launch_bounds__(MAXT) k_band(BArgs<real> a) {
     using C = typename cx<real>::type;
@@ -120,7 +127,17 @@ __global__ void __launch_bounds__(MAXT) k_band(BArgs<real> a) {
     {
         C z; z.x = 0; z.y = 0;
         for (int i = threadIdx.x; i < nring; i += blockDim.x) ring[i] = z;
-        for (int i = threadIdx.x; i < a.g.Q * (LT + 1) + a.g.Pt * (a.g.Q - 1); i += blockDim.x) wt[i] = a.tab[i];
+        // fp32: the sums are squared before they are normalised, and data near 1e-20 or 1e+20 squares out of the range.  The weights
+        // of such a spectrogram carry the power of two that brings its largest magnitude to [1, 2): exact, every sum is linear in
+        // them, and only its direction is used.  Within 2^-24 .. 2^24 -- any ordinary data -- the factor is 1 and no bit moves.
+        real wsc = 1;
+        if constexpr (sizeof(real) == 4) wsc = band_weight_scale(a.amax[blockIdx.x]);
+        const int nw = a.g.Q * (LT + 1);
+        for (int i = threadIdx.x; i < nw + a.g.Pt * (a.g.Q - 1); i += blockDim.x) {
+            C v = a.tab[i];
+            if (i < nw) { v.x *= wsc; v.y *= wsc; }
+            wt[i] = v;
+        }
         for (int i = threadIdx.x; i < a.nsl * 2 * NH * nls * 2; i += blockDim.x) mail[i] = z;
         __syncthreads();
     }

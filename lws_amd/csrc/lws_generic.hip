@@ -124,8 +124,8 @@ __device__ __forceinline__ void update_bin(typename cx<real>::type *S, const rea
     const real target = amp[idx];
     if (!(target > thr)) return;
     C *ctr = S + idx;
-    const C a = accumulate<real>(ctr, c, centre, two_sided, ws, Np, L, Q, Qp, add_self, qdiv, mk);
-    const real mag = sqrt(a.x * a.x + a.y * a.y);
+    C a = accumulate<real>(ctr, c, centre, two_sided, ws, Np, L, Q, Qp, add_self, qdiv, mk);
+    const real mag = rescued_norm<real>(a);       // (rescales a sum that fp32 cannot square: lws_common.h)
     if (!(mag > 0)) return;
     C v;
     v.x = a.x * target / mag;
@@ -166,7 +166,7 @@ __device__ __forceinline__ void update_bin_nfq4(typename cx<real>::type *S, cons
             }
         if (fa[u]) mac<real>(a, wa[u], p[0]);
     }
-    const real mag = sqrt(a.x * a.x + a.y * a.y);
+    const real mag = rescued_norm<real>(a);       // (rescales a sum that fp32 cannot square: lws_common.h)
     if (!(mag > 0)) return;
     C v;
     v.x = a.x * target / mag;
@@ -442,8 +442,8 @@ __global__ void __launch_bounds__(1024) k_skew_batch(GenericArgs<real> a, typena
                 const int lane = me & (NL - 1);
                 const real target = AW[row * NL + lane];
                 if (!(target > thr[g0 + k])) continue;
-                const C acc = accumulate_v<real>(SkewView<C>{SW, row, lane, sk, NL}, c, true, Q, ws, L, Q, Qp, add_self, a.qdiv, mk);
-                const real mag = sqrt(acc.x * acc.x + acc.y * acc.y);
+                C acc = accumulate_v<real>(SkewView<C>{SW, row, lane, sk, NL}, c, true, Q, ws, L, Q, Qp, add_self, a.qdiv, mk);
+                const real mag = rescued_norm<real>(acc);     // (rescales a sum that fp32 cannot square: lws_common.h)
                 if (!(mag > 0)) continue;
                 C v;
                 v.x = acc.x * target / mag;

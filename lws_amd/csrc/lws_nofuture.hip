@@ -186,10 +186,14 @@ __device__ __forceinline__ void nf_update_split(int n, int j, int me, float th, 
     if (j != 0) return;
     // target / |acc| as target * rsqrt(|acc|^2) (hardware reciprocal square root, 1 ulp: a round is a dependent chain, and the
     // exact square root and the two divisions of the reference form are a third of it); sums too small to square in fp32
-    // are rescaled first so that "|acc| > 0" keeps its meaning
+    // are rescaled first so that "|acc| > 0" keeps its meaning, and sums too large so that the square stays finite (data near
+    // 1e+20 used to be written as zeros: tests/test_gpu_sparse.py, power-of-two covariance at 2^66)
     float m2 = acc.x * acc.x + acc.y * acc.y;
     if (m2 < 1e-30f) {
         acc.x *= 0x1p60f; acc.y *= 0x1p60f;
+        m2 = acc.x * acc.x + acc.y * acc.y;
+    } else if (!(m2 <= 1e30f)) {
+        acc.x *= 0x1p-60f; acc.y *= 0x1p-60f;
         m2 = acc.x * acc.x + acc.y * acc.y;
     }
     if (!(m2 > 0.f)) return;

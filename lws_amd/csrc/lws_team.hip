@@ -139,7 +139,7 @@ __device__ __forceinline__ void team_bin(typename cx<real>::type *S, const real 
         }
     }
     if (act && g == 0) {
-        const real mag = sqrt(a.x * a.x + a.y * a.y);
+        const real mag = rescued_norm<real>(a);       // (rescales a sum that fp32 cannot square: lws_common.h)
         if (mag > 0) {
             C v;
             v.x = a.x * target / mag;
@@ -335,7 +335,7 @@ __global__ void __launch_bounds__(1024) k_team_online_ordered(GenericArgs<real> 
                 C acc;
                 acc.x = 0; acc.y = 0;
                 for (int jj = 0; jj <= NT; ++jj) { const C v = mine[jj]; acc.x += v.x; acc.y += v.y; }
-                const real mag = sqrt(acc.x * acc.x + acc.y * acc.y);
+                const real mag = rescued_norm<real>(acc);     // (rescales a sum that fp32 cannot square: lws_common.h)
                 if (mag > 0) {
                     C v;
                     v.x = acc.x * u.target / mag;
@@ -551,7 +551,7 @@ __global__ void __launch_bounds__(NCH == 3 ? 512 : 1024) k_team_online_ring(Gene
             }
         }
         if (act && g == 0) {
-            const real mag = sqrt(acc.x * acc.x + acc.y * acc.y);
+            const real mag = rescued_norm<real>(acc);     // (rescales a sum that fp32 cannot square: lws_common.h)
             if (mag > 0) {
                 C v;
                 v.x = acc.x * target / mag;
