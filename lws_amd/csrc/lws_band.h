@@ -20,8 +20,8 @@ struct BandPlan {
 // tensor with create_weights' twiddle structure (lws.pyx:160-181; WeightStructure::twiddle, any twiddle period whose table leaves room for a ring in the LDS -- for an fp64 plan
 // a summarised tensor (Qp == Q) whose rows are twiddle images of row 0 to 1e-13, so that the results are the reference's to rounding) and a frame short enough for one sweep
 // slot's ring in the LDS (Q F complex values: e.g. Q = 8 at 1025 bins, Q = 16 at 513 bins in fp32; half that in fp64).
-// ws: the analysis of the plan's tensor (lws_weights.h).  False: the caller uses the generic engine.
-bool band_plan(bool fp64, int B, int F, int T, int L, int Q, int Qp, int update, int n_thr, const WeightStructure &ws, BandPlan *out);
+// ws: the analysis of the plan's tensor (lws_weights.h).  sw: the call's switches (the LWS_BAND_* rows).  False: the caller uses the generic engine.
+bool band_plan(bool fp64, int B, int F, int T, int L, int Q, int Qp, int update, int n_thr, const WeightStructure &ws, const Switches &sw, BandPlan *out);
 const char *band_name(const BandPlan &bp);   // "band_fp32" / "band_fp64"
 // The two tables a kernel reads (lws_band_host.h: tables -- [Q][LT+1] weights, then [Pt][Q-1] twiddles), in the plan's arithmetic
 // type: what the caller keeps on the device for the plan's lifetime (they depend on W, LT and the precision only) and hands to

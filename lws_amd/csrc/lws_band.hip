@@ -265,7 +265,7 @@ inline double step_cost(int waves) {
 
 }  // namespace
 
-bool band_plan(bool fp64, int B, int F, int T, int L, int Q, int Qp, int update, int n_thr, const WeightStructure &ws, BandPlan *out) {
+bool band_plan(bool fp64, int B, int F, int T, int L, int Q, int Qp, int update, int n_thr, const WeightStructure &ws, const Switches &sw, BandPlan *out) {
     if (update != 2 || T < 1 || n_thr < 1 || Q < 2 || Q > 16 || L < 1 || L > 10 || Qp < 1) return false;
     // the stencil half-width the kernel is compiled for: 5, 10, and 8 for Q = 4 (`lws(1024,256,L=8)`: frames 10 steps apart instead of 12)
     const int LT = L <= 5 ? 5 : ((L <= 8 && Q == 4) ? 8 : 10), QT = Q <= 8 ? 8 : 16;
@@ -282,11 +282,11 @@ bool band_plan(bool fp64, int B, int F, int T, int L, int Q, int Qp, int update,
     if (!(fp64 ? ws.band_rows_fp64 : ws.band_rows_fp32)) return false;
     const size_t csize = fp64 ? 16 : 8;
     // (LWS_BAND_NO_HELPERS=1: the exact builds' one-wave-per-slot variant -- comparison runs)
-    const int helpers = env_int("LWS_BAND_NO_HELPERS", 0) ? 0 : helpers_of(fp64, LT, Q);
+    const int helpers = sw.band_no_helpers ? 0 : helpers_of(fp64, LT, Q);
     const int maxt = max_threads(fp64, LT, QT, helpers);
     BandPlan best{};
     double best_cost = 1e300;
-    const int skw_force = env_int("LWS_BAND_SKW", 0), nls_force = env_int("LWS_BAND_NLS", 0), ns_force = env_int("LWS_BAND_NS", 0);   // (tests)
+    const int skw_force = sw.band_skw, nls_force = sw.band_nls, ns_force = sw.band_ns;   // (LWS_BAND_SKW, _NLS, _NS: tests)
     for (int nls = 64; nls * (1 + helpers) <= maxt; nls *= 2) {
         if (nls_force && nls != nls_force) continue;
         for (int SKW = LT + 2; SKW <= LT + 2 + 10; ++SKW) {
@@ -313,8 +313,7 @@ bool band_plan(bool fp64, int B, int F, int T, int L, int Q, int Qp, int update,
     // spectrograms that go through the skewed scratch at a time: at most 32 GiB of it (LWS_BAND_CHUNK: for tests)
     const size_t per = (size_t)best.g.rows * best.g.nls * (csize + csize / 2);
     int chunk = (int)std::min<size_t>((size_t)std::max(B, 1), std::max<size_t>(1, ((size_t)32 << 30) / per));
-    const int cf = env_int("LWS_BAND_CHUNK", 0);
-    if (cf > 0) chunk = std::min(chunk, cf);
+    if (sw.band_chunk > 0) chunk = std::min(chunk, sw.band_chunk);
     best.chunk = chunk;
     best.state_bytes = (size_t)chunk * best.g.rows * best.g.nls * csize;
     best.amp_bytes = (size_t)chunk * best.g.rows * best.g.nls * (csize / 2) + (size_t)chunk * (csize / 2);   // (+ a largest magnitude per spectrogram)

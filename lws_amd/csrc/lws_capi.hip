@@ -167,6 +167,7 @@ struct lws_plan {
     int device = 0;
     int F = 0, L = 0, Q = 0, Qp = 0;
     unsigned flags = 0;
+    lws::Switches sw;              // the environment switches (lws_switches.h) as the public call in progress found them; read nowhere below it
     bool fp64 = false;
     bool have[3] = {false, false, false};
     bool twiddle_all = false;      // W, W_ai and W_af all have create_weights' twiddle structure (the online LDS engine relies on it)
@@ -257,8 +258,6 @@ int ensure_scratch(lws_plan *p, int B, int T, int n_thr) {
     return LWS_OK;
 }
 
-using lws::env_int;
-
 void begin_timing(lws_plan *p, hipStream_t s) {
     (void)hipEventRecord(p->ev0, s);
     p->last_launches = 0;
@@ -290,64 +289,59 @@ struct Route {
     lws::OnlinePlan op{};    // online LDS engine
 };
 
-// The engine of a stage: the first one, from `from` on, whose guard holds.  The routing switches (comparison runs) are read once per call:
-//   LWS_TEAM_FIRST=1     the team engine before the LDS engines of the online / no-future stages
-//   LWS_TEAM_FP64=1      fp64 plans: the team engine's re-associating kernels, and its no-future sweeps
-//   LWS_TEAM_ORDERED=1   fp32 plans: the team engine's order-exact online kernel
-//   LWS_NO_TEAM=1, LWS_NO_TEAM_Q8=1 (the online stage of an fp64 plan of Q = 8 on online64), LWS_NO_SYS64=1, LWS_ONLINE64_ONE_WAVE=1
-//   LWS_ONLINE_SERIAL_TAPS=1, LWS_NOFUTURE_SERIAL_TAPS=1: the verification variants of the LDS engines, which promise the generic
+// The engine of a stage: the first one, from `from` on, whose guard holds -- a function of the plan and the stage: the guards see the
+// environment only as the call's snapshot p->sw (the routing rows of lws_switches.h), which they hand to the geometry helpers they ask.
+//   LWS_ONLINE_SERIAL_TAPS, LWS_NOFUTURE_SERIAL_TAPS: the verification variants of the LDS engines, which promise the generic
 //   engine's bits -- a stage they do not take skips the team engine too
 Route choose_engine(const lws_plan *p, const Stage &st, Engine from = Engine::Systolic) {
     const int mode = st.mode, F = p->F, T = st.T, L = p->L, Q = p->Q, Qp = p->Qp, LA = st.LA, n = st.iters;
     const bool fp64 = p->fp64, generic = p->flags & LWS_FORCE_GENERIC, plain = p->flags & LWS_GENERIC_PLAIN_LAYOUT;
     const bool batch = mode == lws::MODE_BATCH, online = mode == lws::MODE_ONLINE;
     const bool nofuture = mode == lws::MODE_NOFUTURE || mode == lws::MODE_NOFUTURE_Q4_COMPAT;
-    const bool team_first = env_int("LWS_TEAM_FIRST", 0), team_fp64 = env_int("LWS_TEAM_FP64", 0), no_team = env_int("LWS_NO_TEAM", 0),
-               no_team_q8 = env_int("LWS_NO_TEAM_Q8", 0), no_sys64 = env_int("LWS_NO_SYS64", 0),
-               online_serial = env_int("LWS_ONLINE_SERIAL_TAPS", 0), nofuture_serial = env_int("LWS_NOFUTURE_SERIAL_TAPS", 0);
+    const lws::Switches &sw = p->sw;
     Route r;
     // (fp64 plans: the online and no-future recursions amplify the rounding of a re-associated sum by 5-10 per frame -- equally valid
     //  phases, but not the reference's numbers an fp64 plan exists to reproduce.  Their online stage runs on the team engine's
     //  ORDER-EXACT kernel (increments by many lanes, the sum by one, in the reference's order: the generic engine's bits); the
     //  re-associating kernels, and no-future sweeps, only with LWS_TEAM_FP64=1.)
-    r.ordered = online && (fp64 ? !team_fp64 : env_int("LWS_TEAM_ORDERED", 0) != 0);
-    r.one_wave = env_int("LWS_ONLINE64_ONE_WAVE", 0) != 0;
+    r.ordered = online && (fp64 ? !sw.team_fp64 : sw.team_ordered);
+    r.one_wave = sw.online64_one_wave;
     auto pick = [&](Engine e) { r.engine = e; return r; };
     auto at = [&](Engine e) { return from <= e; };
     auto team = [&] {
-        return !generic && (mode == lws::MODE_ONLINE || mode == lws::MODE_NOFUTURE) && lws::team_supports(mode, F, T, L, Q, Qp, LA, n) &&
-               (!r.ordered || lws::team_ordered_fits(F, T, L, Q, LA, n, fp64));
+        return !generic && (mode == lws::MODE_ONLINE || mode == lws::MODE_NOFUTURE) && lws::team_supports(sw, mode, F, T, L, Q, Qp, LA, n) &&
+               (!r.ordered || lws::team_ordered_fits(sw, F, T, L, Q, LA, n, fp64));
     };
     // fp64, Q = 8: the online stage goes to the team engine's order-exact kernel (831 ms for 256 x 500 x 257 against 1 296 on online64,
     // the same bits) -- with LWS_TEAM_FP64=1 its re-associating kernel with the window in LDS (483 ms)
     auto q8_team = [&] {
-        return Q == 8 && !no_team && !no_team_q8 && !online_serial && lws::team_supports(mode, F, T, L, Q, Qp, LA, n) &&
-               (team_fp64 ? lws::team_online_in_lds(true, F, T, L, Q, Qp, LA, n) : lws::team_ordered_fits(F, T, L, Q, LA, n, true));
+        return Q == 8 && !sw.no_team && !sw.no_team_q8 && !sw.online_serial_taps && lws::team_supports(sw, mode, F, T, L, Q, Qp, LA, n) &&
+               (sw.team_fp64 ? lws::team_online_in_lds(sw, true, F, T, L, Q, Qp, LA, n) : lws::team_ordered_fits(sw, F, T, L, Q, LA, n, true));
     };
 
     // 1. fp32 batch sweeps of the plans a systolic build was made for (plan creation)
     if (at(Engine::Systolic) && !fp64 && batch && !generic && p->sysb && p->sysb->supports(p->sys, st.wsel, T)) return pick(Engine::Systolic);
-    if (at(Engine::TeamFirst) && team_first && (!fp64 || team_fp64 || online) && team()) return pick(Engine::TeamFirst);
+    if (at(Engine::TeamFirst) && sw.team_first && (!fp64 || sw.team_fp64 || online) && team()) return pick(Engine::TeamFirst);
     // 2. online and no-future sweeps: the moving window / the last Q + 1 frames in LDS (fp64: the generic engine's bits)
     if (at(Engine::OnlineLds) && !fp64 && online && !generic &&
-        (r.op = lws::online_plan(F, T, L, Q, Qp, LA, n, 2, p->twiddle_all ? p->tw_P : 0, p->tw_s, p->online_tw.p != nullptr)).ok)
+        (r.op = lws::online_plan(sw, F, T, L, Q, Qp, LA, n, 2, p->twiddle_all ? p->tw_P : 0, p->tw_s, p->online_tw.p != nullptr)).ok)
         return pick(Engine::OnlineLds);
     if (at(Engine::NofutureLds) && nofuture && !generic &&
-        (fp64 ? lws::nofuture_lds64_supports(F, T, L, Q, Qp, p->wstruct[st.wsel].row_period) : lws::nofuture_lds_supports(F, T, L, Q, Qp, p->wstruct[st.wsel].row_period)))
+        (fp64 ? lws::nofuture_lds64_supports(F, T, L, Q, Qp, p->wstruct[st.wsel].row_period) : lws::nofuture_lds_supports(F, T, L, Q, Qp, p->wstruct[st.wsel].row_period, sw.nofuture_serial_taps)))
         return pick(Engine::NofutureLds);
     if (at(Engine::Online64) && fp64 && online && !generic && !q8_team() && lws::online64_supports(F, T, L, Q, Qp, LA, n, 2))
         return pick(Engine::Online64);
     // 3. batch sweeps no systolic build takes: the fp64 systolic engine, the band engine (weights with create_weights' twiddle
     //    structure, a sweep slot's ring in LDS), the generic engine on a time-skewed copy of the state (coalesced taps; same bits)
-    if (at(Engine::Sys64) && fp64 && batch && !generic && !plain && !no_sys64 &&
+    if (at(Engine::Sys64) && fp64 && batch && !generic && !plain && !sw.no_sys64 &&
         lws::sys64_supports(F, T, L, Q, 2, p->wstruct[st.wsel]))
         return pick(Engine::Sys64);
     if (at(Engine::Band) && batch && !generic && !plain && p->have[st.wsel] &&
-        lws::band_plan(fp64, st.B, F, T, L, Q, Qp, 2, n, p->wstruct[st.wsel], &r.bp))
+        lws::band_plan(fp64, st.B, F, T, L, Q, Qp, 2, n, p->wstruct[st.wsel], sw, &r.bp))
         return pick(Engine::Band);
     if (at(Engine::GenericSkew) && batch && !plain) return pick(Engine::GenericSkew);
     // 4. online and no-future sweeps no LDS engine takes: the team engine (the generic engine's schedule, a bin's taps on a team of lanes)
-    if (at(Engine::Team) && !no_team && (!fp64 || r.ordered || team_fp64) && !online_serial && !nofuture_serial && team()) return pick(Engine::Team);
+    if (at(Engine::Team) && !sw.no_team && (!fp64 || r.ordered || sw.team_fp64) && !sw.online_serial_taps && !sw.nofuture_serial_taps && team()) return pick(Engine::Team);
     return pick(Engine::Generic);
 }
 
@@ -358,7 +352,7 @@ template <typename real>
 int ensure_route_scratch(lws_plan *p, const Route &r, const Stage &st) {
     size_t sb = 0, ab = 0;
     if (r.engine == Engine::Sys64) {
-        sb = lws::sys64_bytes(st.B, p->F, st.T, p->Q, &ab);
+        sb = lws::sys64_bytes(st.B, p->F, st.T, p->Q, p->sw.s64_chunk, &ab);
     } else if (r.engine == Engine::Band) {
         if (p->band_tab_lt[st.wsel] != r.bp.LT) {   // (once per plan and tensor: a blocking copy of a few KB)
             const std::vector<unsigned char> tab = lws::band_tables(r.bp, p->hostW[st.wsel].data());
@@ -403,7 +397,7 @@ int launch_route(lws_plan *p, const Route &r, const lws::GenericArgs<real> &a, i
         break;
     case Engine::TeamFirst:
     case Engine::Team:
-        e = lws::launch_team<real>(a, B, r.ordered, s);
+        e = lws::launch_team<real>(p->sw, a, B, r.ordered, s);
         name = a.mode == lws::MODE_ONLINE ? (r.ordered ? (fp64 ? "team_online_ordered_fp64" : "team_online_ordered_fp32") : (fp64 ? "team_online_fp64" : "team_online_fp32"))
                                           : (fp64 ? "team_nofuture_fp64" : "team_nofuture_fp32");
         what = "team engine";
@@ -414,16 +408,16 @@ int launch_route(lws_plan *p, const Route &r, const lws::GenericArgs<real> &a, i
         break;
     case Engine::NofutureLds:
         if constexpr (fp64) e = lws::launch_nofuture_lds64(a, B, p->wstruct[a.wsel].row_period, s);
-        else e = lws::launch_nofuture_lds(a, B, p->wstruct[a.wsel].row_period, s);
+        else e = lws::launch_nofuture_lds(a, B, p->wstruct[a.wsel].row_period, p->sw.nofuture_serial_taps, s);
         name = fp64 ? (q4compat ? "nofuture_lds_q4compat_fp64" : "nofuture_lds_fp64") : (q4compat ? "nofuture_lds_q4compat_fp32" : "nofuture_lds_fp32");
         what = fp64 ? "fp64 no-future" : "no-future";
         break;
     case Engine::Online64:
-        if constexpr (fp64) e = lws::launch_online64(a, B, r.one_wave, s);
+        if constexpr (fp64) e = lws::launch_online64(a, B, r.one_wave, p->sw.online64_stress, s);
         name = r.one_wave ? "online_lds_fp64_1w" : "online_lds_fp64", what = "fp64 online";
         break;
     case Engine::Sys64:
-        if constexpr (fp64) e = lws::launch_sys64(a, p->hostW[a.wsel].data(), p->wstruct[a.wsel], B, p->gsk_state.p, p->gsk_amp.p, s, &launches, p->ev0, p->ev1);
+        if constexpr (fp64) e = lws::launch_sys64(a, p->hostW[a.wsel].data(), p->wstruct[a.wsel], B, p->sw.s64_chunk, p->gsk_state.p, p->gsk_amp.p, s, &launches, p->ev0, p->ev1);
         name = lws::sys64_name(a.F, a.T, a.Q), what = "fp64 systolic";
         break;
     case Engine::Band:
@@ -731,26 +725,25 @@ namespace {
 // whole_device: some stage of the call runs ONE workgroup per spectrogram (no-future, online, the generic engine): a launch of
 // fewer spectrograms than CUs takes as long as one of a full device's worth, so chunks hold multiples of the CU count
 // (config 3, 256 spectrograms: four chunks of 64 took 259 ms, one of 256 takes 105)
-int host_chunk(size_t per, int B, int n_cu, bool whole_device = false) {
-    const size_t target = (size_t)std::max(1, env_int("LWS_HOST_CHUNK_BINS", 16 << 20));
+int host_chunk(const lws::Switches &sw, size_t per, int B, int n_cu, bool whole_device = false) {
+    const size_t target = (size_t)std::max(1, sw.host_chunk_bins), pin_limit = (size_t)std::max(1, sw.host_pin_mb) << 20;
     if (per * (size_t)B <= target + target / 2) return B;
     int bc = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, (target + per / 2) / per));
-    if (whole_device && n_cu > 1 && !env_int("LWS_HOST_CHUNK_EXACT", 0)) {
+    if (whole_device && n_cu > 1 && !sw.host_chunk_exact) {
         bc = std::min(B, std::max(n_cu, bc - bc % n_cu));
         // ... but the pipeline pins four host buffers of a chunk each (and holds two on the device): long spectrograms are cut
         // below a device's worth (half, a quarter, ... of the CUs busy in the one-workgroup stages) rather than pin tens of GB
-        const size_t pin_limit = (size_t)std::max(1, env_int("LWS_HOST_PIN_MB", 2048)) << 20;
         while (bc > 1 && (size_t)bc * per * sizeof(float2) > pin_limit) bc = (bc + 1) / 2;
         return bc;
     }
     // a launch of fewer spectrograms than CUs gives each floor(CUs / spectrograms) workgroups (lws_systolic.hip: prepare):
     // 65 spectrograms on 256 CUs keep 195 of them busy, 64 all of them -- round to a divisor / multiple of the CU count
-    if (n_cu > 1 && !env_int("LWS_HOST_CHUNK_EXACT", 0)) {
+    if (n_cu > 1 && !sw.host_chunk_exact) {
         if (bc >= n_cu) bc -= bc % n_cu;
         // a batch of several devices' worth: chunks of one device's worth, one workgroup per spectrogram -- the launches then run at
         // the whole-batch rate (no passes shared out between workgroups) and only the first upload / last download are exposed
         // (1024 x 500 x 513, round 5: 211 ms in chunks of 64, 154 in chunks of 256, 131 device-resident)
-        else if (B >= 2 * n_cu && (size_t)n_cu * per * sizeof(float2) <= ((size_t)std::max(1, env_int("LWS_HOST_PIN_MB", 2048)) << 20)) bc = n_cu;
+        else if (B >= 2 * n_cu && (size_t)n_cu * per * sizeof(float2) <= pin_limit) bc = n_cu;
         else bc = std::max(1, n_cu / ((n_cu + bc - 1) / bc));
     }
     return std::min(bc, B);
@@ -790,17 +783,18 @@ int run_host_pipelined(lws_plan *p, const double *S_in, double *S_out, int B, in
     bool whole_device = false;   // (some stage of the call is not on the systolic engine)
     for (int i = 0; i < n; ++i)
         if (st[i].iters > 0 && !on_systolic(p, st[i], B, T)) whole_device = true;
-    const int Bc = host_chunk(per, B, cu_count(p->device), whole_device);
+    const lws::Switches &sw = p->sw;
+    const int Bc = host_chunk(sw, per, B, cu_count(p->device), whole_device);
     // chunk c = spectrograms [cs[c], cs[c + 1]).  The first upload and the last download have nothing to overlap with: when the
     // batch is cut at all, the first chunk is half a chunk (the device starts after half the narrowing and half the copy), and the
     // remainder that leaves at the end is half a chunk too.
     std::vector<int> cs{0};
-    if (Bc < B && Bc >= 2 && !whole_device && env_int("LWS_HOST_HALF_FIRST", 1)) cs.push_back(Bc / 2);
+    if (Bc < B && Bc >= 2 && !whole_device && sw.host_half_first) cs.push_back(Bc / 2);
     while (cs.back() < B) cs.push_back(std::min(B, cs.back() + Bc));
     const int nch = (int)cs.size() - 1;
     // conversion threads: up to 32 (more gain nothing: the passes are memory-bound), at most the CPUs the process can use at once
     // (lws_multi_* plans: their share of them -- eight plans of 32 threads on a 16-CPU quota only fight each other)
-    int nthreads = env_int("LWS_HOST_THREADS", std::min(32, p->host_threads > 0 ? p->host_threads : lws::usable_cpus()));
+    int nthreads = sw.host_threads != lws::SWITCH_UNSET ? sw.host_threads : std::min(32, p->host_threads > 0 ? p->host_threads : lws::usable_cpus());
     if (total < ((size_t)1 << 20)) nthreads = 1;
     nthreads = std::max(1, std::min(nthreads, 64));
     HIP_TRY(hipSetDevice(p->device));
@@ -825,11 +819,11 @@ int run_host_pipelined(lws_plan *p, const double *S_in, double *S_out, int B, in
     // and is expanded on the device.  Decided chunk by chunk while narrowing: the pass that reads every element anyway stops at
     // the first non-zero imaginary part and the chunk is narrowed again as complex (an input that starts real and turns complex
     // pays for that once; a complex input fails the probe below and never tries).
-    bool real_mode = env_int("LWS_HOST_REAL", 1) != 0;
+    bool real_mode = sw.host_real;
     for (size_t i = 0; i < std::min<size_t>(total, 256) && real_mode; ++i) real_mode = S_in[2 * i + 1] == 0.0;
     std::vector<char> chunk_real(nch, 0);
     // LWS_HOST_TRACE=1: where the call's wall time goes, on stderr (ms since the call began)
-    const bool trace = env_int("LWS_HOST_TRACE", 0) != 0;
+    const bool trace = sw.host_trace;
     const auto t_begin = std::chrono::steady_clock::now();
     auto mark = [&](const char *what, int c) {
         if (trace) fprintf(stderr, "[lws host] %7.2f ms  %s %d\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(), what, c);
@@ -935,7 +929,7 @@ int run_host_pipelined(lws_plan *p, const double *S_in, double *S_out, int B, in
             char *hi = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(S_out) + total * 16) & ~(uintptr_t)4095);
             const int ways = std::min(8, pool.size());
             std::atomic<bool> populate_fallback{false};
-            if (hi > lo && env_int("LWS_HOST_PREFAULT", 1))
+            if (hi > lo && sw.host_prefault)
                 pool.run(ways, [&](int i) {
                     const size_t pages = (size_t)(hi - lo) >> 12, a = pages * i / ways, b = pages * (i + 1) / ways;
                     if (b > a && madvise(lo + (a << 12), (b - a) << 12, LWS_MADV_POPULATE_WRITE) != 0) {
@@ -973,6 +967,7 @@ int run_host_pipelined(lws_plan *p, const double *S_in, double *S_out, int B, in
 
 // host complex128 in/out
 int run_host(lws_plan *p, const double *S_in, double *S_out, int B, int T, const StageSpec *st, int n) {
+    p->sw = lws::read_switches();
     if (!S_in || !S_out) return fail(LWS_ERR_INVALID, "null spectrogram pointer");
     int rc = need_weights(p, st, n);
     if (rc) return rc;
@@ -983,7 +978,7 @@ int run_host(lws_plan *p, const double *S_in, double *S_out, int B, int T, const
         if (S_out != S_in) memcpy(S_out, S_in, count * 2 * sizeof(double));
         return LWS_OK;
     }
-    if (!p->fp64 && !env_int("LWS_HOST_MONOLITHIC", 0)) return run_host_pipelined(p, S_in, S_out, B, T, st, n);
+    if (!p->fp64 && !p->sw.host_monolithic) return run_host_pipelined(p, S_in, S_out, B, T, st, n);
     return run_host_monolithic(p, S_in, S_out, B, T, st, n);
 }
 
@@ -1009,6 +1004,7 @@ int run_host_monolithic(lws_plan *p, const double *S_in, double *S_out, int B, i
 
 // device in place: complex64 for fp32 plans, complex128 for fp64 plans
 int run_dev(lws_plan *p, void *S_dev, int B, int T, const StageSpec *st, int n, void *stream) {
+    p->sw = lws::read_switches();
     if (!S_dev) return fail(LWS_ERR_INVALID, "null device pointer");
     int rc = need_weights(p, st, n);
     if (rc) return rc;
@@ -1097,6 +1093,8 @@ int lws_plan_create(lws_plan **plan, int device, int F, int L, int Q, int Qp, co
     p->F = F; p->L = L; p->Q = Q; p->Qp = Qp;
     p->flags = flags;
     p->fp64 = (flags & LWS_PRECISION_FP64) != 0;
+    p->sw = lws::read_switches();   // the CREATE rows bind here: what they decide (systolic build, twiddle table) stays in the plan, no later snapshot is asked
+    p->sys.sw = &p->sw;
     if (p->fp64 && (flags & LWS_STORAGE_FP16)) {
         delete p;
         return fail(LWS_ERR_INVALID, "LWS_STORAGE_FP16 is a storage mode of the fp32 engine; it cannot be combined with LWS_PRECISION_FP64");
@@ -1119,15 +1117,15 @@ int lws_plan_create(lws_plan **plan, int device, int F, int L, int Q, int Qp, co
         if (P > 0) { p->tw_P = P; p->tw_s = sg; }
     }
     if (p->twiddle_all && p->tw_P == 0) { p->tw_P = Q; p->tw_s = 1; }
-    if (rc == LWS_OK && p->twiddle_all && !p->fp64 && !lws::online_static_twiddles(Q, p->tw_P, p->tw_s) && Q <= 8) {
+    if (rc == LWS_OK && p->twiddle_all && !p->fp64 && !lws::online_static_twiddles(Q, p->tw_P, p->tw_s, p->sw.online_table_twiddles) && Q <= 8) {
         std::vector<float> tab((size_t)(p->tw_P + 3) * (Q <= 4 ? 8 : 16));
         lws::online_twiddle_table(p->tw_P, p->tw_s, Q, tab.data());
         if ((rc = p->online_tw.ensure(tab.size() * sizeof(float))) == LWS_OK &&
             hipMemcpy(p->online_tw.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
             rc = fail(LWS_ERR_HIP, "twiddle table upload failed");
     }
-    // (LWS_NO_SYSTOLIC=1, read here: no systolic build -- comparison runs of the engines behind them)
-    if (rc == LWS_OK && !p->fp64 && !(flags & LWS_FORCE_GENERIC) && !env_int("LWS_NO_SYSTOLIC", 0)) {
+    // (LWS_NO_SYSTOLIC=1: no systolic build -- comparison runs of the engines behind them)
+    if (rc == LWS_OK && !p->fp64 && !(flags & LWS_FORCE_GENERIC) && !p->sw.no_systolic) {
         const double *hw[3] = {p->have[0] ? p->hostW[0].data() : nullptr,
                                p->have[1] ? p->hostW[1].data() : nullptr,
                                p->have[2] ? p->hostW[2].data() : nullptr};
@@ -1135,8 +1133,7 @@ int lws_plan_create(lws_plan **plan, int device, int F, int L, int Q, int Qp, co
         hipError_t e = hipSuccess;
         // the first build that takes the shape, in the order of lws_systolic_builds.h.  LWS_SYSTOLIC_NO_SHORT=1, _NO_TW=1, _NO_R16=1 skip
         // kinds of builds (comparison runs)
-        const unsigned skip = (env_int("LWS_SYSTOLIC_NO_SHORT", 0) ? lws::SYSTOLIC_SHORT : 0u) | (env_int("LWS_SYSTOLIC_NO_TW", 0) ? lws::SYSTOLIC_TW : 0u) |
-                              (env_int("LWS_SYSTOLIC_NO_R16", 0) ? lws::SYSTOLIC_R16 : 0u);
+        const unsigned skip = (p->sw.systolic_no_short ? lws::SYSTOLIC_SHORT : 0u) | (p->sw.systolic_no_tw ? lws::SYSTOLIC_TW : 0u) | (p->sw.systolic_no_r16 ? lws::SYSTOLIC_R16 : 0u);
         int n_builds = 0;
         const lws::SystolicBuild *const *builds = lws::systolic_builds(&n_builds);
         for (int i = 0; i < n_builds; ++i) {
@@ -1259,6 +1256,7 @@ int lws_run_lws_dev(lws_plan *p, void *S_dev, int B, int T, const double *thr_no
 int lws_plan_reserve(lws_plan *p, int B, int T, int max_iters) {
     if (!p) return fail(LWS_ERR_INVALID, "null plan");
     if (B < 1 || T < 1 || max_iters < 0) return fail(LWS_ERR_INVALID, "need B >= 1, T >= 1, max_iters >= 0");
+    p->sw = lws::read_switches();
     HIP_TRY(hipSetDevice(p->device));
     int rc = p->fp64 ? ensure_scratch<double>(p, B, T, max_iters) : ensure_scratch<float>(p, B, T, max_iters);
     if (rc) return rc;
@@ -1268,7 +1266,7 @@ int lws_plan_reserve(lws_plan *p, int B, int T, int max_iters) {
                       // first call does not pay for them (hipHostMalloc of 4 x 128 MB: ~50 ms)
         const size_t per = (size_t)T * p->F;
         // (both chunkings: a call that is one batch stage, and one with a one-workgroup-per-spectrogram stage -- larger chunks)
-        const int bc0 = host_chunk(per, B, cu_count(p->device), false), bc1 = host_chunk(per, B, cu_count(p->device), true);
+        const int bc0 = host_chunk(p->sw, per, B, cu_count(p->device), false), bc1 = host_chunk(p->sw, per, B, cu_count(p->device), true);
         if ((rc = p->pipe.ensure((size_t)bc0 * per * sizeof(float2), bc0 < B ? 2 : 1))) return rc;
         if ((rc = p->pipe.ensure((size_t)bc1 * per * sizeof(float2), bc1 < B ? 2 : 1))) return rc;
     }
@@ -1455,6 +1453,7 @@ int lws_debug_stage_ext(lws_plan *p, int stage, int wsel, void *state_ext, const
     int rc = check_common(p, B, T, thresholds, iters);
     if (rc) return rc;
     if (!state_ext || !amp_ext || stage < 0 || stage > 2 || B < 1 || iters < 1) return fail(LWS_ERR_INVALID, "lws_debug_stage_ext: bad arguments");
+    p->sw = lws::read_switches();
     StageSpec st{stage == 0 ? lws::MODE_BATCH : (stage == 1 ? lws::MODE_NOFUTURE : lws::MODE_ONLINE), wsel, thresholds, iters, LA, qdiv};
     if ((rc = need_weights(p, &st, 1))) return rc;
     HIP_TRY(hipSetDevice(p->device));

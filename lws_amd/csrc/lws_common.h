@@ -8,13 +8,9 @@
 
 #include <atomic>
 
-namespace lws {
+#include "lws_switches.h"   // lws::Switches: the environment switches, read once per public call (lws_capi.hip) and handed down
 
-// The environment switches of the library (comparison runs and tests): the integer value of `name`, `dflt` if it is unset or empty.
-inline int env_int(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
-}
+namespace lws {
 
 // Lets `Kernel` be launched with up to `bytes` of dynamic LDS.  The runtime's attribute is per kernel and per device: one bit per
 // device for each kernel, in an atomic (lws_multi_* launches the same kernels from one host thread per device); a

@@ -323,8 +323,8 @@ hipError_t launch_ts(const NfArgsT<R> &a, int B, int threads, size_t lds, hipStr
 }
 // threads: of the one-lane-per-bin variant; the eight-lane one takes up to 1024
 template <int QT, int LT, bool COMPAT>
-hipError_t launch_t(const NfArgs &a, int B, int threads, size_t lds, hipStream_t s) {
-    if (lws::env_int("LWS_NOFUTURE_SERIAL_TAPS", 0) == 1)   // verification only: one lane sums every tap, in the generic engine's order
+hipError_t launch_t(const NfArgs &a, int B, bool serial, int threads, size_t lds, hipStream_t s) {
+    if (serial)   // (LWS_NOFUTURE_SERIAL_TAPS) verification only: one lane sums every tap, in the generic engine's order
         return launch_ts<QT, LT, COMPAT, false>(a, B, threads, lds, s);
     int t8 = threads * 4;
     if (t8 > 1024) t8 = 1024;
@@ -334,7 +334,7 @@ hipError_t launch_t(const NfArgs &a, int B, int threads, size_t lds, hipStream_t
 struct NfShape { int NR, threads; size_t lds; bool ok; };
 
 // rows: weight rows the kernel keeps in LDS (Q for a summarised tensor, the row period of a general one; 0: not periodic)
-NfShape shape_of(int F, int T, int L, int Q, int Qp, int rows, bool fp64 = false) {
+NfShape shape_of(int F, int T, int L, int Q, int Qp, int rows, bool serial, bool fp64 = false) {
     NfShape sh{0, 0, 0, false};
     if (rows < 1 || (Qp == Q && rows != Q) || (Qp != Q && (Qp != 2 * (F - 1) || Qp % rows != 0)) || Q < 2 || L < 1 || T < 1) return sh;
     const int Np = F + 2 * L;
@@ -345,7 +345,7 @@ NfShape shape_of(int F, int T, int L, int Q, int Qp, int rows, bool fp64 = false
     // three elements of a frame per thread at most (the prefetch of the next frame): the eight-lanes-per-bin variant runs up to
     // 1024 threads (frames of up to 3072 columns: 4096-point STFTs), the one-lane verification variant `threads`
     {
-        const int launched = (fp64 || lws::env_int("LWS_NOFUTURE_SERIAL_TAPS", 0) == 1) ? sh.threads : (4 * sh.threads > 1024 ? 1024 : 4 * sh.threads);
+        const int launched = (fp64 || serial) ? sh.threads : (4 * sh.threads > 1024 ? 1024 : 4 * sh.threads);
         if (3 * launched < Np) return sh;
     }
     if (Q * (L + 1) > 64) return sh;     // one 64-bit participation mask per weight row
@@ -358,33 +358,33 @@ NfShape shape_of(int F, int T, int L, int Q, int Qp, int rows, bool fp64 = false
 
 }  // namespace
 
-bool nofuture_lds_supports(int F, int T, int L, int Q, int Qp, int rows) { return shape_of(F, T, L, Q, Qp, rows).ok; }
+bool nofuture_lds_supports(int F, int T, int L, int Q, int Qp, int rows, bool serial) { return shape_of(F, T, L, Q, Qp, rows, serial).ok; }
 // (summarised tensors only: the rows of a general tensor repeat to 1e-9, not to the bit)
-bool nofuture_lds64_supports(int F, int T, int L, int Q, int Qp, int rows) { return Qp == Q && shape_of(F, T, L, Q, Qp, rows, true).ok; }
+bool nofuture_lds64_supports(int F, int T, int L, int Q, int Qp, int rows) { return Qp == Q && shape_of(F, T, L, Q, Qp, rows, true, true).ok; }
 
-hipError_t launch_nofuture_lds(const GenericArgs<float> &g, int B, int rows, hipStream_t stream) {
-    const NfShape sh = shape_of(g.F, g.T, g.L, g.Q, g.Qp, rows);
+hipError_t launch_nofuture_lds(const GenericArgs<float> &g, int B, int rows, bool serial, hipStream_t stream) {
+    const NfShape sh = shape_of(g.F, g.T, g.L, g.Q, g.Qp, rows, serial);
     if (!sh.ok) return hipErrorInvalidValue;
     NfArgs a;
     a.state = g.state; a.amp = g.amp; a.thr = g.thr;
     a.w = g.w[g.wsel].w; a.flag = g.w[g.wsel].flag;
     a.F = g.F; a.T = g.T; a.L = g.L; a.Q = g.Q; a.n_thr = g.n_thr; a.NR = sh.NR; a.rows = rows;
     a.compat = (g.mode == MODE_NOFUTURE_Q4_COMPAT);
-    if (rows != g.Q) return a.compat ? hipErrorInvalidValue : launch_t<0, 0, false>(a, B, sh.threads, sh.lds, stream);   // general weights
+    if (rows != g.Q) return a.compat ? hipErrorInvalidValue : launch_t<0, 0, false>(a, B, serial, sh.threads, sh.lds, stream);   // general weights
     if (a.compat) {
         if (g.Q != 4) return hipErrorInvalidValue;
-        return g.L == 5 ? launch_t<4, 5, true>(a, B, sh.threads, sh.lds, stream) : launch_t<4, 0, true>(a, B, sh.threads, sh.lds, stream);
+        return g.L == 5 ? launch_t<4, 5, true>(a, B, serial, sh.threads, sh.lds, stream) : launch_t<4, 0, true>(a, B, serial, sh.threads, sh.lds, stream);
     }
-    if (g.Q == 4 && g.L == 5) return launch_t<4, 5, false>(a, B, sh.threads, sh.lds, stream);
-    if (g.Q == 2 && g.L == 5) return launch_t<2, 5, false>(a, B, sh.threads, sh.lds, stream);
-    if (g.Q == 8 && g.L == 5) return launch_t<8, 5, false>(a, B, sh.threads, sh.lds, stream);
-    return launch_t<0, 0, false>(a, B, sh.threads, sh.lds, stream);
+    if (g.Q == 4 && g.L == 5) return launch_t<4, 5, false>(a, B, serial, sh.threads, sh.lds, stream);
+    if (g.Q == 2 && g.L == 5) return launch_t<2, 5, false>(a, B, serial, sh.threads, sh.lds, stream);
+    if (g.Q == 8 && g.L == 5) return launch_t<8, 5, false>(a, B, serial, sh.threads, sh.lds, stream);
+    return launch_t<0, 0, false>(a, B, serial, sh.threads, sh.lds, stream);
 }
 
 // The no-future sweeps of an fp64 plan: the one-lane-per-bin variant above in double -- update_bin / update_bin_nfq4 of lws_generic.hip on
 // the LDS ring, same arithmetic, same order, no contraction: generic_fp64's results bit for bit (tests/test_gpu_online64.py).
 hipError_t launch_nofuture_lds64(const GenericArgs<double> &g, int B, int rows, hipStream_t stream) {
-    const NfShape sh = shape_of(g.F, g.T, g.L, g.Q, g.Qp, rows, true);
+    const NfShape sh = shape_of(g.F, g.T, g.L, g.Q, g.Qp, rows, true, true);
     if (!sh.ok) return hipErrorInvalidValue;
     NfArgsT<double> a;
     a.state = g.state; a.amp = g.amp; a.thr = g.thr;

@@ -19,13 +19,13 @@ struct OnlinePlan {
 };
 // Plans a stage, once: ok if launch_online_lds can run this shape -- all three tensors with the common twiddle structure (tw_P, tw_s) that
 // WeightStructure::twiddle (lws_weights.h) finds -- static eighth turns (P = Q in {2,4,8}, s = 1: either layout) or a table (Q in 3..8, any P <= 512:
-// layout 4) -- L <= 5 (L = 5 for layout 2), the window of frames the sweeps in flight need fits the LDS ring.  Reads the engine's
-// switches (LWS_ONLINE_SERIAL_TAPS, LWS_ONLINE_LAG_PLUS, LWS_ONLINE_LAYOUT); the launcher reads none.
-OnlinePlan online_plan(int F, int T, int L, int Q, int Qp, int LA, int n_thr, int update, int tw_P, int tw_s, bool table);
+// layout 4) -- L <= 5 (L = 5 for layout 2), the window of frames the sweeps in flight need fits the LDS ring.  Of the call's
+// switches `sw` it uses LWS_ONLINE_SERIAL_TAPS, LWS_ONLINE_LAG_PLUS, LWS_ONLINE_LAYOUT; the launcher uses none.
+OnlinePlan online_plan(const Switches &sw, int F, int T, int L, int Q, int Qp, int LA, int n_thr, int update, int tw_P, int tw_s, bool table);
 // [P + 3][TQ] complex twiddles for the table variant, TQ = 4 (Q <= 4) or 8 (out: 2 (P + 3) TQ floats)
 void online_twiddle_table(int P, int s, int Q, float *out);
-// do the twiddles exp(2 pi j p r s / P) need no table (eighth turns of Q in {2,4,8})?
-bool online_static_twiddles(int Q, int tw_P, int tw_s);
+// do the twiddles exp(2 pi j p r s / P) need no table (eighth turns of Q in {2,4,8})?  force_table: LWS_ONLINE_TABLE_TWIDDLES at plan creation
+bool online_static_twiddles(int Q, int tw_P, int tw_s, bool force_table);
 
 // Same contract as launch_generic<float> with mode == MODE_ONLINE, as online_plan planned it for this shape.  tw_table_dev: the uploaded
 // online_twiddle_table (table variant: tw_P is its period), else null

@@ -1171,7 +1171,7 @@ template <int Q, int L, bool SERIAL> hipError_t launch_q(const OnlineArgs &a, in
 }
 
 // The shape helpers fill an OnlinePlan (lws_online.h) each for its own layout; online_plan picks one.  The environment switches
-// reach them as arguments: online_plan reads them.
+// reach them as arguments: online_plan takes them from the call's snapshot.
 OnlinePlan shape_of(int F, int T, int L, int Q, int Qp, int LA, int n_thr) {
     OnlinePlan sh{};
     sh.layout = 2;
@@ -1304,18 +1304,18 @@ template <int Q> hipError_t launch_plan(const OnlinePlan &pl, const OnlineArgs &
 
 }  // namespace
 
-// (LWS_ONLINE_TABLE_TWIDDLES=1, read when the plan is made: the table variant also where the static one would do -- comparison runs)
-bool online_static_twiddles(int Q, int tw_P, int tw_s) {
-    return tw_P == Q && tw_s == 1 && (Q == 2 || Q == 4 || Q == 8) && lws::env_int("LWS_ONLINE_TABLE_TWIDDLES", 0) != 1;
+// (force_table: LWS_ONLINE_TABLE_TWIDDLES as plan creation read it -- the table variant also where the static one would do, comparison runs)
+bool online_static_twiddles(int Q, int tw_P, int tw_s, bool force_table) {
+    return tw_P == Q && tw_s == 1 && (Q == 2 || Q == 4 || Q == 8) && !force_table;
 }
 
 // tw_P, tw_s: the common twiddle structure of the three tensors (online_twiddle), 0 if they have none.  Tensors of Qp = N rows
 // (general weights) are served through their first Q rows' base weights like summarised ones.
-// `table`: the plan's decision (latched when it was made: it uploaded the table or it did not), never re-read from the environment
-OnlinePlan online_plan(int F, int T, int L, int Q, int Qp, int LA, int n_thr, int update, int tw_P, int tw_s, bool table) {
-    // the switches of this engine, read here and nowhere else
-    const bool serial = lws::env_int("LWS_ONLINE_SERIAL_TAPS", 0) == 1;   // verification only, see k_online
-    const int lag_plus = lws::env_int("LWS_ONLINE_LAG_PLUS", 0), forced = lws::env_int("LWS_ONLINE_LAYOUT", 0);
+// `table`: the plan's decision (latched when it was made: it uploaded the table or it did not), never taken from a later call's switches
+OnlinePlan online_plan(const Switches &sw, int F, int T, int L, int Q, int Qp, int LA, int n_thr, int update, int tw_P, int tw_s, bool table) {
+    // the switches of this engine, used here and nowhere else (the launcher follows the plan)
+    const bool serial = sw.online_serial_taps;   // verification only, see k_online
+    const int lag_plus = sw.online_lag_plus, forced = sw.online_layout;
     const bool eighth_turns = tw_P == Q && tw_s == 1 && (Q == 2 || Q == 4 || Q == 8);
     // (no structure; or one that needs a table the plan does not have, e.g. Q > 8)
     if (update != 2 || tw_P < 1 || (!table && !eighth_turns)) return OnlinePlan{};

@@ -8,7 +8,7 @@ namespace lws {
 // sweeps in flight need fit the LDS as fp64 rows (frames of up to ~600 bins); otherwise the caller uses the generic engine.
 bool online64_supports(int F, int T, int L, int Q, int Qp, int LA, int n_thr, int update);
 // Same contract and the same BITS as launch_generic<double> with mode == MODE_ONLINE.  one_wave: the one-wave kernel instead of the
-// two-wave one (comparison runs: LWS_ONLINE64_ONE_WAVE, read by the engine chooser)
-hipError_t launch_online64(const GenericArgs<double> &a, int B, bool one_wave, hipStream_t stream);
+// two-wave one (comparison runs: LWS_ONLINE64_ONE_WAVE, the engine chooser's decision); stress: LWS_ONLINE64_STRESS of the call
+hipError_t launch_online64(const GenericArgs<double> &a, int B, bool one_wave, int stress, hipStream_t stream);
 
 }  // namespace lws

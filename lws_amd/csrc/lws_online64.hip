@@ -492,7 +492,7 @@ bool online64_supports(int F, int T, int Lplan, int Q, int Qp, int LA, int n_thr
     return update == 2 && shape64(F, T, Lplan, Q, Qp, LA, n_thr).ok;
 }
 
-hipError_t launch_online64(const GenericArgs<double> &g, int B, bool one_wave, hipStream_t stream) {
+hipError_t launch_online64(const GenericArgs<double> &g, int B, bool one_wave, int stress, hipStream_t stream) {
     const Shape64 sh = shape64(g.F, g.T, g.L, g.Q, g.Qp, g.LA, g.n_thr);
     if (!sh.ok || g.update != 2 || g.mode != MODE_ONLINE) return hipErrorInvalidValue;
     if (B <= 0) return hipSuccess;
@@ -500,7 +500,7 @@ hipError_t launch_online64(const GenericArgs<double> &g, int B, bool one_wave, h
     a.state = g.state; a.amp = g.amp; a.thr = g.thr;
     for (int i = 0; i < 3; ++i) a.w[i] = g.w[i].w;
     a.F = g.F; a.T = g.T; a.n_thr = g.n_thr; a.LA = g.LA; a.NSW = sh.NSW; a.DS = sh.DS; a.NWR = sh.NWR; a.NPS = sh.NPS;
-    a.stress = env_int("LWS_ONLINE64_STRESS", 0);
+    a.stress = stress;
     switch (g.Q) {
     case 2: return launch_q<2>(a, B, sh.lds, sh.amp_lds, one_wave, stream);
     case 3: return launch_q<3>(a, B, sh.lds, sh.amp_lds, one_wave, stream);

@@ -47,9 +47,8 @@ constexpr int SKW = 8;       // steps between consecutive frames
 constexpr int MARG = 96;     // rows before / after the skewed state that prefetches may touch
 constexpr int PFD = 4;       // steps a global load is issued ahead of its use (2: no faster)
 constexpr int LDS_ROWS = 160;
-// spectrograms that go through the skewed scratch at a time (config 2's frames: 7.6 GB for 1024); LWS_S64_CHUNK: for tests
-inline int chunk_size() {
-    const int c = env_int("LWS_S64_CHUNK", 1024);
+// spectrograms that go through the skewed scratch at a time (config 2's frames: 7.6 GB for 1024); LWS_S64_CHUNK (`c`): for tests
+inline int chunk_size(int c) {
     return c >= 2 ? c & ~1 : 1024;   // (even: two spectrograms may share a workgroup)
 }
 constexpr uint64_t MASK_Q4 = 0xfd7fc3, MASK_Q2 = 0x5c3, MASK_ALL = ~0ull;   // non-zero weights of the default (sqrt-Hann) windows   // ring rows of 1 KB that fit the LDS
@@ -554,10 +553,10 @@ bool sys64_supports(int F, int T, int L, int Q, int update, const WeightStructur
     return ws.quarter_turns;
 }
 
-size_t sys64_bytes(int B, int F, int T, int Q, size_t *amp_bytes) {
+size_t sys64_bytes(int B, int F, int T, int Q, int chunk, size_t *amp_bytes) {
     int ns = 0;
     const Geom g = choose_geom(F, T, Q, &ns);
-    const size_t wgs = (std::min(B, chunk_size()) + g.rw / g.nls - 1) / (g.rw / g.nls);
+    const size_t wgs = (std::min(B, chunk_size(chunk)) + g.rw / g.nls - 1) / (g.rw / g.nls);
     if (amp_bytes) *amp_bytes = wgs * g.rows * g.rw * sizeof(double);
     return wgs * g.rows * g.rw * sizeof(double2);
 }
@@ -624,7 +623,7 @@ hipError_t run_passes(S64Args a, const double *W, int NS, int wps, int n_thr, in
 }
 }  // namespace
 
-hipError_t launch_sys64(const GenericArgs<double> &ga, const double *W_host, const WeightStructure &ws, int B, void *gs, void *gamp, hipStream_t stream, int *launches,
+hipError_t launch_sys64(const GenericArgs<double> &ga, const double *W_host, const WeightStructure &ws, int B, int chunk, void *gs, void *gamp, hipStream_t stream, int *launches,
                         hipEvent_t ev0, hipEvent_t ev1) {
     if (B <= 0 || ga.n_thr <= 0) return hipSuccess;
     const int F = ga.F, T = ga.T, Q = ga.Q, Tp = T + 2 * (Q - 1);
@@ -639,7 +638,7 @@ hipError_t launch_sys64(const GenericArgs<double> &ga, const double *W_host, con
     if (ev0) (void)hipEventRecord(ev0, stream);
     int n_all = 0;
     // a batch larger than the scratch was sized for (sys64_bytes: at most CHUNK spectrograms) goes through it chunk by chunk
-    const int CHUNK = chunk_size();
+    const int CHUNK = chunk_size(chunk);
     for (int b0 = 0; b0 < B; b0 += CHUNK) {
         const int Bc = std::min(CHUNK, B - b0);
         const size_t wgs = (Bc + g.rw / g.nls - 1) / (g.rw / g.nls);

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "lws_switches.h"
 #include "lws_systolic_builds.h"
 #include "lws_weights.h"
 
@@ -23,6 +24,7 @@ struct SystolicPlan {
     bool h16 = false;         // fp16-complex storage of the skewed layout (LWS_STORAGE_FP16)
     void *thr_chunk = nullptr;   // dense threshold table of one launch of a schedule longer than one launch holds (MAX_ITERS)
     size_t thr_chunk_cap = 0;
+    const Switches *sw = nullptr;   // the owner's snapshot (lws_capi.hip refreshes it in every public call): LWS_SYSTOLIC_NWG, _SPIN_LIMIT, _STRESS, _ROLEMAP
 };
 
 // Upload tables for the (host, complex128 interleaved) weight tensors W, of the structure ws (lws_weights.h), that the

@@ -2682,7 +2682,7 @@ hipError_t prepare(SystolicPlan &sp, int B, int T, int iters, Geom &g) {
     // each workgroup trails its producer by NSLOTS*LAG + 56 rows, and the first one starts its next pass G rows after
     // its previous one: the lags around the ring must fit into one pass
     const int ring_max = g.G / (NSLOTS * LAG + 96);
-    const int forced = lws::env_int("LWS_SYSTOLIC_NWG", 0);
+    const int forced = sp.sw->systolic_nwg;
     auto pick = [&](int nb) {
         int n = nb > 0 ? n_cu / nb : 1;
         if (n > n_pass_max) n = n_pass_max;
@@ -2739,9 +2739,9 @@ hipError_t launch_update(SystolicPlan &sp, const Geom &g, int wsel, const float 
     a.n_iters = n_it;
     a.T = T; a.Tp = g.Tp; a.TpPad = g.TpPad; a.Kr = g.Kr; a.G = g.G; a.C = F - 1;
     a.nwg = nwg; a.progress = progress; a.err = g.err; a.gate = gate;
-    a.spin_limit = lws::env_int("LWS_SYSTOLIC_SPIN_LIMIT", 1 << 21);   // polls (of ~0.2 us) before a workgroup gives up on its producer
-    a.stress = lws::env_int("LWS_SYSTOLIC_STRESS", 0);
-    a.rolemap = lws::env_int("LWS_SYSTOLIC_ROLEMAP", 0);
+    a.spin_limit = sp.sw->systolic_spin_limit;   // polls (of ~0.2 us) before a workgroup gives up on its producer
+    a.stress = sp.sw->systolic_stress;
+    a.rolemap = sp.sw->systolic_rolemap;
     a.tw_table = tb->tw_dev; a.tw_P = tb->tw_P > 0 ? tb->tw_P : 1; a.tw_invP = 1.0f / (float)a.tw_P;
     for (int r = 0; r < 8; ++r) {
         unsigned ur, ui;

@@ -635,7 +635,7 @@ __global__ void __launch_bounds__(1024) k_team_sweeps(GenericArgs<real> a, TeamG
 int pow2_floor(int x) { int p = 1; while (2 * p <= x) p *= 2; return p; }
 
 // lanes per team, units per step and sweeps in flight for a stage; G = 0: not worth a team
-TeamGeom geometry(int mode, int F, int T, int L, int Q, int LA, int n_thr) {
+TeamGeom geometry(const Switches &sw, int mode, int F, int T, int L, int Q, int LA, int n_thr) {
     TeamGeom tg{0, 0, 0};
     const int sk = L + 1, D = Q * sk;
     if (mode == MODE_ONLINE) {
@@ -655,15 +655,15 @@ TeamGeom geometry(int mode, int F, int T, int L, int Q, int LA, int n_thr) {
     if (tg.nunits <= 0 || tg.nunits > 512) return TeamGeom{0, 0, 0};
     int G = pow2_floor(1024 / tg.nunits);
     if (G > 64) G = 64;
-    const int lanes = env_int("LWS_TEAM_LANES", 0);   // comparison runs: at most this many lanes per bin (1: the generic engine's order of terms)
-    if (lanes >= 1 && lanes < G) G = pow2_floor(lanes);
+    // LWS_TEAM_LANES (comparison runs): at most this many lanes per bin (1: the generic engine's order of terms)
+    if (sw.team_lanes >= 1 && sw.team_lanes < G) G = pow2_floor(sw.team_lanes);
     tg.G = G;
     return tg;
 }
 
 // the online ring: rows, what goes into LDS, bytes; bytes = 0: does not fit (the state stays in memory: k_team_online)
 template <typename real>
-RingGeom ring_geometry(const TeamGeom &tg, int F, int L, int Q, int Qp, int LA, int n_thr) {
+RingGeom ring_geometry(const Switches &sw, const TeamGeom &tg, int F, int L, int Q, int Qp, int LA, int n_thr) {
     RingGeom rg{};
     const int per = n_thr + 1, Np = F + 2 * L, RQ = Q * (L + 1), NT = L + (Q - 1) * (2 * L + 1);
     rg.DM = (tg.nsl + per - 2) / per;
@@ -683,37 +683,37 @@ RingGeom ring_geometry(const TeamGeom &tg, int F, int L, int Q, int Qp, int LA, 
     }
     rg.bytes = (unsigned)off;
     rg.fits = 1;                                                // (... whether or not LWS_TEAM_NO_RING sends the call to the other kernel)
-    if (env_int("LWS_TEAM_NO_RING", 0)) rg.bytes = 0;          // comparison runs: the state stays in memory
-    rg.poison = (env_int("LWS_TEAM_DBG_POISON", 0) && rg.bytes && rg.bytes + 16384 <= cap) ? 1 : 0;
+    if (sw.team_no_ring) rg.bytes = 0;                         // comparison runs: the state stays in memory
+    rg.poison = (sw.team_dbg_poison && rg.bytes && rg.bytes + 16384 <= cap) ? 1 : 0;
     return rg;
 }
 
 }  // namespace
 
-bool team_ordered_fits(int F, int T, int L, int Q, int LA, int n_thr, bool fp64) {
-    const TeamGeom tg = geometry(MODE_ONLINE, F, T, L, Q, LA, n_thr);
+bool team_ordered_fits(const Switches &sw, int F, int T, int L, int Q, int LA, int n_thr, bool fp64) {
+    const TeamGeom tg = geometry(sw, MODE_ONLINE, F, T, L, Q, LA, n_thr);
     if (tg.G < 1) return false;
     const int NT = L + (Q - 1) * (2 * L + 1), NTP = (NT + 1) | 1;
     const size_t csz = fp64 ? 16 : 8;
     return (size_t)NT * sizeof(Term) + (size_t)tg.nunits * NTP * csz + (size_t)tg.nunits * 32 + 64 <= 160 * 1024;
 }
 
-bool team_supports(int mode, int F, int T, int L, int Q, int Qp, int LA, int n_thr) {
+bool team_supports(const Switches &sw, int mode, int F, int T, int L, int Q, int Qp, int LA, int n_thr) {
     if (mode != MODE_ONLINE && mode != MODE_NOFUTURE) return false;
     if (F < 2 || T < 1 || L < 1 || Q < 2 || Q > 255 || Qp < 1 || n_thr < 1) return false;
     const int NT = L + (Q - 1) * (2 * L + 1);
     if ((size_t)NT * sizeof(Term) > 60 * 1024) return false;
-    return geometry(mode, F, T, L, Q, LA, n_thr).G >= (env_int("LWS_TEAM_LANES", 0) ? 1 : 2);
+    return geometry(sw, mode, F, T, L, Q, LA, n_thr).G >= (sw.team_lanes ? 1 : 2);
 }
 
-bool team_online_in_lds(bool fp64, int F, int T, int L, int Q, int Qp, int LA, int n_thr) {
-    if (!team_supports(MODE_ONLINE, F, T, L, Q, Qp, LA, n_thr)) return false;
-    const TeamGeom tg = geometry(MODE_ONLINE, F, T, L, Q, LA, n_thr);
+bool team_online_in_lds(const Switches &sw, bool fp64, int F, int T, int L, int Q, int Qp, int LA, int n_thr) {
+    if (!team_supports(sw, MODE_ONLINE, F, T, L, Q, Qp, LA, n_thr)) return false;
+    const TeamGeom tg = geometry(sw, MODE_ONLINE, F, T, L, Q, LA, n_thr);
     if (tg.G < 8) return false;
-    return (fp64 ? ring_geometry<double>(tg, F, L, Q, Qp, LA, n_thr) : ring_geometry<float>(tg, F, L, Q, Qp, LA, n_thr)).bytes != 0;
+    return (fp64 ? ring_geometry<double>(sw, tg, F, L, Q, Qp, LA, n_thr) : ring_geometry<float>(sw, tg, F, L, Q, Qp, LA, n_thr)).bytes != 0;
 }
 
-int team_lanes(int mode, int F, int T, int L, int Q, int LA, int n_thr) { return geometry(mode, F, T, L, Q, LA, n_thr).G; }
+int team_lanes(const Switches &sw, int mode, int F, int T, int L, int Q, int LA, int n_thr) { return geometry(sw, mode, F, T, L, Q, LA, n_thr).G; }
 
 namespace {
 template <auto Kernel, typename real>
@@ -726,9 +726,9 @@ hipError_t launch_ring(const GenericArgs<real> &a, const TeamGeom &tg, const Rin
 }  // namespace
 
 template <typename real>
-hipError_t launch_team(const GenericArgs<real> &a, int B, bool ordered, hipStream_t stream) {
+hipError_t launch_team(const Switches &sw, const GenericArgs<real> &a, int B, bool ordered, hipStream_t stream) {
     if (B <= 0) return hipSuccess;
-    TeamGeom tg = geometry(a.mode, a.F, a.T, a.L, a.Q, a.LA, a.n_thr);
+    TeamGeom tg = geometry(sw, a.mode, a.F, a.T, a.L, a.Q, a.LA, a.n_thr);
     if (tg.G < 1) return hipErrorInvalidValue;
     int threads = ((tg.nunits * tg.G + 63) / 64) * 64;
     if (threads > 1024) threads = 1024;
@@ -747,13 +747,13 @@ hipError_t launch_team(const GenericArgs<real> &a, int B, bool ordered, hipStrea
         return hipGetLastError();
     }
     if (a.mode == MODE_ONLINE) {
-        const RingGeom rg = ring_geometry<real>(tg, a.F, a.L, a.Q, a.Qp, a.LA, a.n_thr);
+        const RingGeom rg = ring_geometry<real>(sw, tg, a.F, a.L, a.Q, a.Qp, a.LA, a.n_thr);
         // Fewer, fatter teams: what a step costs beside the taps -- schedule bookkeeping, the team sum, the barrier -- is per WAVE, so
         // the ring kernel wants the smallest team whose lanes keep all their terms' placement in registers (8 terms in fp32, 4 in
         // fp64), not the largest the workgroup has room for: lws(1024,256,L=8) 366 -> 298 ms with 8 lanes a bin instead of 16.  (The
         // kernel that leaves the state in memory runs with the same teams when it stands in for the ring kernel: same bits.)
         int nch = 2;
-        if (rg.fits && !env_int("LWS_TEAM_LANES", 0)) {
+        if (rg.fits && !sw.team_lanes) {
             auto smallest = [&](int nc) { int gp = 1; while (gp * nc < NT) gp *= 2; return gp; };
             int gp = smallest(sizeof(real) == 8 ? 4 : 8);
             if (sizeof(real) == 4) {                                           // (fp32: three chunks in registers if that halves the team
@@ -765,7 +765,7 @@ hipError_t launch_team(const GenericArgs<real> &a, int B, bool ordered, hipStrea
                 threads = ((tg.nunits * tg.G + 63) / 64) * 64;
             } else nch = 2;
         }
-        if (env_int("LWS_TEAM_NCH3", 0) && rg.fits && threads <= 512) nch = 3;   // (tests: the three-chunk kernel whatever the team)
+        if (sw.team_nch3 && rg.fits && threads <= 512) nch = 3;   // (tests: the three-chunk kernel whatever the team)
         if (rg.bytes) {
             if (nch == 3) return rg.wl ? launch_ring<&k_team_online_ring<real, true, 3>>(a, tg, rg, B, threads, stream)
                                        : launch_ring<&k_team_online_ring<real, false, 3>>(a, tg, rg, B, threads, stream);
@@ -777,7 +777,7 @@ hipError_t launch_team(const GenericArgs<real> &a, int B, bool ordered, hipStrea
     return hipGetLastError();
 }
 
-template hipError_t launch_team<float>(const GenericArgs<float> &, int, bool, hipStream_t);
-template hipError_t launch_team<double>(const GenericArgs<double> &, int, bool, hipStream_t);
+template hipError_t launch_team<float>(const Switches &, const GenericArgs<float> &, int, bool, hipStream_t);
+template hipError_t launch_team<double>(const Switches &, const GenericArgs<double> &, int, bool, hipStream_t);
 
 }  // namespace lws

@@ -174,3 +174,36 @@ def test_host_chunking_follows_the_engine(fshift, chunks, name, monkeypatch, cap
     err = capfd.readouterr().err
     assert ("pool up, chunks: %d\n" % chunks) in err, err
     plan.close()
+
+
+def test_a_switch_binds_per_call_or_at_plan_creation(monkeypatch):
+    """When a switch binds (lws_switches.h: CALL / CREATE).  LWS_NO_TEAM is read by every call: one plan follows the environment from
+    call to call.  LWS_NO_SYSTOLIC is read by plan creation: what it decided stays with the plan whatever the environment says later."""
+    thr = lws_amd.get_thresholds(ITERS, 1.0, 0.1, 1)
+    S = spectrograms(513, 11)
+    monkeypatch.delenv("LWS_NO_TEAM", raising=False)
+    monkeypatch.delenv("LWS_NO_SYSTOLIC", raising=False)
+    cfg = lws_amd.lws(1024, 64, L=5)                       # (the nf_q16_team row)
+    plan = _capi.Plan(513, cfg.W, cfg.W_ai, cfg.W_af)
+    names = []
+    for no_team in (None, "1", None):
+        if no_team is None:
+            monkeypatch.delenv("LWS_NO_TEAM", raising=False)
+        else:
+            monkeypatch.setenv("LWS_NO_TEAM", no_team)
+        with quiet():
+            plan.nofuture(S, thr)
+        names.append(plan.last_kernel()["name"])
+    plan.close()
+    assert names == ["team_nofuture_fp32", "generic_fp32", "team_nofuture_fp32"]
+
+    cfg = lws_amd.lws(1024, 256, L=5)
+    early = _capi.Plan(513, cfg.W, cfg.W_ai, cfg.W_af)     # created with LWS_NO_SYSTOLIC unset
+    monkeypatch.setenv("LWS_NO_SYSTOLIC", "1")
+    late = _capi.Plan(513, cfg.W, cfg.W_ai, cfg.W_af)
+    early.batch(S, thr)
+    late.batch(S, thr)
+    names = (early.last_kernel()["name"], late.last_kernel()["name"])
+    early.close()
+    late.close()
+    assert names == ("systolic_q4_l5_hann", "band_fp32")

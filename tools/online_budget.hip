@@ -45,7 +45,7 @@ int main(int argc, char **argv) {
     for (int s = 0; s < 3; ++s) { g.w[s].w = dw + s * Q * Q * K1; g.w[s].flag = nullptr; }
     g.F = F; g.T = T; g.L = L; g.Q = Q; g.Qp = Q; g.n_thr = iters; g.LA = LA; g.update = 2; g.qdiv = 4.f; g.mode = lws::MODE_ONLINE;
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    const lws::OnlinePlan pl = lws::online_plan(F, T, L, Q, Q, LA, iters, 2, Q, 1, false);
+    const lws::OnlinePlan pl = lws::online_plan(lws::read_switches(), F, T, L, Q, Q, LA, iters, 2, Q, 1, false);
     float best = 1e30f;
     for (int rep = 0; rep < reps; ++rep) {
         CK(hipMemcpy(ds, ds0, n * 8, hipMemcpyDeviceToDevice));

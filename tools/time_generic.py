@@ -11,5 +11,5 @@ def t(fsize, fshift, B, T, iters, precision="fp32", **kw):
     for _ in range(2):
         plan.batch_dev(S.data_ptr(), B, T, thr); torch.cuda.synchronize(); ms.append(plan.last_kernel()["ms"])
     n = B*T*F*iters
-    print("ITEMS=%s %5d/%4d F=%4d %s %-20s %s  ps/bin-sweep %.1f" % (os.environ.get("LWS_GENERIC_ITEMS"), fsize, fshift, F, precision, plan.last_kernel()["name"], " ".join("%.1f" % m for m in ms), min(ms)*1e9/n), flush=True)
+    print("%5d/%4d F=%4d %s %-20s %s  ps/bin-sweep %.1f" % (fsize, fshift, F, precision, plan.last_kernel()["name"], " ".join("%.1f" % m for m in ms), min(ms)*1e9/n), flush=True)
 t(1024,256,256,500,100); t(1024,256,256,500,100,"fp64"); t(1000,200,256,500,40); t(1024,128,256,500,40)
