@@ -37,29 +37,6 @@ template <typename real> struct cx;
 template <> struct cx<float>  { using type = float2; };
 template <> struct cx<double> { using type = double2; };
 
-#ifdef __HIPCC__
-// |a| of a weighted sum about to be re-projected on its target magnitude (lwslib.cpp:356-360: a -> target a / |a|).  In fp32 a sum of
-// data near 1e-20 squares to a denormal or to zero -- the bin is then left alone as if its neighbourhood were silent -- and one near
-// 1e+20 to infinity -- the bin is then written as zero.  Such a sum is first multiplied by the power of two that brings its larger
-// component to [1, 2) (exact; the quotient a / |a| does not see it), so that "|a| > 0" keeps its meaning and the result stays finite
-// for any normal fp32 data.  A sum whose square is between 1e-30 and 1e+30 -- any sum of data at ordinary scales -- goes through
-// unchanged: the same operations on the same values as before, no bit moves.  fp64 sums have the range as they are.
-template <typename real, typename C> __device__ __forceinline__ real rescued_norm(C &a) {
-    real m2 = a.x * a.x + a.y * a.y;
-    if constexpr (sizeof(real) == 4) {
-        if (!(m2 >= 1e-30f && m2 <= 1e30f)) {
-            const float big = fmaxf(fabsf(a.x), fabsf(a.y));
-            const unsigned e = (__float_as_uint(big) >> 23) & 0xffu;
-            // (a zero or denormal component pair stays as it is: m2 is 0 again and the bin is left alone; infinities and NaN too)
-            const float s = (e == 0u || e == 0xffu) ? 1.0f : __uint_as_float((e >= 254u ? 1u : 254u - e) << 23);
-            a.x *= s; a.y *= s;
-            m2 = a.x * a.x + a.y * a.y;
-        }
-    }
-    return sqrt(m2);
-}
-#endif
-
 // What a sweep does, in the reference's terms.
 //   BATCH    : LWSQ2/LWSQ4/LWSanyQ/LWSfractionalQ            (lwslib.cpp:72-467)
 //   NOFUTURE : NoFuture_LWS{Q2,anyQ,fractionalQ}              (lwslib.cpp:473-535,620-764)

@@ -17,28 +17,12 @@
 // This kernel is the reference-semantics workhorse (and the fp64 parity anchor); the fast path for
 // the headline batch workload is the systolic kernel in lws_systolic.hip.
 #include "lws_common.h"
+#include "lws_bin.h"
+#include "lws_online_unit.h"
 
 #include <type_traits>
 
 namespace lws {
-
-// a += w*b + conj(w)*c in the grouped form of lwslib.cpp:310-311: cancels exactly when c == conj(b)
-// (Hermitian images / real input), which keeps ill-conditioned bins in step with the CPU arithmetic.
-template <typename real, typename C>
-__device__ __forceinline__ void pair(C &a, const C w, const C b, const C c) {
-    a.x += w.x * (b.x + c.x) - w.y * (b.y - c.y);
-    a.y += w.x * (b.y + c.y) + w.y * (b.x - c.x);
-}
-template <typename real, typename C>
-__device__ __forceinline__ void mac(C &a, const C w, const C s) {  // a += w * s
-    a.x += w.x * s.x - w.y * s.y;
-    a.y += w.x * s.y + w.y * s.x;
-}
-template <typename real, typename C>
-__device__ __forceinline__ void macc(C &a, const C w, const C s) {  // a += conj(w) * s
-    a.x += w.x * s.x + w.y * s.y;
-    a.y += w.x * s.y - w.y * s.x;
-}
 
 // The local weighted sum of one bin (no write): LWSanyQ (lwslib.cpp:297-354), NoFuture_LWSanyQ
 // (634-671) and Asym_UpdatePhaseanyQ (1157-1253) in one body; `centre` / `two_sided` are the
@@ -80,23 +64,23 @@ __device__ __forceinline__ typename cx<real>::type accumulate_v(const View nb, i
     if (centre) {
         if (add_self) { const C s0 = nb.at(0, 0); a.x += s0.x / qdiv; a.y += s0.y / qdiv; }
         for (int k = 1; k <= L; ++k)
-            if (fa[k]) pair<real>(a, wa[k], nb.at(0, -k), nb.at(0, k));
+            if (fa[k]) pair(a, wa[k], nb.at(0, -k), nb.at(0, k));
     }
     for (int r = 1; r < Q; ++r) {
         const int u = r * K1;
         const bool both = r < two_sided;
         if (fa[u]) {
-            if (both) pair<real>(a, wa[u], nb.at(-r, 0), nb.at(r, 0));
-            else mac<real>(a, wa[u], nb.at(-r, 0));
+            if (both) pair(a, wa[u], nb.at(-r, 0), nb.at(r, 0));
+            else mac(a, wa[u], nb.at(-r, 0));
         }
         for (int k = 1; k <= L; ++k) {
             if (fa[u + k]) {
-                if (both) pair<real>(a, wa[u + k], nb.at(-r, -k), nb.at(r, -k));
-                else mac<real>(a, wa[u + k], nb.at(-r, -k));
+                if (both) pair(a, wa[u + k], nb.at(-r, -k), nb.at(r, -k));
+                else mac(a, wa[u + k], nb.at(-r, -k));
             }
             if (fb[u + k]) {
-                if (both) pair<real>(a, wb[u + k], nb.at(r, k), nb.at(-r, k));
-                else macc<real>(a, wb[u + k], nb.at(-r, k));
+                if (both) pair(a, wb[u + k], nb.at(r, k), nb.at(-r, k));
+                else macc(a, wb[u + k], nb.at(-r, k));
             }
         }
     }
@@ -125,18 +109,7 @@ __device__ __forceinline__ void update_bin(typename cx<real>::type *S, const rea
     if (!(target > thr)) return;
     C *ctr = S + idx;
     C a = accumulate<real>(ctr, c, centre, two_sided, ws, Np, L, Q, Qp, add_self, qdiv, mk);
-    const real mag = rescued_norm<real>(a);       // (rescales a sum that fp32 cannot square: lws_common.h)
-    if (!(mag > 0)) return;
-    C v;
-    v.x = a.x * target / mag;
-    v.y = a.y * target / mag;
-    ctr[0] = v;
-    // keep the Hermitian images in the pad columns in sync (lwslib.cpp:362-367)
-    const int nyq = F + L - 1;
-    C vc;
-    vc.x = v.x; vc.y = -v.y;
-    if (n >= L + 1 && n < 2 * L + 1) S[(size_t)m_ext * Np + 2 * L - n] = vc;
-    else if (n >= F - 1 && n < nyq) S[(size_t)m_ext * Np + 2 * nyq - n] = vc;
+    finish_bin<real>(S, idx, n, F, L, a, target);
 }
 
 // One bin of NoFuture_LWSQ4 as shipped (lwslib.cpp:550-613): flat offset (m-r)*Np + 2n +- k.
@@ -162,21 +135,11 @@ __device__ __forceinline__ void update_bin_nfq4(typename cx<real>::type *S, cons
             if (fa[u + k]) {
                 C hi = p[k];
                 hi.x *= sgn; hi.y *= sgn;
-                pair<real>(a, wa[u + k], p[-k], hi);
+                pair(a, wa[u + k], p[-k], hi);
             }
-        if (fa[u]) mac<real>(a, wa[u], p[0]);
+        if (fa[u]) mac(a, wa[u], p[0]);
     }
-    const real mag = rescued_norm<real>(a);       // (rescales a sum that fp32 cannot square: lws_common.h)
-    if (!(mag > 0)) return;
-    C v;
-    v.x = a.x * target / mag;
-    v.y = a.y * target / mag;
-    S[idx] = v;
-    const int nyq = F + L - 1;
-    C vc;
-    vc.x = v.x; vc.y = -v.y;
-    if (n >= L + 1 && n < 2 * L + 1) S[(size_t)m_ext * Np + 2 * L - n] = vc;
-    else if (n >= F - 1 && n < nyq) S[(size_t)m_ext * Np + 2 * nyq - n] = vc;
+    finish_bin<real>(S, idx, n, F, L, a, target);
 }
 
 template <typename real>
@@ -275,9 +238,7 @@ __global__ void __launch_bounds__(1024) k_generic(GenericArgs<real> a) {
     } else {  // MODE_ONLINE: TF_RTISI_LA (lwslib.cpp:1432-1491)
         const int LA = a.LA, per = a.n_thr + 1, rps = LA + 1;
         const long nsweeps = (long)T * per;
-        // sweep s: frame m = s / per; q = s % per.  q == 0: first estimate of frame m from the past
-        // (W_ai, threshold 0, M=1, M0=0).  q >= 1: iteration q-1 over frames max(0,m-LA) .. m, the
-        // look-ahead frames with W (M=count, M0=count+1) and frame m with W_af (M=1, M0=1).
+        // sweep s, frame position j: online_unit (lws_online_unit.h)
         const long t_end = D * (nsweeps - 1) + (long)sk * (T - 1) + F;  // one past the last step
         long s_lo = 0;
         for (long t = 0; t < t_end; ++t) {
@@ -292,23 +253,18 @@ __global__ void __launch_bounds__(1024) k_generic(GenericArgs<real> a) {
             for (int idx = tid; idx < nslots; idx += nthr) {
                 const long s = s_lo + idx / rps;
                 const int j = idx % rps;
-                const int m = (int)(s / per), q = (int)(s % per);
-                int first = m - LA;
-                if (first < 0) first = 0;
-                int rho;
-                if (q == 0) { if (j != 0) continue; rho = m; }
-                else { rho = first + j; if (rho > m) continue; }
-                const long cl = t - D * s - (long)sk * rho;
+                const OnlineUnit un = online_unit(s, j, per, LA, Q);
+                if (!un.valid) continue;
+                const long cl = t - D * s - (long)sk * un.rho;
                 if (cl < 0 || cl >= F) continue;
                 const int c = (int)cl;
-                if (q == 0) {
-                    update_bin<real>(S, amp, rho + Q - 1, c, false, 1, a.w[1], (real)0, F, L, Q, Qp,
+                // (two calls: the first estimate's sum is compiled without its centre and right-hand terms)
+                if (un.q == 0) {
+                    update_bin<real>(S, amp, un.rho + Q - 1, c, false, 1, a.w[1], (real)0, F, L, Q, Qp,
                                      add_self, a.qdiv, mk[1]);
                 } else {
-                    int ts = m - rho + 1;
-                    if (ts > Q) ts = Q;
-                    update_bin<real>(S, amp, rho + Q - 1, c, true, ts, (rho == m) ? a.w[2] : a.w[0],
-                                     thr[q - 1], F, L, Q, Qp, add_self, a.qdiv, (rho == m) ? mk[2] : mk[0]);
+                    update_bin<real>(S, amp, un.rho + Q - 1, c, true, un.ts, a.w[un.wset],
+                                     thr[un.q - 1], F, L, Q, Qp, add_self, a.qdiv, mk[un.wset]);
                 }
             }
             __syncthreads();
@@ -419,7 +375,6 @@ __global__ void __launch_bounds__(1024) k_skew_batch(GenericArgs<real> a, typena
     int lpi = (F - 1) / sk + 1;  // frames that can sit on one hyperplane
     if (lpi > T) lpi = T;
     const int group = a.group < 1 ? 1 : a.group;
-    const int nyq = F + L - 1;
     for (int g0 = 0; g0 < nsweeps; g0 += group) {
         const int ng = (nsweeps - g0 < group) ? nsweeps - g0 : group;
         const int nsteps = F + sk * (T - 1) + D * (ng - 1);
@@ -443,16 +398,7 @@ __global__ void __launch_bounds__(1024) k_skew_batch(GenericArgs<real> a, typena
                 const real target = AW[row * NL + lane];
                 if (!(target > thr[g0 + k])) continue;
                 C acc = accumulate_v<real>(SkewView<C>{SW, row, lane, sk, NL}, c, true, Q, ws, L, Q, Qp, add_self, a.qdiv, mk);
-                const real mag = rescued_norm<real>(acc);     // (rescales a sum that fp32 cannot square: lws_common.h)
-                if (!(mag > 0)) continue;
-                C v;
-                v.x = acc.x * target / mag;
-                v.y = acc.y * target / mag;
-                SW[row * NL + lane] = v;
-                C vc;
-                vc.x = v.x; vc.y = -v.y;            // Hermitian images in the pad columns (lwslib.cpp:362-367)
-                if (n >= L + 1 && n < 2 * L + 1) SW[(row + 2 * (L - n)) * NL + lane] = vc;
-                else if (n >= F - 1 && n < nyq) SW[(row + 2 * (nyq - n)) * NL + lane] = vc;
+                finish_bin<real>(SW + lane, row, n, F, L, acc, target, NL);   // (a column further on is a row further on)
             }
             __syncthreads();
         }

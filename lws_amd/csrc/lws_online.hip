@@ -40,7 +40,9 @@
 // further down (one wave per tap group: the default where it fits).  online_plan chooses between them once per stage and
 // launch_online_lds runs what it chose.
 #include "lws_common.h"
+#include "lws_bin.h"
 #include "lws_online.h"
+#include "lws_online_unit.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -73,14 +75,6 @@ namespace {
 
 constexpr int NW = 16;  // frames in the LDS ring
 
-template <int... Is, typename F_>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, Is...>, F_ &&f) {
-    (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N_, typename F_> __device__ __forceinline__ void static_for(F_ &&f) {
-    static_for_impl(std::make_integer_sequence<int, N_>{}, static_cast<F_ &&>(f));
-}
-
 struct OnlineArgs {
     float2 *state;       // [B][Tp][Np]
     const float *amp;    // [B][Tp][Np]
@@ -97,11 +91,6 @@ struct OnlineArgs {
     const float2 *twt;   // device: [PT + 3][TQ], TQ = 4 (Q <= 4) or 8: row p = tau_0 .. tau_{TQ-1} of bin p (periodic: rows PT .. PT + 2 repeat rows 0 .. 2)
     int PT;              // period of the twiddles in bins
 };
-
-__device__ __forceinline__ void pair(float2 &a, float2 w, float2 b, float2 c) {   // the generic engine's grouped form
-    a.x += w.x * (b.x + c.x) - w.y * (b.y - c.y);
-    a.y += w.x * (b.y + c.y) + w.y * (b.x - c.x);
-}
 
 // a += w * v (cmac_pk) and a += conj(w) * v (cmacc_pk) as packed instructions.  A complex value is an aligned register pair
 // (re, im); "w times v" is
@@ -120,18 +109,6 @@ __device__ __forceinline__ void cmacc_pk(v2f &a, v2f w, v2f v) {
         : "+v"(a) : "v"(w), "v"(v));
 }
 __device__ __forceinline__ v2f as_v2f(float2 x) { return (v2f){x.x, x.y}; }
-
-// sum over the Q adjacent lanes of a group (Q = 4, 8, 16; groups are aligned), in data-parallel-primitive moves
-template <int Q> __device__ __forceinline__ float quad_sum(float v) {
-    auto dpp = [](float x, auto ctrl) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, 0xf, 0xf, true));
-    };
-    v += dpp(v, std::integral_constant<int, 0xB1>());                    // quad_perm [1,0,3,2]
-    if constexpr (Q >= 4) v += dpp(v, std::integral_constant<int, 0x4E>());   // quad_perm [2,3,0,1]
-    if constexpr (Q >= 8) v += dpp(v, std::integral_constant<int, 0x141>());  // row_half_mirror: the other quad of the 8
-    if constexpr (Q >= 16) v += dpp(v, std::integral_constant<int, 0x140>()); // row_mirror: the other half of the 16
-    return v;
-}
 
 // magnitude re-projection (lwslib.cpp:356-360): target / |acc| as target * rsqrt(|acc|^2) with one Newton step (relative
 // error < 2^-22); sums too small to square in fp32 are rescaled first so that "|acc| > 0" keeps the reference's meaning
@@ -195,15 +172,11 @@ __global__ void __launch_bounds__(MAXT) k_online(OnlineArgs a) {
     float gain = 0.f, thr = 0.f;
     v2f w0[K1];                         // W[wset][0][r][k] (side 0) or its conjugate (side 1): see the sums below
     auto setup = [&]() {
-        const int m = s / per, q = s - m * per;
-        const int first = m - LA > 0 ? m - LA : 0;
-        if (q == 0) { valid = (j == 0); rho = m; wset = 1; centre = false; ts = 1; thr = 0.f; }
-        else {
-            rho = first + j; valid = rho <= m; wset = (rho == m) ? 2 : 0; centre = true;
-            ts = m - rho + 1; if (ts > Q) ts = Q;
-            thr = thr_s[q - 1];
-        }
-        valid = valid && lane_used && s < nsweeps;
+        const OnlineUnit un = online_unit(s, j, per, LA, Q);
+        const int m = un.m;
+        rho = un.rho; wset = un.wset; centre = un.centre; ts = un.ts;
+        thr = un.q ? thr_s[un.q - 1] : 0.f;
+        valid = un.valid && lane_used && s < nsweeps;
         tstart = DS * s + SKS * rho;
         t_done = DS * s + SKS * m + NU - 1;     // last step of the sweep (its newest frame's last pair)
         const int e = rho + Q - 1;
@@ -268,17 +241,7 @@ __global__ void __launch_bounds__(MAXT) k_online(OnlineArgs a) {
                         }
                         const int li = ctb + nb;
                         const float target = A[li];
-                        if (target > thr) {
-                            const float mag = sqrtf(acc.x * acc.x + acc.y * acc.y);
-                            if (mag > 0.f) {
-                                const float2 v = make_float2(acc.x * target / mag, acc.y * target / mag);
-                                const float2 vc = make_float2(v.x, -v.y);
-                                S[li] = v;
-                                const int nyq = F + L - 1;     // Hermitian images in the pad columns (lwslib.cpp:362-367)
-                                if (nb >= L + 1 && nb < 2 * L + 1) S[li + 2 * (L - nb)] = vc;
-                                else if (nb >= F - 1 && nb < nyq) S[li + 2 * (nyq - nb)] = vc;
-                            }
-                        }
+                        if (target > thr) finish_bin<float, false>(S, li, nb, F, L, acc, target);   // (the plain square root, where update_bin rescues)
                     }
                 }
             } else {
@@ -314,8 +277,8 @@ __global__ void __launch_bounds__(MAXT) k_online(OnlineArgs a) {
                     float2 o;
                     o.x = fmaf(-tw.y, x.y, tw.x * x.x);
                     o.y = fmaf(tw.y, x.x, tw.x * x.y);
-                    o.x = quad_sum<2 * Q>(o.x);
-                    o.y = quad_sum<2 * Q>(o.y);
+                    o.x = group_sum<2 * Q>(o.x);
+                    o.y = group_sum<2 * Q>(o.y);
                     return o;
                 };
                 const float2 acc_a = assemble(a14, twa);
@@ -636,15 +599,11 @@ __global__ void __launch_bounds__(Online4Waves<Q>::N * 64) k_online4(OnlineArgs 
     v2f wc[K1];                         // projection wave: centre weights W[wset][0][0][k] (zero if the centre frame takes no part)
     v2f wlate = {0.f, 0.f};             // ... and conj W[wset][0][1][L]
     auto setup = [&]() {
-        const int m = s / per, q = s - m * per;
-        const int first = m - LA > 0 ? m - LA : 0;
-        if (q == 0) { valid = (j == 0); rho = m; wset = 1; centre = false; ts = 1; thr = 0.f; }
-        else {
-            rho = first + j; valid = rho <= m; wset = (rho == m) ? 2 : 0; centre = true;
-            ts = m - rho + 1; if (ts > Q) ts = Q;
-            thr = thr_s[q - 1];
-        }
-        valid = valid && lane_used && s < nsweeps;
+        const OnlineUnit un = online_unit(s, j, per, LA, Q);
+        const int m = un.m;
+        rho = un.rho; wset = un.wset; centre = un.centre; ts = un.ts;
+        thr = un.q ? thr_s[un.q - 1] : 0.f;
+        valid = un.valid && lane_used && s < nsweeps;
         tstart = DS * s + SKS * rho;
         t_done = DS * s + SKS * m + NU - 1;     // (even when DS is: SKS is, NU is odd)
         const int e = rho + Q - 1;
@@ -957,17 +916,7 @@ __global__ void __launch_bounds__(Online4Waves<Q>::N * 64) k_online4(OnlineArgs 
                     }
                     const int lj = ctb + nb;
                     const float target = A[lj];
-                    if (target > thr) {
-                        const float mag = sqrtf(acc.x * acc.x + acc.y * acc.y);
-                        if (mag > 0.f) {
-                            const float2 v = make_float2(acc.x * target / mag, acc.y * target / mag);
-                            const float2 vc = make_float2(v.x, -v.y);
-                            S[lj] = v;
-                            const int nyq = F + L - 1;
-                            if (nb >= L + 1 && nb < 2 * L + 1) S[lj + 2 * (L - nb)] = vc;
-                            else if (nb >= F - 1 && nb < nyq) S[lj + 2 * (nyq - nb)] = vc;
-                        }
-                    }
+                    if (target > thr) finish_bin<float, false>(S, lj, nb, F, L, acc, target);   // (the plain square root, where update_bin rescues)
                 }
                 }
                 if (t >= t_done) { s += NSW; setup(); }

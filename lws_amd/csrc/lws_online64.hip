@@ -16,6 +16,8 @@
 //
 // Entry: online64_supports / launch_online64 (lws_online64.h), called by lws_capi.hip: run_stage for MODE_ONLINE of an fp64 plan.
 #include "lws_online64.h"
+#include "lws_bin.h"
+#include "lws_online_unit.h"
 
 #include <algorithm>
 #include <atomic>
@@ -37,14 +39,6 @@ struct Args64 {
     int F, T, n_thr, LA, NSW, DS, NWR, NPS;
     int stress;            // test hook (LWS_ONLINE64_STRESS): the two-wave kernel's waves idle for pseudo-random times inside their half-steps
 };
-
-// a += w b + conj(w) c, the grouped form of lwslib.cpp:310-311 exactly as lws_generic.hip: pair() writes it
-__device__ __forceinline__ void pair(double2 &a, const double2 w, const double2 b, const double2 c) {
-    a.x += w.x * (b.x + c.x) - w.y * (b.y - c.y);
-    a.y += w.x * (b.y + c.y) + w.y * (b.x - c.x);
-}
-
-__device__ __forceinline__ double2 sel(bool c, double2 a, double2 b) { return make_double2(c ? a.x : b.x, c ? a.y : b.y); }
 
 // (Measured and not kept, round 5: four waves sharing out the PRODUCTS of a bin's tap pairs through LDS, wave 0 adding them up in order --
 //  the same bits, the same 440 ms: the counters say one wave issues 1 380 vector instructions a step, 68 % of its time, but spreading the
@@ -81,18 +75,12 @@ __global__ void __launch_bounds__(64) k_online64(Args64 a) {
     int rowL[Q], rowR[Q];               // ring rows (element offsets) of frames rho - rr / rho + rr, per sweep (no division in the step loop)
     bool valid = false, centre = false;
     double thr = 0.0;
-    // sweep s: frame m = s / per, q = s % per.  q == 0: first estimate of frame m from the past (W_ai, threshold 0); q >= 1: iteration
-    // q - 1 over frames max(0, m - LA) .. m, the look-ahead frames with W, frame m with W_af (lwslib.cpp:1432-1491)
     auto setup = [&]() {
-        const int m = s / per, q = s - m * per;
-        const int first = m - LA > 0 ? m - LA : 0;
-        if (q == 0) { valid = (j == 0); rho = m; wset = 1; centre = false; ts = 1; thr = 0.0; }
-        else {
-            rho = first + j; valid = rho <= m; wset = (rho == m) ? 2 : 0; centre = true;
-            ts = m - rho + 1; if (ts > Q) ts = Q;
-            thr = thr_s[q - 1];
-        }
-        valid = valid && lane_used && s < nsweeps;
+        const OnlineUnit un = online_unit(s, j, per, LA, Q);
+        const int m = un.m;
+        rho = un.rho; wset = un.wset; centre = un.centre; ts = un.ts;
+        thr = un.q ? thr_s[un.q - 1] : 0.0;
+        valid = un.valid && lane_used && s < nsweeps;
         tstart = DS * s + SKS * rho;
         t_done = DS * s + SKS * m + NU - 1;
         ctb = ((rho + Q - 1) % NWR) * NPS;
@@ -144,7 +132,7 @@ __global__ void __launch_bounds__(64) k_online64(Args64 a) {
                     const double2 *wb_r = W + wset * Q * Q * K1 + (rowneg * Q + rr) * K1;
                     const bool two = rr < ts;
                     // a frame to the right that is not usable yet contributes a zero: pair(w, b, 0) == w b, pair(w, 0, c) == conj(w) c,
-                    // the one-sided forms of lwslib.cpp:1222-1253 (lws_generic.hip: mac / macc) bit for bit
+                    // the one-sided forms of lwslib.cpp:1222-1253 (mac / macc) bit for bit
                     // (fetched whether usable or not, dropped by a select: `two ? rt[..] : zero` makes the compiler branch around every load)
                     { const double2 rv = rt[0]; pair(acc, wa_r[0], lf[0], sel(two, rv, zero)); }
 #pragma unroll
@@ -156,17 +144,7 @@ __global__ void __launch_bounds__(64) k_online64(Args64 a) {
                 }
                 const int lj = ctb + nb;
                 const double target = AMP_LDS ? A[lj] : target_mem;
-                if (target > thr) {
-                    const double mag = sqrt(acc.x * acc.x + acc.y * acc.y);
-                    if (mag > 0.0) {
-                        const double2 v = make_double2(acc.x * target / mag, acc.y * target / mag);
-                        const double2 vc = make_double2(v.x, -v.y);
-                        S[lj] = v;
-                        const int nyq = F + L - 1;     // Hermitian images in the pad columns (lwslib.cpp:362-367)
-                        if (nb >= L + 1 && nb < 2 * L + 1) S[lj + 2 * (L - nb)] = vc;
-                        else if (nb >= F - 1 && nb < nyq) S[lj + 2 * (nyq - nb)] = vc;
-                    }
-                }
+                if (target > thr) finish_bin<double>(S, lj, nb, F, L, acc, target);
             }
         }
         if (t >= t_done) { s += NSW; setup(); }
@@ -198,11 +176,6 @@ __global__ void __launch_bounds__(64) k_online64(Args64 a) {
 // is formed one and a half steps before the one-wave schedule reads its taps (up to bin c + 8 of the frame one to the left, which that
 // frame's even-bin wave wrote in the first half of this step; up to c + 8 of the previous sweep's frames, 2 DS - 8 r >= 8 bins ahead:
 // shape64 keeps 2 DS >= 8 Q + 2), and reading later-to-be-overwritten values earlier is always safe.
-template <class Fn, int... I> __device__ __forceinline__ void static_for64_impl(Fn &f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class Fn> __device__ __forceinline__ void static_for64(Fn &&f) { static_for64_impl(f, std::make_integer_sequence<int, N>{}); }
-
 template <int Q, bool AMP_LDS, int SPLIT, bool STRESS, int ONCH = 0>
 __global__ void __launch_bounds__(128) k_online64p(Args64 a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -242,15 +215,11 @@ __global__ void __launch_bounds__(128) k_online64p(Args64 a) {
     bool valid = false, centre = false;
     double thr = 0.0;
     auto setup = [&]() {      // as in k_online64
-        const int m = s / per, q = s - m * per;
-        const int first = m - LA > 0 ? m - LA : 0;
-        if (q == 0) { valid = (j == 0); rho = m; wset = 1; centre = false; ts = 1; thr = 0.0; }
-        else {
-            rho = first + j; valid = rho <= m; wset = (rho == m) ? 2 : 0; centre = true;
-            ts = m - rho + 1; if (ts > Q) ts = Q;
-            thr = thr_s[q - 1];
-        }
-        valid = valid && lane_used && s < nsweeps;
+        const OnlineUnit un = online_unit(s, j, per, LA, Q);
+        const int m = un.m;
+        rho = un.rho; wset = un.wset; centre = un.centre; ts = un.ts;
+        thr = un.q ? thr_s[un.q - 1] : 0.0;
+        valid = un.valid && lane_used && s < nsweeps;
         tstart = DS * s + SKS * rho;
         t_done = DS * s + SKS * m + NU - 1;
         ctb = ((rho + Q - 1) % NWR) * NPS;
@@ -307,7 +276,7 @@ __global__ void __launch_bounds__(128) k_online64p(Args64 a) {
         if (cb < 0) return;
         const int nb = cb + L, row = cb % Q, rowneg = (Q - row) % Q;
         if constexpr (LO == NPC) target = AMP_LDS ? A[ctb + nb] : gA[(size_t)(rho + Q - 1) * Np + nb];
-        static_for64<HI - LO>([&](auto ic) {
+        static_for<HI - LO>([&](auto ic) {
             constexpr int I = LO + decltype(ic)::value;
             product(std::integral_constant<int, I>{}, nb, row, rowneg, px[I], py[I]);
         });
@@ -323,24 +292,14 @@ __global__ void __launch_bounds__(128) k_online64p(Args64 a) {
 #pragma unroll
             for (int k = 1; k <= L; ++k) pair(acc, wa[k], ctr[-k], ctr[k]);
         }
-        static_for64<NPC>([&](auto ic) {      // the nearest frames' pairs, formed here
+        static_for<NPC>([&](auto ic) {      // the nearest frames' pairs, formed here
             double tx, ty;
             product(ic, nb, row, (Q - row) % Q, tx, ty);
             acc.x += tx; acc.y += ty;
         });
-        static_for64<NP - NPC>([&](auto ic) { constexpr int I = NPC + decltype(ic)::value; acc.x += px[I]; acc.y += py[I]; });
+        static_for<NP - NPC>([&](auto ic) { constexpr int I = NPC + decltype(ic)::value; acc.x += px[I]; acc.y += py[I]; });
         const int lj = ctb + nb;
-        if (target > thr) {
-            const double mag = sqrt(acc.x * acc.x + acc.y * acc.y);
-            if (mag > 0.0) {
-                const double2 v = make_double2(acc.x * target / mag, acc.y * target / mag);
-                const double2 vc = make_double2(v.x, -v.y);
-                S[lj] = v;
-                const int nyq = F + L - 1;
-                if (nb >= L + 1 && nb < 2 * L + 1) S[lj + 2 * (L - nb)] = vc;
-                else if (nb >= F - 1 && nb < nyq) S[lj + 2 * (nyq - nb)] = vc;
-            }
-        }
+        if (target > thr) finish_bin<double>(S, lj, nb, F, L, acc, target);
     };
     auto advance = [&](int t) { if (t >= t_done) { s += NSW; setup(); } };     // the unit's state becomes that of step t + 1
 #define O64_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")

@@ -33,6 +33,7 @@
 //
 // Entry: launch_sys64 (lws_sys64.h), called by lws_capi.hip:run_stage for MODE_BATCH of an fp64 plan.
 #include "lws_sys64.h"
+#include "lws_bin.h"   // sel
 
 #include <algorithm>
 #include <cmath>
@@ -113,7 +114,6 @@ template <int Q> __host__ __device__ constexpr int quarter_turns(int row, int r)
 }
 
 __device__ __forceinline__ double2 cj(double2 v) { v.y = -v.y; return v; }
-__device__ __forceinline__ double2 sel(bool c, double2 a, double2 b) { double2 r; r.x = c ? a.x : b.x; r.y = c ? a.y : b.y; return r; }
 
 // LDS writes of this step complete, then everybody meets.  (Not __syncthreads(): that waits for the global prefetches too.)
 // the order of the independent parts of a step is chosen in the source (the bin's dependent chain interleaved with the taps of

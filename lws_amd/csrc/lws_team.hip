@@ -23,6 +23,8 @@
 // engine's bits).  k_team_sweeps: no-future sweeps.  Pins: LWS_TEAM_LANES=1 makes every kernel add in the generic engine's order (its
 // bits); tools/stress_team.py compares random shapes bit for bit; LWS_TEAM_DBG_POISON=1 starts the ring kernel's LDS as NaNs.
 #include "lws_team.h"
+#include "lws_bin.h"
+#include "lws_online_unit.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -31,12 +33,6 @@ namespace lws {
 namespace {
 
 template <typename real> struct Chunk { static constexpr int N = sizeof(real) == 8 ? 4 : 8; };   // terms of a lane whose loads are in flight together
-
-template <typename real, typename C>
-__device__ __forceinline__ void pair(C &a, const C w, const C b, const C c) {   // lws_generic.hip: pair
-    a.x += w.x * (b.x + c.x) - w.y * (b.y - c.y);
-    a.y += w.x * (b.y + c.y) + w.y * (b.x - c.x);
-}
 
 // term table entry: {offset of b, offset of c (elements, from the bin), weight index in its row,
 //                    r | negrow << 8 | (what !both removes: 1 = c, 2 = b) << 9 | centre << 11}
@@ -125,7 +121,7 @@ __device__ __forceinline__ void team_bin(typename cx<real>::type *S, const real 
 #pragma unroll
             for (int i = 0; i < CH; ++i) {
                 C t = a;
-                pair<real>(t, w[i], vb[i], vc[i]);
+                pair(t, w[i], vb[i], vc[i]);
                 a = live[i] ? t : a;
             }
         }
@@ -139,7 +135,8 @@ __device__ __forceinline__ void team_bin(typename cx<real>::type *S, const real 
         }
     }
     if (act && g == 0) {
-        const real mag = rescued_norm<real>(a);       // (rescales a sum that fp32 cannot square: lws_common.h)
+        // (finish_bin of lws_bin.h, spelt out: with the call k_team_online runs lws(1024,64) in 2368-2374 ms against 2357-2365)
+        const real mag = rescued_norm<real>(a);
         if (mag > 0) {
             C v;
             v.x = a.x * target / mag;
@@ -189,22 +186,13 @@ __global__ void __launch_bounds__(1024) k_team_online(GenericArgs<real> a, TeamG
     auto setup = [&]() {
         valid = false;
         if (s >= nsweeps) { s_end = t_end; return; }
-        const int m = (int)(s / per), q = (int)(s - (long)m * per);
-        s_end = D * s + (long)sk * m + F - 1;                // last step of the sweep (its last frame is m)
-        int first = m - LA;
-        if (first < 0) first = 0;
-        int rho;
-        if (q == 0) { if (j != 0) return; rho = m; }        // first estimate of frame m from the past: W_ai, threshold 0
-        else { rho = first + j; if (rho > m) return; }
+        const OnlineUnit un = online_unit(s, j, per, LA, Q);
+        s_end = D * s + (long)sk * un.m + F - 1;             // last step of the sweep (its last frame is m)
+        if (!un.valid) return;
         valid = true;
-        t0 = D * s + (long)sk * rho;
-        m_ext = rho + Q - 1;
-        if (q == 0) { centre = false; two_sided = 1; wsel = 1; th = 0; }
-        else {
-            int ts = m - rho + 1;
-            if (ts > Q) ts = Q;
-            centre = true; two_sided = ts; wsel = (rho == m) ? 2 : 0; th = thr[q - 1];
-        }
+        t0 = D * s + (long)sk * un.rho;
+        m_ext = un.rho + Q - 1;
+        centre = un.centre; two_sided = un.ts; wsel = un.wset; th = un.q ? thr[un.q - 1] : (real)0;
     };
     setup();
     for (long t = 0; t < t_end; ++t) {
@@ -259,22 +247,13 @@ __global__ void __launch_bounds__(1024) k_team_online_ordered(GenericArgs<real> 
     auto setup = [&]() __attribute__((always_inline)) {
         valid = false;
         if (s >= nsweeps) { s_end = t_end; return; }
-        const int m = (int)(s / per), q = (int)(s - (long)m * per);
-        s_end = D * s + (long)sk * m + F - 1;
-        int first = m - LA;
-        if (first < 0) first = 0;
-        int rho;
-        if (q == 0) { if (j != 0) return; rho = m; }
-        else { rho = first + j; if (rho > m) return; }
+        const OnlineUnit un = online_unit(s, j, per, LA, Q);
+        s_end = D * s + (long)sk * un.m + F - 1;
+        if (!un.valid) return;
         valid = true;
-        t0 = D * s + (long)sk * rho;
-        m_ext = rho + Q - 1;
-        if (q == 0) { centre = false; two_sided = 1; wsel = 1; th = 0; }
-        else {
-            int ts = m - rho + 1;
-            if (ts > Q) ts = Q;
-            centre = true; two_sided = ts; wsel = (rho == m) ? 2 : 0; th = thr[q - 1];
-        }
+        t0 = D * s + (long)sk * un.rho;
+        m_ext = un.rho + Q - 1;
+        centre = un.centre; two_sided = un.ts; wsel = un.wset; th = un.q ? thr[un.q - 1] : (real)0;
     };
     setup();
     for (long t = 0; t < t_end; ++t) {
@@ -320,7 +299,7 @@ __global__ void __launch_bounds__(1024) k_team_online_ordered(GenericArgs<real> 
                 for (int i = 0; i < CH; ++i) {
                     const int jj = j0 + i * G;
                     C v; v.x = 0; v.y = 0;
-                    pair<real>(v, w[i], vb[i], vc[i]);            // 0 + increment: the increment
+                    pair(v, w[i], vb[i], vc[i]);            // 0 + increment: the increment
                     if (!live[i]) { v.x = 0; v.y = 0; }
                     if (jj < NT) mine[1 + jj] = v;
                 }
@@ -335,18 +314,7 @@ __global__ void __launch_bounds__(1024) k_team_online_ordered(GenericArgs<real> 
                 C acc;
                 acc.x = 0; acc.y = 0;
                 for (int jj = 0; jj <= NT; ++jj) { const C v = mine[jj]; acc.x += v.x; acc.y += v.y; }
-                const real mag = rescued_norm<real>(acc);     // (rescales a sum that fp32 cannot square: lws_common.h)
-                if (mag > 0) {
-                    C v;
-                    v.x = acc.x * u.target / mag;
-                    v.y = acc.y * u.target / mag;
-                    S[u.idx] = v;
-                    const int n = u.n, nyq = F + L - 1;   // Hermitian images in the pad columns (lwslib.cpp:362-367)
-                    C vc;
-                    vc.x = v.x; vc.y = -v.y;
-                    if (n >= L + 1 && n < 2 * L + 1) S[(size_t)u.m_ext * Np + 2 * L - n] = vc;
-                    else if (n >= F - 1 && n < nyq) S[(size_t)u.m_ext * Np + 2 * nyq - n] = vc;
-                }
+                finish_bin<real>(S, u.idx, u.n, F, L, acc, u.target);
             }
         }
         __syncthreads();
@@ -463,6 +431,8 @@ __global__ void __launch_bounds__(NCH == 3 ? 512 : 1024) k_team_online_ring(Gene
         // then not written.  tools/stress_team.py found it: one bin in a few thousand, after fp64 cases had run on the same CU.)
         w_n = none ? 0 : ((r * (L + 1) + (dk < 0 ? -dk : dk)) | (((meta >> 8) & 1) << 31));
     };
+    // (this kernel spells out online_unit of lws_online_unit.h here and finish_bin of lws_bin.h below: with online_unit its fp32
+    //  builds take three more registers or spill more, with finish_bin lws(1024,64) and lws(1024,112) run 2.4 % slower)
     auto setup = [&]() __attribute__((always_inline)) {
         valid = false;
         if (s >= nsweeps) { s_end = t_end; return; }
@@ -528,7 +498,7 @@ __global__ void __launch_bounds__(NCH == 3 ? 512 : 1024) k_team_online_ring(Gene
                     vc[i] = ring[oc[O + i] + n];
                 }
 #pragma unroll
-                for (int i = 0; i < CH; ++i) pair<real>(acc, w[i], vb[i], vc[i]);
+                for (int i = 0; i < CH; ++i) pair(acc, w[i], vb[i], vc[i]);
             };
             chunk(std::integral_constant<int, 0>{}, rb, rc, wn);
             if constexpr (NC > CH) { if (two_chunks) chunk(std::integral_constant<int, CH>{}, rb, rc, wn); }
@@ -551,7 +521,7 @@ __global__ void __launch_bounds__(NCH == 3 ? 512 : 1024) k_team_online_ring(Gene
             }
         }
         if (act && g == 0) {
-            const real mag = rescued_norm<real>(acc);     // (rescales a sum that fp32 cannot square: lws_common.h)
+            const real mag = rescued_norm<real>(acc);     // (finish_bin of lws_bin.h, spelt out: see setup)
             if (mag > 0) {
                 C v;
                 v.x = acc.x * target / mag;
