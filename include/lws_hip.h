@@ -232,6 +232,21 @@ int lws_griffin_lim_dev(int device, void *C_dev, const float *A_dev, int B, int 
 int lws_misi_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, int B, int K, int M, int N, int fshift,
                  const double *awin, const double *swin, int perfectrec, int iters, float *x_dev, double *trace, void *stream);
 
+/* RTISI-LA (Real-Time Iterative Spectrogram Inversion with Look-Ahead, Zhu, Beauregard & Wyse 2007), device resident (lws_gla.hip;
+ * what the reference's online sweeps approximate): Griffin-Lim under a look-ahead, frame m of the result depending on no input
+ * frame later than m + look_ahead.  With inv(c) = swin irfft(c) and fwd(y) = rfft(awin y) on the uncut timeline of hop (M - 1) + N
+ * samples (with perfectrec the samples istft cuts read as zero), the frames m = 0 .. M-1 are committed in order: the frames up to
+ * last = min(m + look_ahead, M - 1) enter as f_j = inv(c_j); `iters` times, y = done + sum_{j = m..last} f_j (j ascending),
+ * c_j = A_j X_j / |X_j| with X_j = fwd(y at hop j) (A_j + 0j where |X_j| == 0) and f_j = inv(c_j) for all j = m..last from the same
+ * y; then done += f_m.  C_dev[B][M][N/2+1] (complex64) holds the start on entry and the committed c_m -- whose magnitudes are A --
+ * on return; iters == 0 leaves it unchanged.  A_dev[B][M][N/2+1] (float32): target magnitudes, NULL: |C| on entry.  x_dev: NULL,
+ * or [B][lws_istft_length(M, N, fshift, perfectrec)] (float32) for the committed sum cut as istft cuts it, which is istft of the
+ * result (also with iters == 0).  One workgroup per spectrogram and one launch; the call only enqueues work on `stream`.
+ * iters < 0, look_ahead < 0, a null C_dev / window, or, with iters > 0 and perfectrec, an M the round trip does not keep:
+ * LWS_ERR_INVALID, before anything is enqueued; frame sizes outside the device transform: as lws_griffin_lim_dev. */
+int lws_rtisi_la_dev(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift,
+                     const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream);
+
 /* ---- host-side construction of windows, weights and schedules (lws.pyx:10-40,160-206), fp64, no device work: what a
  *      caller without numpy needs to build a plan.  Complex outputs are interleaved (re, im) doubles. ---- */
 

@@ -20,8 +20,11 @@ constexpr int MAXN = 4096, MINN = 32, FFT_THREADS = 256;   // two N-point comple
 
 // Complex DFT of n = m 2^a points held in LDS (x: data, y: scratch of the same size, followed -- if m > 1 -- by n entries for
 // the twiddle table), by all threads of the block; natural order in and out.  sign = -1 forward, +1 inverse (unnormalised).
-// Returns the buffer that holds the result.
-__device__ float2 *fft_lds(float2 *x, float2 *y, int n, int m, int a, float sign) {
+// Returns the buffer that holds the result.  USER: a caller that passes other buffers than the start of the dynamic LDS (k_rtisi)
+// takes an instance of its own, so that what the compiler derives from the other callers' arguments (all alike) stays derived; with
+// one shared instance a scalar shift moves by two slots in each of them.  Nothing computed depends on that: it only keeps their
+// instruction streams what they were.  tools/compare_kernel_isa.py checks it, kernel by kernel, against another build's assembly.
+template <int USER = 0> __device__ float2 *fft_lds(float2 *x, float2 *y, int n, int m, int a, float sign) {
     const int tid = threadIdx.x, nthr = blockDim.x;
     const int n2 = n / m;                                // 2^a
     float2 *tw = y + n;

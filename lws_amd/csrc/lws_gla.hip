@@ -224,11 +224,161 @@ __global__ void __launch_bounds__(256) k_misi_signals(const float *sig, const fl
     x[(size_t)bk * len + j] = sig[(size_t)bk * Tfull + t] + delta[(size_t)(bk / K) * Tfull + t];
 }
 
+// ---- RTISI-LA (Zhu, Beauregard & Wyse 2007): Griffin-Lim under a look-ahead of LA frames.  One workgroup per spectrogram marches
+// over the frames m = 0 .. M-1; committing frame m runs `iters` Jacobi iterations over the active frames m .. min(m + LA, M-1)
+// against the committed overlap-add sum, then adds frame m to that sum for good.  The timeline is the uncut one of gla_sample.
+//   ring : the committed sum `done` over [hop m, hop (m + LA) + N), a ring of R = N + LA hop floats (sample t of the window sits at
+//          (base + t - hop m) mod R); the hop samples frame m leaves behind are final, go to the signal and are zeroed for re-use;
+//   fcur : the windowed inverse frames f_j of the active frames, frame j in slot j mod (LA + 1);
+//   fnxt : the f_j of the iteration under way (Jacobi: every pair reads fcur), swapped with fcur after the last pair.
+// The three live in dynamic LDS behind the transform buffers (IN_LDS) or in a slice of device scratch of this workgroup alone,
+// ordered by the same barriers.  Every loop that encloses a barrier runs over m, last, it, j or the direction: kernel arguments and
+// counters derived from them alone, the same in every thread.
+constexpr int RTISI_MAX_THREADS = 1024;
+struct RtisiArgs {
+    int M, N, odd, log2e, hop, LA, iters, zero_lo, zero_hi, len;
+    size_t state_floats;   // R + 2 (LA + 1) N
+};
+
+// Z = c_j + i c_{j+1} on the Hermitian-completed bins, as k_gla_inverse builds it
+__device__ __forceinline__ void rtisi_put_pair(float2 *Z, int k, int N, float2 u, float2 v) {
+    if (k == 0 || k == N / 2) {
+        Z[k] = make_float2(u.x, v.x);
+    } else {
+        Z[k] = make_float2(u.x - v.y, u.y + v.x);
+        Z[N - k] = make_float2(u.x + v.y, v.x - u.y);
+    }
+}
+
+// sample t of keep (done + sum of the active frames m .. last that cover t, ascending); slot: that of frame m
+__device__ __forceinline__ float rtisi_sample(const float *ring, const float *f, int t, int m, int last, int slot, int base, int R,
+                                              int t_end, RtisiArgs a) {
+    if (t < a.zero_lo || t >= t_end) return 0.f;
+    int d = t - a.hop * m;                                   // in [0, R): the ring's window starts at frame m
+    int pos = base + d;
+    if (pos >= R) pos -= R;
+    float acc = ring[pos];
+    for (int s = m; s <= last; ++s, d -= a.hop) {
+        if ((unsigned)d < (unsigned)a.N) acc += f[(size_t)slot * a.N + d];
+        if (++slot > a.LA) slot = 0;
+    }
+    return acc;
+}
+
+__device__ __forceinline__ float2 rtisi_project(float2 X, float a) {
+    const float mag = sqrtf(X.x * X.x + X.y * X.y);
+    return mag > 0.f ? make_float2(a * (X.x / mag), a * (X.y / mag)) : make_float2(a, 0.f);
+}
+
+template <bool IN_LDS>
+__global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi(float2 *C, const float *A, float *xout, const float *awin, const float *swin,
+                                                        float *scratch, RtisiArgs a) {
+    extern __shared__ float2 lds[];
+    const int b = blockIdx.x, N = a.N, F = N / 2 + 1, hop = a.hop, M = a.M, W = a.LA + 1, R = N + a.LA * hop;
+    const int t_end = hop * (M - 1) + N - a.zero_hi;
+    float2 *bufA = lds, *bufB = lds + N, *bufC = lds + 2 * N;   // bufC: the twiddle table's place, N not a power of two only
+    float *state = IN_LDS ? reinterpret_cast<float *>(lds + (a.odd > 1 ? 3 : 2) * N) : scratch + (size_t)b * a.state_floats;
+    float *ring = state, *fcur = state + R, *fnxt = fcur + (size_t)W * N;
+    float2 *Cb = C + (size_t)b * M * F;
+    const float *Ab = A ? A + (size_t)b * M * F : nullptr;   // null without iterations, and not read then
+    float *xb = xout ? xout + (size_t)b * a.len : nullptr;
+    for (int i = threadIdx.x; i < R; i += blockDim.x) ring[i] = 0.f;
+    __syncthreads();
+    int base = 0, slot_m = 0;   // slot_m: the slot of frame m
+    for (int m = 0; m < M; ++m) {
+        const int last = m + a.LA < M - 1 ? m + a.LA : M - 1;
+        // pass 0: the frames that have not entered, f_j = inv(S_j) (LA + 1 frames at m = 0, one per step after that), into fcur;
+        // passes 1 .. iters: the active frames, from fcur into fnxt
+        for (int it = 0; it <= a.iters; ++it) {
+            float *dst = it == 0 ? fcur : fnxt;
+            // pass 0 starts at frame 0 (slot 0) in the first step and at frame m + LA after that: the slot before slot_m, cyclically
+            const int j0 = it > 0 ? m : m == 0 ? 0 : m + a.LA;
+            int slot = it > 0 || m == 0 ? slot_m : slot_m == 0 ? a.LA : slot_m - 1;   // of frame j: j mod (LA + 1), counted, not divided
+            for (int j = j0; j <= last; j += 2) {
+                const bool two = j + 1 <= last;
+                // one transform call for both directions (ph 0: forward, not in pass 0; ph 1: inverse): its uniform state once
+                float2 *r = bufB;
+#pragma nounroll
+                for (int ph = it == 0 ? 1 : 0; ph < 2; ++ph) {
+                    float2 *x = bufA, *y = bufB;
+                    if (ph == 0) {
+                        for (int n = threadIdx.x; n < N; n += blockDim.x) {
+                            const float w = awin[n];
+                            const float re = rtisi_sample(ring, fcur, j * hop + n, m, last, slot_m, base, R, t_end, a) * w;
+                            const float im = two ? rtisi_sample(ring, fcur, (j + 1) * hop + n, m, last, slot_m, base, R, t_end, a) * w : 0.f;
+                            x[n] = make_float2(re, im);
+                        }
+                    } else if (it == 0) {
+                        const float2 *r0 = Cb + (size_t)j * F, *r1 = r0 + F;
+                        for (int k = threadIdx.x; k < F; k += blockDim.x)
+                            rtisi_put_pair(x, k, N, r0[k], two ? r1[k] : make_float2(0.f, 0.f));
+                    } else {
+                        // the projected pair goes where the forward result is not, and where the inverse transform finds room for
+                        // its table behind its second buffer: result in bufB -> (bufA, bufB, table bufC); in bufA -> (bufC, bufA,
+                        // table bufB)
+                        x = r == bufB ? bufA : (a.odd > 1 ? bufC : bufB);
+                        y = r;
+                        const bool commit = it == a.iters && j == m;
+                        const float *A0 = Ab + (size_t)j * F, *A1 = A0 + F;
+                        for (int k = threadIdx.x; k < F; k += blockDim.x) {
+                            const float2 zk = r[k], zn = r[k == 0 ? 0 : N - k];
+                            const float2 u = rtisi_project(make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)), A0[k]);
+                            float2 v = make_float2(0.f, 0.f);
+                            if (two) v = rtisi_project(make_float2(0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)), A1[k]);
+                            if (commit) Cb[(size_t)m * F + k] = u;
+                            rtisi_put_pair(x, k, N, u, v);
+                        }
+                    }
+                    __syncthreads();
+                    // the transform's own uniforms (its strides, quotients and stage masks) are derived here, at the call, from
+                    // values the compiler cannot see through: hoisted over all five loops they cost more SGPRs than a wave has
+                    int n_ = N, odd_ = a.odd, log2e_ = a.log2e;
+                    asm volatile("" : "+s"(n_), "+s"(odd_), "+s"(log2e_));
+                    r = fft_lds<1>(x, y, n_, odd_, log2e_, ph == 0 ? -1.0f : 1.0f);
+                }
+                // times the synthesis window, into the slots of frames j and j + 1
+                const float inv = 1.0f / (float)N;
+                float *o0 = dst + (size_t)slot * N, *o1 = dst + (size_t)(slot < a.LA ? slot + 1 : 0) * N;
+                for (int n = threadIdx.x; n < N; n += blockDim.x) {
+                    const float w = inv * swin[n];
+                    o0[n] = r[n].x * w;
+                    if (two) o1[n] = r[n].y * w;
+                }
+                __syncthreads();   // r is the next load's buffer, dst the next reader's
+                slot += 2;
+                if (slot > a.LA) slot -= W;
+                if (slot > a.LA) slot -= W;   // W == 1
+            }
+            if (it > 0) { fnxt = fcur; fcur = dst; }
+        }
+        // done += f_m; what no later frame reaches is final: hop samples, or all N behind the last frame
+        const float *fm = fcur + (size_t)slot_m * N;
+        const int nfinal = m == M - 1 ? N : hop;
+        for (int n = threadIdx.x; n < N; n += blockDim.x) {
+            int pos = base + n;
+            if (pos >= R) pos -= R;
+            const float v = ring[pos] + fm[n];
+            const int t = hop * m + n;
+            if (n < nfinal) {
+                if (xb && t >= a.zero_lo && t < t_end) xb[t - a.zero_lo] = v;
+                ring[pos] = 0.f;
+            } else {
+                ring[pos] = v;
+            }
+        }
+        base += hop;
+        if (base >= R) base -= R;
+        if (++slot_m > a.LA) slot_m = 0;
+        __syncthreads();
+    }
+}
+
 // Windows and scratch of the iteration, one set per device, serialised on the device by the event scheme of lws_stft.hip.  The
 // windows stay on the device between calls: a call with the windows of the previous one uploads nothing.
 struct GlaCtx {
     Scratch frames, t, a, rows, trace, win_a, win_s;
     Scratch delta, sig;                   // MISI: the shared mixture error, and the K overlap-added signals
+    Scratch state;                        // RTISI-LA: ring and frames of the workgroups whose state does not fit in LDS
     std::vector<double> host_a, host_s;   // what win_a / win_s hold
     hipEvent_t last = nullptr;
     bool busy = false;
@@ -398,5 +548,70 @@ extern "C" int lws_misi_dev(int device, void *C_dev, const float *A_dev, const f
         STFT_TRY(hipMemcpyAsync(trace, c.trace.p, (size_t)iters * B * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
         STFT_TRY(hipStreamSynchronize(s));
     }
+    return ctx_leave(c, s);
+}
+
+namespace {
+
+// Where the state of k_rtisi lives: behind the transform buffers in LDS if all of it fits there, in device scratch otherwise.
+struct RtisiPlan {
+    size_t state_floats, lds_bytes;
+    bool in_lds;
+    int threads;   // one workgroup per CU and every step behind a barrier: a thread per sample, up to 16 waves, hides the LDS latency
+};
+constexpr size_t RTISI_LDS_CAP = 160 * 1024;
+RtisiPlan rtisi_plan(int N, int hop, int LA) {
+    RtisiPlan p;
+    p.state_floats = (size_t)N + (size_t)LA * hop + 2 * (size_t)(LA + 1) * N;
+    const size_t all = fft_lds_bytes(N) + p.state_floats * sizeof(float);
+    p.in_lds = all <= RTISI_LDS_CAP;
+    p.lds_bytes = p.in_lds ? all : fft_lds_bytes(N);
+    p.threads = N <= FFT_THREADS ? FFT_THREADS : N >= RTISI_MAX_THREADS ? RTISI_MAX_THREADS : (N + FFT_THREADS - 1) / FFT_THREADS * FFT_THREADS;
+    return p;
+}
+
+}  // namespace
+
+extern "C" int lws_rtisi_la_dev(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift,
+                                const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream) {
+    int rc = check_shape(device, B, M, N, fshift);
+    if (rc) return rc;
+    if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
+    if (look_ahead < 0) return lws::set_error(LWS_ERR_INVALID, "look-ahead of %d frames", look_ahead);
+    if (!C_dev || !awin || !swin) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    if (iters > 0 && (rc = check_round_trip(M, N, fshift, perfectrec))) return rc;
+    const int len = lws_istft_length(M, N, fshift, perfectrec);
+    if (B == 0 || (iters == 0 && (!x_dev || len < 1))) return LWS_OK;
+    STFT_TRY(hipSetDevice(device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> lk(g_mu);
+    GlaCtx &c = g_ctx[device];
+    if ((rc = ctx_enter(c, s))) return rc;
+    STFT_TRY(lws::allow_dynamic_lds<&k_rtisi<true>>((int)RTISI_LDS_CAP));
+    STFT_TRY(lws::allow_dynamic_lds<&k_rtisi<false>>(3 * MAXN * (int)sizeof(float2)));
+    if ((rc = upload_window(c.win_a, c.host_a, awin, N, s))) return rc;
+    if ((rc = upload_window(c.win_s, c.host_s, swin, N, s))) return rc;
+    const int F = N / 2 + 1, LA = look_ahead < M - 1 ? look_ahead : M - 1;   // no frame beyond M - 1 to look at
+    const size_t bins = (size_t)B * M * F;
+    const RtisiPlan p = rtisi_plan(N, fshift, LA);
+    if (!p.in_lds && (rc = c.state.ensure((size_t)B * p.state_floats * sizeof(float)))) return rc;
+    if (!A_dev && iters > 0) {
+        if ((rc = c.a.ensure(bins * sizeof(float)))) return rc;
+        hipLaunchKernelGGL(k_gla_abs, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, s, static_cast<const float2 *>(C_dev),
+                           static_cast<float *>(c.a.p), bins);
+        A_dev = static_cast<const float *>(c.a.p);
+    }
+    const Factors fc = factor(N);
+    const RtisiArgs a{M, N, fc.odd, fc.log2e, fshift, LA, iters, perfectrec ? prepad(N, fshift) : 0, perfectrec ? N - fshift : 0,
+                      len, p.state_floats};
+    float2 *C = static_cast<float2 *>(C_dev);
+    const float *wa = static_cast<const float *>(c.win_a.p), *ws = static_cast<const float *>(c.win_s.p);
+    if (p.in_lds)
+        hipLaunchKernelGGL(k_rtisi<true>, dim3(B), dim3(p.threads), p.lds_bytes, s, C, A_dev, len < 1 ? nullptr : x_dev, wa, ws,
+                           static_cast<float *>(nullptr), a);
+    else
+        hipLaunchKernelGGL(k_rtisi<false>, dim3(B), dim3(p.threads), p.lds_bytes, s, C, A_dev, len < 1 ? nullptr : x_dev, wa, ws,
+                           static_cast<float *>(c.state.p), a);
+    STFT_TRY(hipGetLastError());
     return ctx_leave(c, s);
 }

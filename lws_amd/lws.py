@@ -380,6 +380,118 @@ def misi_dev(S, mixture, fsize, fshift, awin, swin, iterations, magnitudes=None,
     return _misi_returns(t4, db, sig, return_trace, return_signals)
 
 
+# --------------------------------------------------------------------------------------------
+# RTISI-LA (Zhu, Beauregard & Wyse 2007): Griffin-Lim under a look-ahead -- what online LWS approximates, as batch LWS does Griffin-Lim
+# --------------------------------------------------------------------------------------------
+def _look_ahead_arg(look_ahead):
+    if int(look_ahead) != look_ahead or look_ahead < 0:
+        raise ValueError('look_ahead must be a non-negative integer, got %r' % (look_ahead,))
+    return int(look_ahead)
+
+
+def _rtisi_project(X, A):
+    mag = np.abs(X)
+    return np.where(mag > 0, A * X / np.where(mag > 0, mag, 1.0), A + 0j)
+
+
+def rtisi_la(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=None, perfectrec=False, return_signal=False,
+             _perturb=None):
+    """Real-Time Iterative Spectrogram Inversion with Look-Ahead from the start S, (T, F) or a stack (B, T, F), in fp64 on the
+    host: the definition the device form is held to.  Frame m of the result depends on no input frame later than m + look_ahead.
+    With inv(c) = swin irfft(c) and fwd(y) = rfft(awin y) on the timeline of fshift (T - 1) + fsize samples -- where, with
+    perfectrec, the samples istft cuts read as zero -- the frames m = 0 .. T-1 are committed in order: every frame up to
+    last = min(m + look_ahead, T - 1) that has not entered does, f_j = inv(c_j); `iterations` times, all active frames are
+    projected from the same sum (Jacobi), y = done + sum_{j = m..last} f_j (j ascending), c_j = A_j X_j / |X_j| with
+    X_j = fwd(y[fshift j : fshift j + fsize]) (A_j + 0j where |X_j| == 0), f_j = inv(c_j); then done += f_m for good.  Returns c
+    (its magnitudes are A = `magnitudes`, by default |S|); zero iterations return S.  With look_ahead >= T - 1 the first commit
+    is `iterations` plain Griffin-Lim steps.  return_signal: also done cut as istft cuts it, which is istft(c), (len,) / (B, len).
+    (_perturb(m, it, b, X) -> X: replaces the stacked projections of one inner iteration; the error model of the tests.)"""
+    n, _ = _gla_args(iterations, 0.0)
+    LA = _look_ahead_arg(look_ahead)
+    S = np.asarray(S)
+    if S.ndim not in (2, 3):
+        raise ValueError('expected a (T, F) spectrogram or a (B, T, F) stack')
+    A = np.abs(S) if magnitudes is None else np.asarray(magnitudes, dtype=np.float64)
+    if A.shape != S.shape:
+        raise ValueError('magnitudes of shape %s for a spectrogram of shape %s' % (A.shape, S.shape))
+    T, F = S.shape[-2:]
+    if F != fsize // 2 + 1 or fsize % 2:
+        raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
+    awin, swin = np.asarray(awin, dtype=np.float64), np.squeeze(np.asarray(swin, dtype=np.float64))
+    total = fshift * (T - 1) + fsize
+    keep = np.ones(total)
+    lo, hi = 0, total
+    if perfectrec is True:
+        lo, hi = _perfectrec_prepad(fsize, fshift), total - (fsize - fshift)
+        keep[:lo] = 0.0
+        keep[max(hi, 0):] = 0.0
+        back = stft(np.zeros(max(hi - lo, 0)), fsize, fshift, awin, perfectrec=True).shape[0]
+        if n > 0 and back != T:
+            raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
+    S3, A3 = (S[None], A[None]) if S.ndim == 2 else (S, A)
+    out = S3.astype(np.complex128)
+    sig = np.empty((S3.shape[0], max(hi - lo, 0)))
+    for b in range(S3.shape[0] if (n > 0 or return_signal) else 0):
+        c, done, f, entered = out[b], np.zeros(total), np.zeros((T, fsize)), 0
+        for m in range(T):
+            last = min(m + LA, T - 1)
+            while entered <= last:
+                f[entered] = swin * np.fft.irfft(c[entered], fsize)
+                entered += 1
+            for it in range(1, n + 1):
+                y = done.copy()
+                for j in range(m, last + 1):
+                    y[fshift * j: fshift * j + fsize] += f[j]
+                y *= keep
+                X = np.stack([np.fft.rfft(awin * y[fshift * j: fshift * j + fsize]) for j in range(m, last + 1)])
+                if _perturb is not None:
+                    X = _perturb(m, it, b, X)
+                c[m: last + 1] = _rtisi_project(X, A3[b, m: last + 1])
+                for j in range(m, last + 1):
+                    f[j] = swin * np.fft.irfft(c[j], fsize)
+            done[fshift * m: fshift * m + fsize] += f[m]
+        sig[b] = (keep * done)[lo: max(hi, lo)]
+    if S.ndim == 2:
+        out, sig = out[0], sig[0]
+    if n == 0:
+        out = S
+    return (out, sig) if return_signal else out
+
+
+def rtisi_la_dev(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=None, perfectrec=False, return_signal=False,
+                 device=0):
+    """rtisi_la() above on the device (lws_gla.hip: float32, one workgroup per spectrogram marching over the frames with its
+    state in LDS, one launch): S (T, F) or (B, T, F), numpy or torch; returns a new complex64 torch tensor (S itself is not
+    modified), and with return_signal also the float32 signals (len,) / (B, len).  Runs on the caller's current torch stream
+    and only enqueues work.  Raises ValueError, as rtisi_la() does, for a frame count the round trip does not keep."""
+    import torch
+    n, _ = _gla_args(iterations, 0.0)
+    LA = _look_ahead_arg(look_ahead)
+    t = _dev_tensor(S, torch.complex64, device)
+    if t.dim() not in (2, 3):
+        raise ValueError('expected a (T, F) spectrogram or a (B, T, F) stack')
+    single = t.dim() == 2
+    t3 = (t[None] if single else t).clone()
+    B, T, F = t3.shape
+    if F != fsize // 2 + 1:
+        raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
+    length = _capi.istft_length(T, fsize, fshift, perfectrec)
+    back = _capi.stft_frames(length, fsize, fshift, perfectrec)
+    if n > 0 and perfectrec and back != T:
+        raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
+    A = None
+    if magnitudes is not None:
+        A = _dev_tensor(magnitudes, torch.float32, device)
+        if A.shape != t.shape:
+            raise ValueError('magnitudes of shape %s for a spectrogram of shape %s' % (tuple(A.shape), tuple(t.shape)))
+    sig = torch.empty((B, max(length, 0)), dtype=torch.float32, device=t3.device) if return_signal else None
+    _capi.rtisi_la_dev(t3.data_ptr(), None if A is None else A.data_ptr(), None if sig is None or sig.numel() == 0 else sig.data_ptr(),
+                       B, T, fsize, fshift, awin, swin, perfectrec, n, LA, device=int(device),
+                       stream=torch.cuda.current_stream(t3.device).cuda_stream)
+    out = t3[0] if single else t3
+    return (out, sig[0] if single else sig) if return_signal else out
+
+
 def extspec(S, L, Q):
     """Extended spectrogram: L Hermitian columns each side, Q-1 repeated frames each end (lws.pyx:146-157)."""
     S = np.asarray(S)
@@ -726,6 +838,18 @@ class lws(object):
         """Device form: a new complex64 torch tensor, see the module's misi_dev."""
         return misi_dev(S, mixture, self.fsize, self.fshift, self.awin, self.swin, iterations, magnitudes=magnitudes,
                         perfectrec=self.perfectrec, return_trace=return_trace, return_signals=return_signals, device=self.device)
+
+    def rtisi_la(self, S, iterations, look_ahead=None, magnitudes=None, return_signal=False):
+        """Host fp64 form with this object's windows, perfectrec and (look_ahead=None) look-ahead: see the module's rtisi_la."""
+        return rtisi_la(S, self.fsize, self.fshift, self.awin, self.swin, iterations,
+                        look_ahead=self.look_ahead if look_ahead is None else look_ahead, magnitudes=magnitudes,
+                        perfectrec=self.perfectrec, return_signal=return_signal)
+
+    def rtisi_la_dev(self, S, iterations, look_ahead=None, magnitudes=None, return_signal=False):
+        """Device form: a new complex64 torch tensor, see the module's rtisi_la_dev."""
+        return rtisi_la_dev(S, self.fsize, self.fshift, self.awin, self.swin, iterations,
+                            look_ahead=self.look_ahead if look_ahead is None else look_ahead, magnitudes=magnitudes,
+                            perfectrec=self.perfectrec, return_signal=return_signal, device=self.device)
 
     def nofuture_lws(self, S, iterations=None, thresholds=None):
         if iterations is None:
