@@ -247,6 +247,24 @@ int lws_misi_dev(int device, void *C_dev, const float *A_dev, const float *y_dev
 int lws_rtisi_la_dev(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift,
                      const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream);
 
+/* Online MISI, device resident (lws_gla.hip): MISI under a look-ahead, for the K sources of each of B mixtures -- lws_misi_dev as
+ * lws_rtisi_la_dev is lws_griffin_lim_dev.  Frame m of every source depends on no input frame later than m + look_ahead and on no
+ * mixture sample behind the end of that frame.  On the timeline and with inv, fwd and the cuts of lws_rtisi_la_dev, the mixture y
+ * sitting where istft would put it, w = awin swin, and g_l = (sum_{j <= l} w) / (sum_j w) over the frames j that cover a sample
+ * (ascending; 1 where the denominator is 0), the frames m = 0 .. M-1 are committed in order: the frames up to
+ * last = min(m + look_ahead, M - 1) enter as f_kj = inv(c_kj); `iters` times, y_k = done_k + sum_{j = m..last} f_kj (j ascending),
+ * e = g_last y - sum_k y_k (k ascending), c_kj = A_kj X / |X| with X = fwd(y_k + e / K at hop j) (A_kj + 0j where |X| == 0) and
+ * f_kj = inv(c_kj) for all k and all j = m..last from the same iterate; then done_k += f_km.  C_dev[B][K][M][N/2+1] (complex64) holds
+ * the starts on entry and the committed c_km -- whose magnitudes are A -- on return; iters == 0 leaves it unchanged.
+ * A_dev[B][K][M][N/2+1] (float32): target magnitudes, NULL: |C| on entry.  y_dev[B][len] (float32), len = lws_istft_length(M, ...):
+ * the mixtures.  x_dev: NULL, or [B][K][len] (float32) for s_k = done_k + (y - sum_j done_j) / K cut as istft cuts it, which sum
+ * to y (also with iters == 0).  look_ahead is clamped to M - 1.  One workgroup per mixture and one launch; the call only enqueues
+ * work on `stream`.  K < 1, iters < 0, look_ahead < 0, a null C_dev / y_dev / window, frames that leave no samples, or, with
+ * iters > 0 and perfectrec, an M the round trip does not keep: LWS_ERR_INVALID, before anything is enqueued; frame sizes outside
+ * the device transform: as lws_griffin_lim_dev. */
+int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, float *x_dev, int B, int K, int M, int N,
+                    int fshift, const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream);
+
 /* ---- host-side construction of windows, weights and schedules (lws.pyx:10-40,160-206), fp64, no device work: what a
  *      caller without numpy needs to build a plan.  Complex outputs are interleaved (re, im) doubles. ---- */
 

@@ -30,7 +30,7 @@ EXPORTS = (
     "lws_batch_lws", "lws_nofuture_lws", "lws_online_lws", "lws_run_lws", "lws_batch_lws_dev",
     "lws_nofuture_lws_dev", "lws_online_lws_dev", "lws_residual_dev", "lws_last_kernel_time",
     "lws_last_kernel_name", "lws_generic_stage", "lws_stft_frames", "lws_istft_length", "lws_stft_dev", "lws_istft_dev", "lws_stft_zp_dev",
-    "lws_consistency_dev", "lws_griffin_lim_dev", "lws_misi_dev", "lws_rtisi_la_dev", "lws_hann", "lws_synthwin", "lws_weights_shape", "lws_create_weights",
+    "lws_consistency_dev", "lws_griffin_lim_dev", "lws_misi_dev", "lws_rtisi_la_dev", "lws_misi_la_dev", "lws_hann", "lws_synthwin", "lws_weights_shape", "lws_create_weights",
     "lws_build_asymmetric_windows", "lws_get_thresholds", "lws_plan_create_from_windows", "lws_stream_copy",
     "lws_run_lws_dev", "lws_plan_reserve", "lws_residual", "lws_residual_allreduce_dev", "lws_weights_structure", "lws_multi_plan_create", "lws_multi_plan_destroy",
     "lws_multi_plan_shards", "lws_multi_batch_lws", "lws_multi_run_lws", "lws_multi_residual",
@@ -105,6 +105,7 @@ def load():
     lib.lws_griffin_lim_dev.argtypes = [ip, vp, vp, ip, ip, ip, ip, vp, vp, ip, ip, dp, vp, vp]
     lib.lws_misi_dev.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, vp, vp, vp]
     lib.lws_rtisi_la_dev.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, vp, vp, ip, ip, ip, vp]
+    lib.lws_misi_la_dev.argtypes = [ip, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, ip, vp]
     lib.lws_hann.argtypes = [ip, ip, ip, vp]
     lib.lws_synthwin.argtypes = [vp, ip, ip, vp, vp]
     lib.lws_weights_shape.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
@@ -501,3 +502,15 @@ def rtisi_la_dev(C_ptr, A_ptr, x_ptr, B, frames, fsize, fshift, awin, swin, perf
         raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
     check(load().lws_rtisi_la_dev(int(device), C_ptr, A_ptr, x_ptr, int(B), int(frames), int(fsize), int(fshift), a.ctypes.data,
                                   w.ctypes.data, int(bool(perfectrec)), int(iterations), int(look_ahead), stream))
+
+
+def misi_la_dev(C_ptr, A_ptr, y_ptr, x_ptr, B, K, frames, fsize, fshift, awin, swin, perfectrec, iterations, look_ahead, device=0,
+                stream=None):
+    """Online MISI in place on C_ptr (device complex64 [B][K][frames][fsize//2+1]); A_ptr: device float32 target magnitudes or None
+    (|C| on entry); y_ptr: device float32 mixtures [B][istft_length(...)]; x_ptr: None or device float32 [B][K][length] for the
+    signals.  Only enqueues."""
+    a, w = _win(awin), _win(swin)
+    if a.shape != (int(fsize),) or w.shape != (int(fsize),):
+        raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
+    check(load().lws_misi_la_dev(int(device), C_ptr, A_ptr, y_ptr, x_ptr, int(B), int(K), int(frames), int(fsize), int(fshift),
+                                 a.ctypes.data, w.ctypes.data, int(bool(perfectrec)), int(iterations), int(look_ahead), stream))

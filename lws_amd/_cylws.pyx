@@ -294,6 +294,17 @@ def lws_rtisi_la_dev(int device, C_dev, A_dev, x_dev, int B, int M, int N, int f
     return rc
 
 
+def lws_misi_la_dev(int device, C_dev, A_dev, y_dev, x_dev, int B, int K, int M, int N, int fshift, awin, swin, int perfectrec,
+                    int iters, int look_ahead, stream):
+    cdef uintptr_t cd = _addr(C_dev), ad = _addr(A_dev), yd = _addr(y_dev), xd = _addr(x_dev), a = _addr(awin), w = _addr(swin)
+    cdef uintptr_t st = _addr(stream)
+    cdef int rc
+    with nogil:
+        rc = c.lws_misi_la_dev(device, <void *>cd, <const float *>ad, <const float *>yd, <float *>xd, B, K, M, N, fshift,
+                               <const double *>a, <const double *>w, perfectrec, iters, look_ahead, <void *>st)
+    return rc
+
+
 def lws_hann(int n, int symmetric, int use_offset, out):
     cdef uintptr_t o = _addr(out)
     return c.lws_hann(n, symmetric, use_offset, <double *>o)

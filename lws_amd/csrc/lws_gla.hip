@@ -373,6 +373,168 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi(float2 *C, const fl
     }
 }
 
+// ---- Online MISI: the K sources of a mixture under a look-ahead, MISI as k_rtisi is Griffin-Lim.  One workgroup per MIXTURE marches
+// over the frames; inside each stage its sources are taken one after another.  The state is K copies of k_rtisi's (ring_k, fcur_k,
+// fnxt_k), and over the active window of R samples, sample hop m + d at index d:
+//   target : keep g_last y, once per commit step.  g_last = num / den (1 where den == 0) is the share of a sample's overlap-add weight
+//            w = awin swin that has entered: den sums w over every frame that covers the sample, ascending, num is that sum as it stood
+//            behind frame `last` -- from the two device windows, no table;
+//   xs     : [K][R], x_k = y_k + delta with delta = (target - sum_k y_k) / K (k ascending), every y_k gathered by rtisi_sample once per
+//            inner iteration, before any fnxt is written; the forward load of frame j is xs_k[hop (j - m) + n] awin[n].
+// A thread owns the indices d = threadIdx.x + i blockDim.x of target and of all K rows of xs in every loop that writes them, so
+// target needs no barrier of its own and y_k becomes x_k in place.  Loops that enclose a barrier run over m, it, k, j and the
+// direction: kernel arguments and counters derived from them alone.
+struct MisiLaArgs {
+    RtisiArgs r;         // r.state_floats: the state of ONE source, R + 2 (LA + 1) N; r.len: samples of the mixture and of each signal
+    int K;
+    size_t all_floats;   // K r.state_floats + (K + 1) R: the scratch slice of a workgroup
+};
+
+template <bool IN_LDS>
+__global__ void __launch_bounds__(RTISI_MAX_THREADS) k_misi_la(float2 *C, const float *A, const float *Y, float *xout, const float *awin,
+                                                               const float *swin, float *scratch, MisiLaArgs q) {
+    extern __shared__ float2 lds[];
+    const RtisiArgs a = q.r;
+    const int b = blockIdx.x, K = q.K, N = a.N, F = N / 2 + 1, hop = a.hop, M = a.M, W = a.LA + 1, R = N + a.LA * hop;
+    const int t_end = hop * (M - 1) + N - a.zero_hi;
+    float2 *bufA = lds, *bufB = lds + N, *bufC = lds + 2 * N;   // as in k_rtisi
+    float *state = IN_LDS ? reinterpret_cast<float *>(lds + (a.odd > 1 ? 3 : 2) * N) : scratch + (size_t)b * q.all_floats;
+    float *target = state + (size_t)K * a.state_floats, *xs = target + R;
+    size_t cur = R, nxt = R + (size_t)W * N;   // fcur and fnxt within the state of a source; its ring is at 0
+    float2 *Cb = C + (size_t)b * K * M * F;
+    const float *Ab = A ? A + (size_t)b * K * M * F : nullptr;   // null without iterations, and not read then
+    const float *yb = Y + (size_t)b * a.len;
+    float *xb = xout ? xout + (size_t)b * K * a.len : nullptr;
+    for (int k = 0; k < K; ++k)
+        for (int i = threadIdx.x; i < R; i += blockDim.x) state[(size_t)k * a.state_floats + i] = 0.f;
+    __syncthreads();
+    int base = 0, slot_m = 0;   // slot_m: the slot of frame m
+    for (int m = 0; m < M; ++m) {
+        const int last = m + a.LA < M - 1 ? m + a.LA : M - 1;
+        for (int d = threadIdx.x; d < R; d += blockDim.x) {
+            const int t = hop * m + d;
+            float v = 0.f;
+            if (t >= a.zero_lo && t < t_end) {
+                int s_hi = t / hop;
+                if (s_hi > M - 1) s_hi = M - 1;
+                const int s_lo = (t - N + 1 <= 0) ? 0 : (t - N + hop) / hop;
+                float num = 0.f, den = 0.f;
+                for (int s = s_lo, n = t - s_lo * hop; s <= s_hi; ++s, n -= hop) {
+                    den += awin[n] * swin[n];
+                    if (s <= last) num = den;
+                }
+                const int i = t - a.zero_lo;
+                v = (den != 0.f ? num / den : 1.0f) * (i < a.len ? yb[i] : 0.f);
+            }
+            target[d] = v;
+        }
+        // pass 0: the frames that have not entered, f_kj = inv(S_kj), into fcur_k; passes 1 .. iters: the active frames of every source,
+        // from xs into fnxt_k
+        for (int it = 0; it <= a.iters; ++it) {
+            if (it > 0) {
+                for (int d = threadIdx.x; d < R; d += blockDim.x) {
+                    const int t = hop * m + d;
+                    float acc = 0.f;
+                    for (int k = 0; k < K; ++k) {
+                        const float *sk = state + (size_t)k * a.state_floats;
+                        const float y = rtisi_sample(sk, sk + cur, t, m, last, slot_m, base, R, t_end, a);
+                        xs[(size_t)k * R + d] = y;
+                        acc = k ? acc + y : y;
+                    }
+                    const float delta = (target[d] - acc) / (float)K;
+                    for (int k = 0; k < K; ++k) xs[(size_t)k * R + d] += delta;
+                }
+                __syncthreads();
+            }
+            const int j0 = it > 0 ? m : m == 0 ? 0 : m + a.LA;   // as in k_rtisi
+            for (int k = 0; k < K; ++k) {
+                float *dst = state + (size_t)k * a.state_floats + (it == 0 ? cur : nxt);
+                float2 *Ck = Cb + (size_t)k * M * F;
+                int slot = it > 0 || m == 0 ? slot_m : slot_m == 0 ? a.LA : slot_m - 1;
+                for (int j = j0; j <= last; j += 2) {
+                    const bool two = j + 1 <= last;
+                    float2 *r = bufB;
+#pragma nounroll
+                    for (int ph = it == 0 ? 1 : 0; ph < 2; ++ph) {
+                        float2 *x = bufA, *y = bufB;
+                        if (ph == 0) {
+                            const float *xk = xs + (size_t)k * R + (j - m) * hop;
+                            for (int n = threadIdx.x; n < N; n += blockDim.x) {
+                                const float w = awin[n];
+                                x[n] = make_float2(xk[n] * w, two ? xk[hop + n] * w : 0.f);
+                            }
+                        } else if (it == 0) {
+                            const float2 *r0 = Ck + (size_t)j * F, *r1 = r0 + F;
+                            for (int i = threadIdx.x; i < F; i += blockDim.x)
+                                rtisi_put_pair(x, i, N, r0[i], two ? r1[i] : make_float2(0.f, 0.f));
+                        } else {
+                            x = r == bufB ? bufA : (a.odd > 1 ? bufC : bufB);   // the buffers: as in k_rtisi
+                            y = r;
+                            const bool commit = it == a.iters && j == m;
+                            const float *A0 = Ab + ((size_t)k * M + j) * F, *A1 = A0 + F;
+                            for (int i = threadIdx.x; i < F; i += blockDim.x) {
+                                const float2 zk = r[i], zn = r[i == 0 ? 0 : N - i];
+                                const float2 u = rtisi_project(make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)), A0[i]);
+                                float2 v = make_float2(0.f, 0.f);
+                                if (two) v = rtisi_project(make_float2(0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)), A1[i]);
+                                if (commit) Ck[(size_t)m * F + i] = u;
+                                rtisi_put_pair(x, i, N, u, v);
+                            }
+                        }
+                        __syncthreads();
+                        // one call site for both directions and every source, its uniforms derived here: see k_rtisi.  An instance of
+                        // its own, so that k_rtisi's stays what it was.
+                        int n_ = N, odd_ = a.odd, log2e_ = a.log2e;
+                        asm volatile("" : "+s"(n_), "+s"(odd_), "+s"(log2e_));
+                        r = fft_lds<2>(x, y, n_, odd_, log2e_, ph == 0 ? -1.0f : 1.0f);
+                    }
+                    const float inv = 1.0f / (float)N;
+                    float *o0 = dst + (size_t)slot * N, *o1 = dst + (size_t)(slot < a.LA ? slot + 1 : 0) * N;
+                    for (int n = threadIdx.x; n < N; n += blockDim.x) {
+                        const float w = inv * swin[n];
+                        o0[n] = r[n].x * w;
+                        if (two) o1[n] = r[n].y * w;
+                    }
+                    __syncthreads();   // r is the next load's buffer, dst the next reader's
+                    slot += 2;
+                    if (slot > a.LA) slot -= W;
+                    if (slot > a.LA) slot -= W;   // W == 1
+                }
+            }
+            if (it > 0) { const size_t t = cur; cur = nxt; nxt = t; }
+        }
+        // done_k += f_km; what no later frame reaches is final (hop samples, or all N behind the last frame) and g = 1 there: the signals
+        // are v_k + (y - sum_k v_k) / K, k ascending, with the final samples of all K rings at hand
+        const int nfinal = m == M - 1 ? N : hop;
+        for (int n = threadIdx.x; n < N; n += blockDim.x) {
+            int pos = base + n;
+            if (pos >= R) pos -= R;
+            const int t = hop * m + n, i = t - a.zero_lo;
+            const bool out = xb && n < nfinal && t >= a.zero_lo && t < t_end && i < a.len;
+            float share = 0.f;
+            if (out) {
+                float acc = 0.f;
+                for (int k = 0; k < K; ++k) {
+                    const float *sk = state + (size_t)k * a.state_floats;
+                    const float v = sk[pos] + sk[cur + (size_t)slot_m * N + n];
+                    acc = k ? acc + v : v;
+                }
+                share = (yb[i] - acc) / (float)K;
+            }
+            for (int k = 0; k < K; ++k) {
+                float *sk = state + (size_t)k * a.state_floats;
+                const float v = sk[pos] + sk[cur + (size_t)slot_m * N + n];
+                if (out) xb[(size_t)k * a.len + i] = v + share;
+                sk[pos] = n < nfinal ? 0.f : v;
+            }
+        }
+        base += hop;
+        if (base >= R) base -= R;
+        if (++slot_m > a.LA) slot_m = 0;
+        __syncthreads();
+    }
+}
+
 // Windows and scratch of the iteration, one set per device, serialised on the device by the event scheme of lws_stft.hip.  The
 // windows stay on the device between calls: a call with the windows of the previous one uploads nothing.
 struct GlaCtx {
@@ -612,6 +774,76 @@ extern "C" int lws_rtisi_la_dev(int device, void *C_dev, const float *A_dev, flo
     else
         hipLaunchKernelGGL(k_rtisi<false>, dim3(B), dim3(p.threads), p.lds_bytes, s, C, A_dev, len < 1 ? nullptr : x_dev, wa, ws,
                            static_cast<float *>(c.state.p), a);
+    STFT_TRY(hipGetLastError());
+    return ctx_leave(c, s);
+}
+
+namespace {
+
+// Where the state of k_misi_la lives: as rtisi_plan decides for one source, for K of them and the (K + 1) R floats of the coupling.
+struct MisiLaPlan {
+    size_t source_floats, all_floats, lds_bytes;
+    bool in_lds;
+    int threads;
+};
+MisiLaPlan misi_la_plan(int N, int hop, int LA, int K) {
+    const RtisiPlan one = rtisi_plan(N, hop, LA);
+    MisiLaPlan p;
+    p.source_floats = one.state_floats;
+    p.all_floats = (size_t)K * one.state_floats + ((size_t)K + 1) * ((size_t)N + (size_t)LA * hop);
+    const size_t all = fft_lds_bytes(N) + p.all_floats * sizeof(float);
+    p.in_lds = all <= RTISI_LDS_CAP;
+    p.lds_bytes = p.in_lds ? all : fft_lds_bytes(N);
+    p.threads = one.threads;
+    return p;
+}
+
+}  // namespace
+
+extern "C" int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, float *x_dev, int B, int K, int M, int N,
+                               int fshift, const double *awin, const double *swin, int perfectrec, int iters, int look_ahead,
+                               void *stream) {
+    int rc = check_shape(device, B, M, N, fshift);
+    if (rc) return rc;
+    if (K < 1) return lws::set_error(LWS_ERR_INVALID, "%d sources", K);
+    if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
+    if (look_ahead < 0) return lws::set_error(LWS_ERR_INVALID, "look-ahead of %d frames", look_ahead);
+    if (!C_dev || !y_dev || !awin || !swin) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    const int len = lws_istft_length(M, N, fshift, perfectrec);
+    if (len < 1) return lws::set_error(LWS_ERR_INVALID, "%d frames leave no samples", M);
+    if (iters > 0 && (rc = check_round_trip(M, N, fshift, perfectrec))) return rc;
+    if (B == 0 || (iters == 0 && !x_dev)) return LWS_OK;
+    STFT_TRY(hipSetDevice(device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> lk(g_mu);
+    GlaCtx &c = g_ctx[device];
+    if ((rc = ctx_enter(c, s))) return rc;
+    STFT_TRY(lws::allow_dynamic_lds<&k_misi_la<true>>((int)RTISI_LDS_CAP));
+    STFT_TRY(lws::allow_dynamic_lds<&k_misi_la<false>>(3 * MAXN * (int)sizeof(float2)));
+    if ((rc = upload_window(c.win_a, c.host_a, awin, N, s))) return rc;
+    if ((rc = upload_window(c.win_s, c.host_s, swin, N, s))) return rc;
+    const int F = N / 2 + 1, LA = look_ahead < M - 1 ? look_ahead : M - 1;   // no frame beyond M - 1 to look at
+    const size_t bins = (size_t)B * K * M * F;
+    const MisiLaPlan p = misi_la_plan(N, fshift, LA, K);
+    if (!p.in_lds && (rc = c.state.ensure((size_t)B * p.all_floats * sizeof(float)))) return rc;
+    if (!A_dev && iters > 0) {
+        if ((rc = c.a.ensure(bins * sizeof(float)))) return rc;
+        hipLaunchKernelGGL(k_gla_abs, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, s, static_cast<const float2 *>(C_dev),
+                           static_cast<float *>(c.a.p), bins);
+        A_dev = static_cast<const float *>(c.a.p);
+    }
+    const Factors fc = factor(N);
+    const MisiLaArgs q{{M, N, fc.odd, fc.log2e, fshift, LA, iters, perfectrec ? prepad(N, fshift) : 0, perfectrec ? N - fshift : 0, len,
+                        p.source_floats},
+                       K, p.all_floats};
+    float2 *C = static_cast<float2 *>(C_dev);
+    const float *wa = static_cast<const float *>(c.win_a.p), *ws = static_cast<const float *>(c.win_s.p);
+    if (p.in_lds)
+        hipLaunchKernelGGL(k_misi_la<true>, dim3(B), dim3(p.threads), p.lds_bytes, s, C, A_dev, y_dev, x_dev, wa, ws,
+                           static_cast<float *>(nullptr), q);
+    else
+        hipLaunchKernelGGL(k_misi_la<false>, dim3(B), dim3(p.threads), p.lds_bytes, s, C, A_dev, y_dev, x_dev, wa, ws,
+                           static_cast<float *>(c.state.p), q);
     STFT_TRY(hipGetLastError());
     return ctx_leave(c, s);
 }

@@ -57,6 +57,8 @@ cdef extern from "lws_hip.h" nogil:
                      const double *awin, const double *swin, int perfectrec, int iters, float *x_dev, double *trace, void *stream)
     int lws_rtisi_la_dev(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift,
                          const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream)
+    int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, float *x_dev, int B, int K, int M, int N,
+                        int fshift, const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream)
     int lws_hann(int n, int symmetric, int use_offset, double *out)
     int lws_synthwin(const double *awin, int fsize, int fshift, const double *swin, double *out)
     int lws_weights_shape(int fsize, int fshift, int use_summarized_weights, int *Qprime, int *Q)

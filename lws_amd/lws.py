@@ -492,6 +492,144 @@ def rtisi_la_dev(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitu
     return (out, sig[0] if single else sig) if return_signal else out
 
 
+# --------------------------------------------------------------------------------------------
+# Online MISI: the K sources of a known mixture under a look-ahead -- MISI as RTISI-LA is Griffin-Lim
+# --------------------------------------------------------------------------------------------
+def misi_la(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=None, perfectrec=False, return_signals=False,
+            _perturb=None):
+    """MISI under a look-ahead from the starts S, (K, T, F) or a stack (B, K, T, F), and the real mixture(s) `mixture`, (len,) /
+    (B, len) with len that of istft(S[k]), in fp64 on the host: the definition the device form is held to.  Frame m of every
+    source depends on no input frame later than m + look_ahead and on no mixture sample behind the end of that frame.  On the
+    timeline and with inv, fwd and the cuts of rtisi_la(), the mixture y sitting where istft would put it, and with
+    g_l = (sum_{j <= l} w) / (sum_j w), w = awin swin shifted to the frames that cover a sample (j ascending; 1 where the
+    denominator is 0) -- the share of a sample's overlap-add weight that has entered -- the frames m = 0 .. T-1 are committed in
+    order: every frame up to last = min(m + look_ahead, T - 1) that has not entered does, f_kj = inv(c_kj) for every source;
+    `iterations` times, from the same iterate (Jacobi over frames and sources), y_k = done_k + sum_{j = m..last} f_kj (j ascending),
+    e = g_last y - sum_k y_k (k ascending), c_kj = A_kj X / |X| with X = fwd((y_k + e / K)[fshift j : fshift j + fsize]) (A_kj + 0j
+    where |X| == 0), f_kj = inv(c_kj); then done_k += f_km for good.  Returns c (its magnitudes are A = `magnitudes`, by default
+    |S|); zero iterations return S.  With look_ahead >= T - 1 the first commit is `iterations` steps of misi().  At
+    look_ahead = 0 the last active frame is always transformed from a partial sum and the iteration moves away from a good
+    start, as RTISI itself does.  return_signals: also s_k = done_k + (y - sum_j done_j) / K cut as istft cuts it, (K, len) /
+    (B, K, len), which sum to the mixture.  (_perturb(m, it, b, X) -> X: replaces the (K, last - m + 1, F) stack of projections of
+    one inner iteration; the error model of the tests.)"""
+    n, _ = _gla_args(iterations, 0.0)
+    LA = _look_ahead_arg(look_ahead)
+    S = np.asarray(S)
+    if S.ndim not in (3, 4):
+        raise ValueError('expected (K, T, F) spectrograms of the sources or a (B, K, T, F) stack')
+    A = np.abs(S) if magnitudes is None else np.asarray(magnitudes, dtype=np.float64)
+    if A.shape != S.shape:
+        raise ValueError('magnitudes of shape %s for spectrograms of shape %s' % (A.shape, S.shape))
+    y = np.asarray(mixture, dtype=np.float64)
+    S4, A4, y2 = (S[None], A[None], y[None]) if S.ndim == 3 else (S, A, y)
+    B, K, T, F = S4.shape
+    if K < 1:
+        raise ValueError('no sources')
+    if F != fsize // 2 + 1 or fsize % 2:
+        raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
+    awin, swin = np.asarray(awin, dtype=np.float64), np.squeeze(np.asarray(swin, dtype=np.float64))
+    total = fshift * (T - 1) + fsize
+    keep = np.ones(total)
+    lo, hi = 0, total
+    if perfectrec is True:
+        lo, hi = _perfectrec_prepad(fsize, fshift), total - (fsize - fshift)
+        keep[:lo] = 0.0
+        keep[max(hi, 0):] = 0.0
+        back = stft(np.zeros(max(hi - lo, 0)), fsize, fshift, awin, perfectrec=True).shape[0]
+        if n > 0 and back != T:
+            raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
+    length = max(hi - lo, 0)
+    if y.ndim != S.ndim - 2 or y2.shape != (B, length):
+        raise ValueError('mixture of shape %s for %s spectrograms of %d frames: expected %s' %
+                         (y.shape, S.shape[:-2], T, S.shape[:-3] + (length,)))
+    w = awin * swin
+    den = np.zeros(total)
+    for j in range(T):
+        den[fshift * j: fshift * j + fsize] += w
+    out = S4.astype(np.complex128)
+    sig = np.empty((B, K, length))
+    for b in range(B if (n > 0 or return_signals) else 0):
+        c, done, f, entered = out[b], np.zeros((K, total)), np.zeros((K, T, fsize)), 0
+        yfull, num = np.zeros(total), np.zeros(total)
+        yfull[lo: lo + length] = y2[b]
+        for m in range(T):
+            last = min(m + LA, T - 1)
+            while entered <= last:
+                for k in range(K):
+                    f[k, entered] = swin * np.fft.irfft(c[k, entered], fsize)
+                num[fshift * entered: fshift * entered + fsize] += w
+                entered += 1
+            target = keep * np.where(den != 0, num / np.where(den != 0, den, 1.0), 1.0) * yfull
+            for it in range(1, n + 1):
+                yk = done.copy()
+                for j in range(m, last + 1):
+                    yk[:, fshift * j: fshift * j + fsize] += f[:, j]
+                yk *= keep
+                tot = yk[0].copy()
+                for k in range(1, K):
+                    tot += yk[k]
+                x = yk + keep * (target - tot) / K
+                X = np.stack([[np.fft.rfft(awin * x[k, fshift * j: fshift * j + fsize]) for j in range(m, last + 1)]
+                              for k in range(K)])
+                if _perturb is not None:
+                    X = _perturb(m, it, b, X)
+                c[:, m: last + 1] = _rtisi_project(X, A4[b, :, m: last + 1])
+                for k in range(K):
+                    for j in range(m, last + 1):
+                        f[k, j] = swin * np.fft.irfft(c[k, j], fsize)
+            done[:, fshift * m: fshift * m + fsize] += f[:, m]
+        tot = done[0].copy()
+        for k in range(1, K):
+            tot += done[k]
+        sig[b] = (keep * done + keep * (yfull - tot) / K)[:, lo: lo + length]
+    if n == 0:
+        out = S4
+    if S.ndim == 3:
+        out, sig = out[0], sig[0]
+    return (out, sig) if return_signals else out
+
+
+def misi_la_dev(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=None, perfectrec=False,
+                return_signals=False, device=0):
+    """misi_la() above on the device (lws_gla.hip: float32, one workgroup per mixture marching over the frames, its sources one
+    after another, the state in LDS when it fits; one launch): S (K, T, F) or (B, K, T, F) and mixture (len,) / (B, len), numpy or
+    torch; returns a new complex64 torch tensor (S itself is not modified), and with return_signals also the float32 signals
+    (K, len) / (B, K, len).  Runs on the caller's current torch stream and only enqueues work.  Raises ValueError, as misi_la()
+    does, for a frame count the round trip does not keep."""
+    import torch
+    n, _ = _gla_args(iterations, 0.0)
+    LA = _look_ahead_arg(look_ahead)
+    t = _dev_tensor(S, torch.complex64, device)
+    if t.dim() not in (3, 4):
+        raise ValueError('expected (K, T, F) spectrograms of the sources or a (B, K, T, F) stack')
+    single = t.dim() == 3
+    t4 = (t[None] if single else t).clone()
+    B, K, T, F = t4.shape
+    if K < 1:
+        raise ValueError('no sources')
+    if F != fsize // 2 + 1:
+        raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
+    A = None
+    if magnitudes is not None:
+        A = _dev_tensor(magnitudes, torch.float32, device)
+        if A.shape != t.shape:
+            raise ValueError('magnitudes of shape %s for spectrograms of shape %s' % (tuple(A.shape), tuple(t.shape)))
+    y = _dev_tensor(mixture, torch.float32, device)
+    length = max(_capi.istft_length(T, fsize, fshift, perfectrec), 0)
+    if y.dim() != t.dim() - 2 or tuple(y.shape)[-1:] != (length,) or (not single and y.shape[0] != B):
+        raise ValueError('mixture of shape %s for %s spectrograms of %d frames: expected %s' %
+                         (tuple(y.shape), tuple(t.shape[:-2]), T, tuple(t.shape[:-3]) + (length,)))
+    back = _capi.stft_frames(length, fsize, fshift, perfectrec)
+    if n > 0 and perfectrec and back != T:
+        raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
+    sig = torch.empty((B, K, length), dtype=torch.float32, device=t4.device) if return_signals else None
+    _capi.misi_la_dev(t4.data_ptr(), None if A is None else A.data_ptr(), y.data_ptr(),
+                      None if sig is None or sig.numel() == 0 else sig.data_ptr(), B, K, T, fsize, fshift, awin, swin, perfectrec, n,
+                      LA, device=int(device), stream=torch.cuda.current_stream(t4.device).cuda_stream)
+    out = t4[0] if single else t4
+    return (out, sig[0] if single else sig) if return_signals else out
+
+
 def extspec(S, L, Q):
     """Extended spectrogram: L Hermitian columns each side, Q-1 repeated frames each end (lws.pyx:146-157)."""
     S = np.asarray(S)
@@ -850,6 +988,18 @@ class lws(object):
         return rtisi_la_dev(S, self.fsize, self.fshift, self.awin, self.swin, iterations,
                             look_ahead=self.look_ahead if look_ahead is None else look_ahead, magnitudes=magnitudes,
                             perfectrec=self.perfectrec, return_signal=return_signal, device=self.device)
+
+    def misi_la(self, S, mixture, iterations, look_ahead=None, magnitudes=None, return_signals=False):
+        """Host fp64 form with this object's windows, perfectrec and (look_ahead=None) look-ahead: see the module's misi_la."""
+        return misi_la(S, mixture, self.fsize, self.fshift, self.awin, self.swin, iterations,
+                       look_ahead=self.look_ahead if look_ahead is None else look_ahead, magnitudes=magnitudes,
+                       perfectrec=self.perfectrec, return_signals=return_signals)
+
+    def misi_la_dev(self, S, mixture, iterations, look_ahead=None, magnitudes=None, return_signals=False):
+        """Device form: a new complex64 torch tensor, see the module's misi_la_dev."""
+        return misi_la_dev(S, mixture, self.fsize, self.fshift, self.awin, self.swin, iterations,
+                           look_ahead=self.look_ahead if look_ahead is None else look_ahead, magnitudes=magnitudes,
+                           perfectrec=self.perfectrec, return_signals=return_signals, device=self.device)
 
     def nofuture_lws(self, S, iterations=None, thresholds=None):
         if iterations is None:
