@@ -247,6 +247,32 @@ int lws_misi_dev(int device, void *C_dev, const float *A_dev, const float *y_dev
 int lws_rtisi_la_dev(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift,
                      const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream);
 
+/* Streaming RTISI-LA (lws_gla.hip): lws_rtisi_la_dev for frames that arrive over time, B streams side by side, the state of the
+ * iteration (the overlap-add ring, the windowed inverse frames and the magnitudes of the look_ahead frames still active; per stream)
+ * in device memory owned by the handle.  The rows all calls return, one after another, are what one call with every pushed row
+ * would return under an open end: as lws_rtisi_la_dev, except that with perfectrec the samples behind fshift M read as zero only
+ * in the returned signal, not inside the iteration -- lws_amd.rtisi_la(..., open_end=True) is the fp64 definition.  A stream has
+ * no length limit.
+ *   create : windows as lws_rtisi_la_dev takes them (the handle keeps its own device copy); synchronises once.
+ *   push   : S_dev[B][frames][N/2+1] (complex64) the next `frames` rows of every stream, A_dev[B][frames][N/2+1] (float32) their
+ *            target magnitudes or NULL (|S|).  Commits every frame m with m + look_ahead pushed: *frames_out = max(0, pushed -
+ *            look_ahead) - committed rows, written to C_out_dev[B][frames][N/2+1] (rows beyond *frames_out of each stream are left
+ *            alone), and -- x_out_dev not NULL -- the fshift samples each commit finalises, less what perfectrec cuts at the start, to
+ *            x_out_dev[B][frames fshift], *samples_out of each stream.  Both counts come from the host's counters; the call only
+ *            enqueues work on `stream` and keeps no reference to the caller's buffers.  frames == 0 does nothing.
+ *   finish : commits the rest, C_out_dev[B][look_ahead][N/2+1] and x_out_dev[B][N + look_ahead fshift]; with fewer than look_ahead + 1
+ *            rows pushed, as one call on them would (look_ahead clamped); with none, 0 and 0.  The stream takes no rows after it.
+ * Calls on one handle are ordered by `stream`, or by an event of the handle's if `stream` changes between calls.  A null handle,
+ * frames < 0, a null S_dev with frames > 0, a null C_out_dev with rows to return, a push or finish after finish: LWS_ERR_INVALID,
+ * nothing enqueued.  create: B < 1, iters < 0, look_ahead < 0, null window: LWS_ERR_INVALID; frame sizes: as lws_griffin_lim_dev. */
+typedef struct lws_rtisi_stream lws_rtisi_stream;
+int lws_rtisi_stream_create(int device, int B, int N, int fshift, const double *awin, const double *swin, int perfectrec, int iters,
+                            int look_ahead, lws_rtisi_stream **out);
+int lws_rtisi_stream_push(lws_rtisi_stream *h, const void *S_dev, const float *A_dev, int frames, void *C_out_dev, float *x_out_dev,
+                          int *frames_out, int *samples_out, void *stream);
+int lws_rtisi_stream_finish(lws_rtisi_stream *h, void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out, void *stream);
+void lws_rtisi_stream_destroy(lws_rtisi_stream *h);
+
 /* Online MISI, device resident (lws_gla.hip): MISI under a look-ahead, for the K sources of each of B mixtures -- lws_misi_dev as
  * lws_rtisi_la_dev is lws_griffin_lim_dev.  Frame m of every source depends on no input frame later than m + look_ahead and on no
  * mixture sample behind the end of that frame.  On the timeline and with inv, fwd and the cuts of lws_rtisi_la_dev, the mixture y

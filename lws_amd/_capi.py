@@ -30,7 +30,8 @@ EXPORTS = (
     "lws_batch_lws", "lws_nofuture_lws", "lws_online_lws", "lws_run_lws", "lws_batch_lws_dev",
     "lws_nofuture_lws_dev", "lws_online_lws_dev", "lws_residual_dev", "lws_last_kernel_time",
     "lws_last_kernel_name", "lws_generic_stage", "lws_stft_frames", "lws_istft_length", "lws_stft_dev", "lws_istft_dev", "lws_stft_zp_dev",
-    "lws_consistency_dev", "lws_griffin_lim_dev", "lws_misi_dev", "lws_rtisi_la_dev", "lws_misi_la_dev", "lws_hann", "lws_synthwin", "lws_weights_shape", "lws_create_weights",
+    "lws_consistency_dev", "lws_griffin_lim_dev", "lws_misi_dev", "lws_rtisi_la_dev", "lws_misi_la_dev",
+    "lws_rtisi_stream_create", "lws_rtisi_stream_push", "lws_rtisi_stream_finish", "lws_rtisi_stream_destroy", "lws_hann", "lws_synthwin", "lws_weights_shape", "lws_create_weights",
     "lws_build_asymmetric_windows", "lws_get_thresholds", "lws_plan_create_from_windows", "lws_stream_copy",
     "lws_run_lws_dev", "lws_plan_reserve", "lws_residual", "lws_residual_allreduce_dev", "lws_weights_structure", "lws_multi_plan_create", "lws_multi_plan_destroy",
     "lws_multi_plan_shards", "lws_multi_batch_lws", "lws_multi_run_lws", "lws_multi_residual",
@@ -106,6 +107,11 @@ def load():
     lib.lws_misi_dev.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, vp, vp, vp]
     lib.lws_rtisi_la_dev.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, vp, vp, ip, ip, ip, vp]
     lib.lws_misi_la_dev.argtypes = [ip, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, ip, vp]
+    lib.lws_rtisi_stream_create.argtypes = [ip, ip, ip, ip, vp, vp, ip, ip, ip, C.POINTER(vp)]
+    lib.lws_rtisi_stream_push.argtypes = [vp, vp, vp, ip, vp, vp, C.POINTER(ip), C.POINTER(ip), vp]
+    lib.lws_rtisi_stream_finish.argtypes = [vp, vp, vp, C.POINTER(ip), C.POINTER(ip), vp]
+    lib.lws_rtisi_stream_destroy.argtypes = [vp]
+    lib.lws_rtisi_stream_destroy.restype = None
     lib.lws_hann.argtypes = [ip, ip, ip, vp]
     lib.lws_synthwin.argtypes = [vp, ip, ip, vp, vp]
     lib.lws_weights_shape.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
@@ -514,3 +520,33 @@ def misi_la_dev(C_ptr, A_ptr, y_ptr, x_ptr, B, K, frames, fsize, fshift, awin, s
         raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
     check(load().lws_misi_la_dev(int(device), C_ptr, A_ptr, y_ptr, x_ptr, int(B), int(K), int(frames), int(fsize), int(fshift),
                                  a.ctypes.data, w.ctypes.data, int(bool(perfectrec)), int(iterations), int(look_ahead), stream))
+
+
+def rtisi_stream_create(B, fsize, fshift, awin, swin, perfectrec, iterations, look_ahead, device=0):
+    """A handle (c_void_p) for B RTISI-LA streams; free it with rtisi_stream_destroy."""
+    a, w = _win(awin), _win(swin)
+    if a.shape != (int(fsize),) or w.shape != (int(fsize),):
+        raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
+    h = C.c_void_p()
+    check(load().lws_rtisi_stream_create(int(device), int(B), int(fsize), int(fshift), a.ctypes.data, w.ctypes.data,
+                                         int(bool(perfectrec)), int(iterations), int(look_ahead), C.byref(h)))
+    return h
+
+
+def rtisi_stream_push(h, S_ptr, A_ptr, frames, C_out_ptr, x_out_ptr, stream=None):
+    """The next `frames` rows of every stream (device complex64 [B][frames][F]; A_ptr: device float32 or None).  Returns (rows,
+    samples) committed per stream, written to C_out_ptr [B][frames][F] and x_out_ptr [B][frames*fshift] (or None).  Only enqueues."""
+    nf, ns = C.c_int(0), C.c_int(0)
+    check(load().lws_rtisi_stream_push(h, S_ptr, A_ptr, int(frames), C_out_ptr, x_out_ptr, C.byref(nf), C.byref(ns), stream))
+    return nf.value, ns.value
+
+
+def rtisi_stream_finish(h, C_out_ptr, x_out_ptr, stream=None):
+    """Commits what is left: C_out_ptr [B][look_ahead][F], x_out_ptr [B][fsize + look_ahead*fshift] (or None).  Returns (rows, samples)."""
+    nf, ns = C.c_int(0), C.c_int(0)
+    check(load().lws_rtisi_stream_finish(h, C_out_ptr, x_out_ptr, C.byref(nf), C.byref(ns), stream))
+    return nf.value, ns.value
+
+
+def rtisi_stream_destroy(h):
+    load().lws_rtisi_stream_destroy(h)

@@ -305,6 +305,41 @@ def lws_misi_la_dev(int device, C_dev, A_dev, y_dev, x_dev, int B, int K, int M,
     return rc
 
 
+def lws_rtisi_stream_create(int device, int B, int N, int fshift, awin, swin, int perfectrec, int iters, int look_ahead, out_ref):
+    cdef c.lws_rtisi_stream *h = NULL
+    cdef uintptr_t a = _addr(awin), w = _addr(swin)
+    cdef int rc
+    with nogil:
+        rc = c.lws_rtisi_stream_create(device, B, N, fshift, <const double *>a, <const double *>w, perfectrec, iters, look_ahead, &h)
+    out_ref._obj.value = <uintptr_t>h if h != NULL else None
+    return rc
+
+
+def lws_rtisi_stream_push(h, S_dev, A_dev, int frames, C_out_dev, x_out_dev, frames_out, samples_out, stream):
+    cdef uintptr_t p = _addr(h), sd = _addr(S_dev), ad = _addr(A_dev), cd = _addr(C_out_dev), xd = _addr(x_out_dev)
+    cdef uintptr_t fo = _addr(frames_out), so = _addr(samples_out), st = _addr(stream)
+    cdef int rc
+    with nogil:
+        rc = c.lws_rtisi_stream_push(<c.lws_rtisi_stream *>p, <const void *>sd, <const float *>ad, frames, <void *>cd, <float *>xd,
+                                     <int *>fo, <int *>so, <void *>st)
+    return rc
+
+
+def lws_rtisi_stream_finish(h, C_out_dev, x_out_dev, frames_out, samples_out, stream):
+    cdef uintptr_t p = _addr(h), cd = _addr(C_out_dev), xd = _addr(x_out_dev)
+    cdef uintptr_t fo = _addr(frames_out), so = _addr(samples_out), st = _addr(stream)
+    cdef int rc
+    with nogil:
+        rc = c.lws_rtisi_stream_finish(<c.lws_rtisi_stream *>p, <void *>cd, <float *>xd, <int *>fo, <int *>so, <void *>st)
+    return rc
+
+
+def lws_rtisi_stream_destroy(h):
+    cdef uintptr_t p = _addr(h)
+    with nogil:
+        c.lws_rtisi_stream_destroy(<c.lws_rtisi_stream *>p)
+
+
 def lws_hann(int n, int symmetric, int use_offset, out):
     cdef uintptr_t o = _addr(out)
     return c.lws_hann(n, symmetric, use_offset, <double *>o)

@@ -535,6 +535,178 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_misi_la(float2 *C, const 
     }
 }
 
+// ---- Streaming RTISI-LA: the commit steps of k_rtisi, a few per launch, with the state kept in device memory between launches.  One
+// workgroup per stream runs q.nsteps steps.  Everything is counted from the launch's first step: frame 0 is the frame that step
+// commits, sample 0 its first sample, so no index grows with the length of a stream.  The frames 0 .. nheld-1 entered in earlier
+// calls: their rows (A, and S where it is still read) are in the handle's `held` buffers, the rows of the later frames in the caller's
+// chunk.  While the stream is open every step looks at LA frames ahead (Mrel = nsteps + LA); the closing launch knows the end
+// (Mrel = what is left) and cuts the emitted samples there, never the iteration: the stream computes rtisi_la(..., open_end=True).
+// State per stream in device memory: ring | fcur | (scratch placement only) the other frame buffer.  IN_LDS copies ring and fcur in on
+// entry and out on exit and has fnxt in LDS alone; otherwise the kernel works in place and q.cur says which buffer is fcur.  Pairing,
+// buffers, arithmetic and barriers are k_rtisi's, step for step; the loops that enclose a barrier run over kernel arguments and
+// counters derived from them alone.
+struct RtisiHeld {
+    const float2 *S;     // [B][rows][F]: start rows of the held frames (read by pass 0 of the first launch, and without iterations)
+    const float *A;      // [B][rows][F]: magnitudes of the held frames
+    float2 *S_next;      // where the rows of the frames still active after this launch go (null: not kept)
+    float *A_next;
+};
+struct RtisiStreamArgs {
+    int N, odd, log2e, hop, LA, iters;
+    int nsteps, Mrel;            // steps of this launch; frames from its first step to the end of the stream (nsteps + LA while open)
+    int closing, origin;         // the launch that ends the stream; the first step is frame 0 of the stream
+    int zero_lo, emit_end;       // the lead-in cut and the end of the emitted samples, from the first sample of the first step
+    int base, slot_m, cur;       // ring offset and slot of the first step's frame; which frame buffer is fcur (scratch placement)
+    int nheld, held_rows;        // held frames in front of the chunk's; row stride of a stream in the held buffers
+    int chunk_rows, out_rows, out_samples;   // rows per stream of S / A, of Cout, samples per stream of xout
+    size_t state_floats;         // stride of a stream in `state`
+};
+
+template <class T> __device__ __forceinline__ const T *rtisi_row(const T *held, const T *chunk, int j, int nheld, int F) {
+    return j < nheld ? held + (size_t)j * F : chunk + (size_t)(j - nheld) * F;
+}
+
+template <bool IN_LDS>
+__global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi_stream(const float2 *S, const float *A, float2 *Cout, float *xout,
+                                                                    const float *awin, const float *swin, float *state, RtisiHeld h,
+                                                                    RtisiStreamArgs q) {
+    extern __shared__ float2 lds[];
+    const int b = blockIdx.x, N = q.N, F = N / 2 + 1, hop = q.hop, W = q.LA + 1, R = N + q.LA * hop;
+    const RtisiArgs a{q.Mrel, N, q.odd, q.log2e, hop, q.LA, q.iters, q.zero_lo, 0, 0, 0};   // what rtisi_sample reads
+    constexpr int no_end = 0x7fffffff;   // the iteration sees no tail cut
+    float2 *bufA = lds, *bufB = lds + N, *bufC = lds + 2 * N;   // as in k_rtisi
+    float *gs = state + (size_t)b * q.state_floats;
+    float *ls = IN_LDS ? reinterpret_cast<float *>(lds + (q.odd > 1 ? 3 : 2) * N) : gs;
+    float *ring = ls;
+    int cur = R, nxt = R + W * N;   // fcur and fnxt within ls
+    if (IN_LDS) {
+        for (int i = threadIdx.x; i < R + W * N; i += blockDim.x) ls[i] = gs[i];
+    } else if (q.cur) {
+        cur = nxt;
+        nxt = R;
+    }
+    // where the rows of this stream start (offsets and, for the frame buffers, indices: pointers held across the loops cost SGPR pairs)
+    const size_t held_at = (size_t)b * q.held_rows * F, chunk_at = (size_t)b * q.chunk_rows * F;
+    __syncthreads();
+    int base = q.base, slot_m = q.slot_m;   // slot_m: the slot of frame m
+    for (int m = 0; m < q.nsteps; ++m) {
+        const int last = m + q.LA < q.Mrel - 1 ? m + q.LA : q.Mrel - 1;
+        const bool origin = q.origin && m == 0;   // k_rtisi's m == 0: the LA + 1 first frames enter together
+        for (int it = 0; it <= q.iters; ++it) {
+            const float *fcur = ls + cur;
+            float *dst = ls + (it == 0 ? cur : nxt);
+            const int j0 = it > 0 ? m : origin ? 0 : m + q.LA;
+            int slot = it > 0 || origin ? slot_m : slot_m == 0 ? q.LA : slot_m - 1;
+            for (int j = j0; j <= last; j += 2) {
+                const bool two = j + 1 <= last;
+                float2 *r = bufB;
+#pragma nounroll
+                for (int ph = it == 0 ? 1 : 0; ph < 2; ++ph) {
+                    float2 *x = bufA, *y = bufB;
+                    if (ph == 0) {
+                        for (int n = threadIdx.x; n < N; n += blockDim.x) {
+                            const float w = awin[n];
+                            const float re = rtisi_sample(ring, fcur, j * hop + n, m, last, slot_m, base, R, no_end, a) * w;
+                            const float im = two ? rtisi_sample(ring, fcur, (j + 1) * hop + n, m, last, slot_m, base, R, no_end, a) * w : 0.f;
+                            x[n] = make_float2(re, im);
+                        }
+                    } else if (it == 0) {
+                        const float2 *Sh = h.S + held_at, *Sc = S + chunk_at;
+                        const float2 *r0 = rtisi_row(Sh, Sc, j, q.nheld, F), *r1 = two ? rtisi_row(Sh, Sc, j + 1, q.nheld, F) : r0;
+                        for (int k = threadIdx.x; k < F; k += blockDim.x)
+                            rtisi_put_pair(x, k, N, r0[k], two ? r1[k] : make_float2(0.f, 0.f));
+                    } else {
+                        x = r == bufB ? bufA : (q.odd > 1 ? bufC : bufB);   // the buffers: as in k_rtisi
+                        y = r;
+                        const bool commit = it == q.iters && j == m;
+                        const float *Ah = h.A + held_at, *Ac = A + chunk_at;
+                        float2 *Co = Cout + (size_t)b * q.out_rows * F;
+                        const float *A0 = rtisi_row(Ah, Ac, j, q.nheld, F), *A1 = two ? rtisi_row(Ah, Ac, j + 1, q.nheld, F) : A0;
+                        for (int k = threadIdx.x; k < F; k += blockDim.x) {
+                            const float2 zk = r[k], zn = r[k == 0 ? 0 : N - k];
+                            const float2 u = rtisi_project(make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)), A0[k]);
+                            float2 v = make_float2(0.f, 0.f);
+                            if (two) v = rtisi_project(make_float2(0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)), A1[k]);
+                            if (commit) Co[(size_t)m * F + k] = u;
+                            rtisi_put_pair(x, k, N, u, v);
+                        }
+                    }
+                    __syncthreads();
+                    // one call site for both directions, its uniforms derived here: see k_rtisi.  An instance of its own, so that
+                    // k_rtisi's and k_misi_la's stay what they were.
+                    int n_ = N, odd_ = q.odd, log2e_ = q.log2e;
+                    asm volatile("" : "+s"(n_), "+s"(odd_), "+s"(log2e_));
+                    r = fft_lds<3>(x, y, n_, odd_, log2e_, ph == 0 ? -1.0f : 1.0f);
+                }
+                const float inv = 1.0f / (float)N;
+                float *o0 = dst + (size_t)slot * N, *o1 = dst + (size_t)(slot < q.LA ? slot + 1 : 0) * N;
+                for (int n = threadIdx.x; n < N; n += blockDim.x) {
+                    const float w = inv * swin[n];
+                    o0[n] = r[n].x * w;
+                    if (two) o1[n] = r[n].y * w;
+                }
+                __syncthreads();   // r is the next load's buffer, dst the next reader's
+                slot += 2;
+                if (slot > q.LA) slot -= W;
+                if (slot > q.LA) slot -= W;   // W == 1
+            }
+            if (it > 0) { const int t = cur; cur = nxt; nxt = t; }
+        }
+        if (q.iters == 0) {   // nothing was projected: the committed row is the start row
+            const float2 *r0 = rtisi_row(h.S + held_at, S + chunk_at, m, q.nheld, F);
+            float2 *Co = Cout + (size_t)b * q.out_rows * F;
+            for (int k = threadIdx.x; k < F; k += blockDim.x) Co[(size_t)m * F + k] = r0[k];
+        }
+        // done += f_m; what no later frame reaches is final: hop samples (what lies behind the last frame of the stream: below)
+        const float *fm = ls + cur + (size_t)slot_m * N;
+        float *xb = xout ? xout + (size_t)b * q.out_samples : nullptr;
+        for (int n = threadIdx.x; n < N; n += blockDim.x) {
+            int pos = base + n;
+            if (pos >= R) pos -= R;
+            const float v = ring[pos] + fm[n];
+            const int t = hop * m + n;
+            if (n < hop) {
+                if (xb && t >= q.zero_lo && t < q.emit_end) xb[t - q.zero_lo] = v;
+                ring[pos] = 0.f;
+            } else {
+                ring[pos] = v;
+            }
+        }
+        base += hop;
+        if (base >= R) base -= R;
+        if (++slot_m > q.LA) slot_m = 0;
+        __syncthreads();
+    }
+    if (q.closing && xout) {   // the N - hop samples behind the last commit: final now, also when this launch has no step (LA == 0)
+        float *xb = xout + (size_t)b * q.out_samples;
+        for (int d = threadIdx.x; d < N - hop; d += blockDim.x) {
+            int pos = base + d;
+            if (pos >= R) pos -= R;
+            const int t = hop * q.nsteps + d;
+            if (t >= q.zero_lo && t < q.emit_end) xb[t - q.zero_lo] = ring[pos];
+        }
+    }
+    if (IN_LDS) {
+        for (int i = threadIdx.x; i < R; i += blockDim.x) gs[i] = ring[i];
+        for (int i = threadIdx.x; i < W * N; i += blockDim.x) gs[R + i] = ls[cur + i];
+    }
+    const float2 *Sh = h.S + held_at, *Sc = S + chunk_at;
+    const float *Ah = h.A + held_at, *Ac = A + chunk_at;
+    // the rows of the frames nsteps .. nsteps + LA - 1, active in the next launch, into the other held buffer
+    for (int i = 0; i < q.LA; ++i) {
+        if (h.A_next) {
+            const float *src = rtisi_row(Ah, Ac, q.nsteps + i, q.nheld, F);
+            float *to = h.A_next + held_at + (size_t)i * F;
+            for (int k = threadIdx.x; k < F; k += blockDim.x) to[k] = src[k];
+        }
+        if (h.S_next) {
+            const float2 *src = rtisi_row(Sh, Sc, q.nsteps + i, q.nheld, F);
+            float2 *to = h.S_next + held_at + (size_t)i * F;
+            for (int k = threadIdx.x; k < F; k += blockDim.x) to[k] = src[k];
+        }
+    }
+}
+
 // Windows and scratch of the iteration, one set per device, serialised on the device by the event scheme of lws_stft.hip.  The
 // windows stay on the device between calls: a call with the windows of the previous one uploads nothing.
 struct GlaCtx {
@@ -846,4 +1018,215 @@ extern "C" int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, cons
                            static_cast<float *>(c.state.p), q);
     STFT_TRY(hipGetLastError());
     return ctx_leave(c, s);
+}
+
+// ---- Streaming RTISI-LA: the handle.  Everything a stream carries between calls is its own -- state, held rows, windows, the
+// magnitudes of a chunk given without them -- so streams share nothing with each other or with the calls on GlaCtx.
+struct lws_rtisi_stream {
+    int device = 0, B = 0, N = 0, hop = 0, LA = 0, iters = 0, perfectrec = 0;
+    RtisiPlan plan{};
+    size_t state_floats = 0;              // per stream: ring, fcur and, with the scratch placement, the other frame buffer
+    Scratch state, held_s[2], held_a[2], abuf, win_a, win_s;
+    long long entered = 0, committed = 0; // frames pushed, frames committed
+    int base = 0, slot = 0, cur = 0;      // of the next step: ring offset, slot of its frame, which frame buffer is fcur
+    int held = 0;                         // which held buffer is current
+    bool ran = false, finished = false;
+    hipEvent_t last = nullptr;            // the event scheme of GlaCtx, for a caller that changes streams between calls
+    hipStream_t last_stream = nullptr;
+    bool busy = false;
+    std::mutex mu;
+};
+
+namespace {
+
+int stream_enter(lws_rtisi_stream &h, hipStream_t s) {
+    if (h.busy && s != h.last_stream) STFT_TRY(hipStreamWaitEvent(s, h.last, 0));
+    return LWS_OK;
+}
+int stream_leave(lws_rtisi_stream &h, hipStream_t s) {
+    STFT_TRY(hipEventRecord(h.last, s));
+    h.busy = true;
+    h.last_stream = s;
+    return LWS_OK;
+}
+
+// rows [at, at + frames) of the held buffers from a chunk: the frames that arrive before the first commit can run
+int stream_stash(lws_rtisi_stream &h, const float2 *S, const float *A, int frames, hipStream_t s) {
+    const size_t F = (size_t)h.N / 2 + 1, at = (size_t)h.entered;
+    STFT_TRY(hipMemcpy2DAsync(static_cast<float2 *>(h.held_s[h.held].p) + at * F, (size_t)h.LA * F * sizeof(float2), S,
+                              (size_t)frames * F * sizeof(float2), (size_t)frames * F * sizeof(float2), h.B, hipMemcpyDeviceToDevice, s));
+    if (A)
+        STFT_TRY(hipMemcpy2DAsync(static_cast<float *>(h.held_a[h.held].p) + at * F, (size_t)h.LA * F * sizeof(float), A,
+                                  (size_t)frames * F * sizeof(float), (size_t)frames * F * sizeof(float), h.B, hipMemcpyDeviceToDevice, s));
+    return LWS_OK;
+}
+
+// the commit steps committed .. committed + nsteps - 1; M < 0 while the stream is open, the frame count at its end
+int stream_launch(lws_rtisi_stream &h, const float2 *S, const float *A, int frames, float2 *C_out, float *x_out, int out_rows,
+                  int out_samples, int nsteps, long long M, hipStream_t s) {
+    const bool closing = M >= 0;
+    const int LA = (closing && !h.ran) ? (int)M - 1 : h.LA;   // an end before the first commit: no frame beyond M - 1 to look at
+    const RtisiPlan p = rtisi_plan(h.N, h.hop, LA);
+    const Factors fc = factor(h.N);
+    const long long t0 = (long long)h.hop * h.committed, lo = h.perfectrec ? prepad(h.N, h.hop) : 0;
+    RtisiStreamArgs q{};
+    q.N = h.N; q.odd = fc.odd; q.log2e = fc.log2e; q.hop = h.hop; q.LA = LA; q.iters = h.iters;
+    q.nsteps = nsteps;
+    q.Mrel = closing ? (int)(M - h.committed) : nsteps + LA;
+    q.closing = closing;
+    q.origin = h.committed == 0;
+    q.zero_lo = lo > t0 ? (int)(lo - t0) : 0;
+    q.emit_end = closing && h.perfectrec ? (int)((long long)h.hop * M - t0) : 0x7fffffff;
+    q.base = h.base; q.slot_m = h.slot; q.cur = h.cur;
+    q.nheld = h.ran ? h.LA : (int)h.entered;   // before the first launch: the stashed frames (the chunk's are not counted yet)
+    q.held_rows = h.LA;
+    q.chunk_rows = frames; q.out_rows = out_rows; q.out_samples = out_samples;
+    q.state_floats = h.state_floats;
+    const int nxt = h.held ^ 1;
+    const RtisiHeld held{static_cast<const float2 *>(h.held_s[h.held].p), static_cast<const float *>(h.held_a[h.held].p),
+                         closing || h.iters > 0 ? nullptr : static_cast<float2 *>(h.held_s[nxt].p),
+                         closing || h.iters == 0 ? nullptr : static_cast<float *>(h.held_a[nxt].p)};
+    const float *wa = static_cast<const float *>(h.win_a.p), *ws = static_cast<const float *>(h.win_s.p);
+    float *st = static_cast<float *>(h.state.p);
+    if (p.in_lds)
+        hipLaunchKernelGGL(k_rtisi_stream<true>, dim3(h.B), dim3(p.threads), p.lds_bytes, s, S, A, C_out, x_out, wa, ws, st, held, q);
+    else
+        hipLaunchKernelGGL(k_rtisi_stream<false>, dim3(h.B), dim3(p.threads), p.lds_bytes, s, S, A, C_out, x_out, wa, ws, st, held, q);
+    STFT_TRY(hipGetLastError());
+    const int R = h.N + LA * h.hop;
+    h.base = (int)(((long long)h.base + (long long)h.hop * nsteps) % R);
+    h.slot = (int)(((long long)h.slot + nsteps) % (LA + 1));
+    h.cur ^= (int)(((long long)h.iters * nsteps) & 1);
+    h.held = nxt;
+    h.committed += nsteps;
+    h.ran = true;
+    return LWS_OK;
+}
+
+}  // namespace
+
+extern "C" int lws_rtisi_stream_create(int device, int B, int N, int fshift, const double *awin, const double *swin, int perfectrec,
+                                       int iters, int look_ahead, lws_rtisi_stream **out) {
+    if (!out) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    *out = nullptr;
+    int rc = check_shape(device, B, 1, N, fshift);
+    if (rc) return rc;
+    if (B < 1) return lws::set_error(LWS_ERR_INVALID, "%d streams", B);
+    if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
+    if (look_ahead < 0) return lws::set_error(LWS_ERR_INVALID, "look-ahead of %d frames", look_ahead);
+    if (!awin || !swin) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    if ((long long)(look_ahead + 2) * fshift + N > 0x7fffffffLL / 2)
+        return lws::set_error(LWS_ERR_UNSUPPORTED, "look-ahead of %d frames", look_ahead);
+    STFT_TRY(hipSetDevice(device));
+    STFT_TRY(lws::allow_dynamic_lds<&k_rtisi_stream<true>>((int)RTISI_LDS_CAP));
+    STFT_TRY(lws::allow_dynamic_lds<&k_rtisi_stream<false>>(3 * MAXN * (int)sizeof(float2)));
+    lws_rtisi_stream *h = new lws_rtisi_stream;
+    h->device = device; h->B = B; h->N = N; h->hop = fshift; h->LA = look_ahead; h->iters = iters; h->perfectrec = perfectrec ? 1 : 0;
+    h->plan = rtisi_plan(N, fshift, look_ahead);
+    const size_t F = (size_t)N / 2 + 1, frame_floats = (size_t)(look_ahead + 1) * N;
+    h->state_floats = h->plan.in_lds ? h->plan.state_floats - frame_floats : h->plan.state_floats;
+    const size_t state_bytes = (size_t)B * h->state_floats * sizeof(float), rows = (size_t)B * look_ahead * F;
+    std::vector<float> wa(N), ws(N);
+    for (int i = 0; i < N; ++i) { wa[i] = (float)awin[i]; ws[i] = (float)swin[i]; }
+    rc = h->state.ensure(state_bytes);
+    if (!rc) rc = h->win_a.ensure((size_t)N * sizeof(float));
+    if (!rc) rc = h->win_s.ensure((size_t)N * sizeof(float));
+    if (!rc) rc = h->held_s[0].ensure(rows * sizeof(float2));
+    if (!rc && iters == 0) rc = h->held_s[1].ensure(rows * sizeof(float2));
+    if (!rc && iters > 0) rc = h->held_a[0].ensure(rows * sizeof(float));
+    if (!rc && iters > 0) rc = h->held_a[1].ensure(rows * sizeof(float));
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipEventCreateWithFlags(&h->last, hipEventDisableTiming);
+    if (!rc && e == hipSuccess) e = hipMemset(h->state.p, 0, state_bytes);
+    if (!rc && e == hipSuccess) e = hipMemcpy(h->win_a.p, wa.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice);
+    if (!rc && e == hipSuccess) e = hipMemcpy(h->win_s.p, ws.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice);
+    if (!rc && e == hipSuccess) e = hipDeviceSynchronize();   // the state is zero before any stream of the caller's touches it
+    if (!rc && e != hipSuccess) rc = lws::set_error(LWS_ERR_HIP, "creating a stream's state failed: %s", hipGetErrorString(e));
+    if (rc) {
+        lws_rtisi_stream_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return LWS_OK;
+}
+
+extern "C" int lws_rtisi_stream_push(lws_rtisi_stream *h, const void *S_dev, const float *A_dev, int frames, void *C_out_dev,
+                                     float *x_out_dev, int *frames_out, int *samples_out, void *stream) {
+    if (frames_out) *frames_out = 0;
+    if (samples_out) *samples_out = 0;
+    if (!h) return lws::set_error(LWS_ERR_INVALID, "null stream handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (frames < 0) return lws::set_error(LWS_ERR_INVALID, "%d frames", frames);
+    if (h->finished) return lws::set_error(LWS_ERR_INVALID, "push after finish");
+    if (frames == 0) return LWS_OK;
+    if (!S_dev) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    if (((long long)frames + h->LA + 2) * h->hop + h->N > 0x7fffffffLL)
+        return lws::set_error(LWS_ERR_UNSUPPORTED, "%d frames in one push", frames);
+    const long long entered = h->entered + frames;
+    const long long nsteps = entered > h->LA ? entered - h->LA - h->committed : 0;
+    if (nsteps > 0 && !C_out_dev) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    STFT_TRY(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = stream_enter(*h, s);
+    if (rc) return rc;
+    const float2 *S = static_cast<const float2 *>(S_dev);
+    const size_t bins = (size_t)h->B * frames * (h->N / 2 + 1);
+    if (!A_dev && h->iters > 0) {   // |S| by the kernel lws_rtisi_la_dev takes it from
+        if ((rc = h->abuf.ensure(bins * sizeof(float)))) return rc;
+        hipLaunchKernelGGL(k_gla_abs, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, s, S, static_cast<float *>(h->abuf.p), bins);
+        A_dev = static_cast<const float *>(h->abuf.p);
+    }
+    if (h->iters == 0) A_dev = nullptr;
+    if (nsteps == 0) {
+        if ((rc = stream_stash(*h, S, A_dev, frames, s))) return rc;
+    } else {
+        const long long t0 = (long long)h->hop * h->committed, lo = h->perfectrec ? prepad(h->N, h->hop) : 0;
+        const long long from = lo > t0 ? lo : t0, to = (long long)h->hop * (h->committed + nsteps);
+        if ((rc = stream_launch(*h, S, A_dev, frames, static_cast<float2 *>(C_out_dev), x_out_dev, frames, frames * h->hop, (int)nsteps,
+                                -1, s)))
+            return rc;
+        if (frames_out) *frames_out = (int)nsteps;
+        if (samples_out) *samples_out = to > from ? (int)(to - from) : 0;
+    }
+    h->entered = entered;
+    return stream_leave(*h, s);
+}
+
+extern "C" int lws_rtisi_stream_finish(lws_rtisi_stream *h, void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out,
+                                       void *stream) {
+    if (frames_out) *frames_out = 0;
+    if (samples_out) *samples_out = 0;
+    if (!h) return lws::set_error(LWS_ERR_INVALID, "null stream handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->finished) return lws::set_error(LWS_ERR_INVALID, "finish after finish");
+    const long long M = h->entered, nsteps = M - h->committed;
+    // no step left (nothing pushed, or look_ahead == 0): only the samples behind the last commit, which perfectrec cuts
+    if (nsteps == 0 && (M == 0 || h->perfectrec || !x_out_dev)) {
+        h->finished = true;
+        if (samples_out && M > 0 && !h->perfectrec) *samples_out = h->N - h->hop;
+        return LWS_OK;
+    }
+    if (nsteps > 0 && !C_out_dev) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    STFT_TRY(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = stream_enter(*h, s);
+    if (rc) return rc;
+    const long long t0 = (long long)h->hop * h->committed, lo = h->perfectrec ? prepad(h->N, h->hop) : 0;
+    const long long from = lo > t0 ? lo : t0, to = h->perfectrec ? (long long)h->hop * M : (long long)h->hop * (M - 1) + h->N;
+    if ((rc = stream_launch(*h, nullptr, nullptr, 0, static_cast<float2 *>(C_out_dev), x_out_dev, h->LA, h->N + h->LA * h->hop,
+                            (int)nsteps, M, s)))
+        return rc;
+    h->finished = true;
+    if (frames_out) *frames_out = (int)nsteps;
+    if (samples_out) *samples_out = to > from ? (int)(to - from) : 0;
+    return stream_leave(*h, s);
+}
+
+extern "C" void lws_rtisi_stream_destroy(lws_rtisi_stream *h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    for (Scratch *b : {&h->state, &h->held_s[0], &h->held_s[1], &h->held_a[0], &h->held_a[1], &h->abuf, &h->win_a, &h->win_s})
+        if (b->p) (void)hipFree(b->p);
+    if (h->last) (void)hipEventDestroy(h->last);
+    delete h;
 }

@@ -59,6 +59,15 @@ cdef extern from "lws_hip.h" nogil:
                          const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream)
     int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, float *x_dev, int B, int K, int M, int N,
                         int fshift, const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream)
+    ctypedef struct lws_rtisi_stream:
+        pass
+    int lws_rtisi_stream_create(int device, int B, int N, int fshift, const double *awin, const double *swin, int perfectrec,
+                                int iters, int look_ahead, lws_rtisi_stream **out)
+    int lws_rtisi_stream_push(lws_rtisi_stream *h, const void *S_dev, const float *A_dev, int frames, void *C_out_dev,
+                              float *x_out_dev, int *frames_out, int *samples_out, void *stream)
+    int lws_rtisi_stream_finish(lws_rtisi_stream *h, void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out,
+                                void *stream)
+    void lws_rtisi_stream_destroy(lws_rtisi_stream *h)
     int lws_hann(int n, int symmetric, int use_offset, double *out)
     int lws_synthwin(const double *awin, int fsize, int fshift, const double *swin, double *out)
     int lws_weights_shape(int fsize, int fshift, int use_summarized_weights, int *Qprime, int *Q)

@@ -395,7 +395,7 @@ def _rtisi_project(X, A):
 
 
 def rtisi_la(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=None, perfectrec=False, return_signal=False,
-             _perturb=None):
+             _perturb=None, open_end=False):
     """Real-Time Iterative Spectrogram Inversion with Look-Ahead from the start S, (T, F) or a stack (B, T, F), in fp64 on the
     host: the definition the device form is held to.  Frame m of the result depends on no input frame later than m + look_ahead.
     With inv(c) = swin irfft(c) and fwd(y) = rfft(awin y) on the timeline of fshift (T - 1) + fsize samples -- where, with
@@ -405,6 +405,10 @@ def rtisi_la(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=
     X_j = fwd(y[fshift j : fshift j + fsize]) (A_j + 0j where |X_j| == 0), f_j = inv(c_j); then done += f_m for good.  Returns c
     (its magnitudes are A = `magnitudes`, by default |S|); zero iterations return S.  With look_ahead >= T - 1 the first commit
     is `iterations` plain Griffin-Lim steps.  return_signal: also done cut as istft cuts it, which is istft(c), (len,) / (B, len).
+    open_end: nothing inside the iteration depends on where the spectrogram ends -- with perfectrec the samples from fshift T on are
+    not read as zero (the lead-in still is, and the returned signal is still cut as istft cuts it), and the frame count need not be
+    one the round trip keeps -- so the rows [:T1 - look_ahead] of a run on S[:T1] are those of a run on any longer S: what a stream
+    (RtisiLaStream) computes.  Without perfectrec it changes nothing.
     (_perturb(m, it, b, X) -> X: replaces the stacked projections of one inner iteration; the error model of the tests.)"""
     n, _ = _gla_args(iterations, 0.0)
     LA = _look_ahead_arg(look_ahead)
@@ -424,10 +428,11 @@ def rtisi_la(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=
     if perfectrec is True:
         lo, hi = _perfectrec_prepad(fsize, fshift), total - (fsize - fshift)
         keep[:lo] = 0.0
-        keep[max(hi, 0):] = 0.0
-        back = stft(np.zeros(max(hi - lo, 0)), fsize, fshift, awin, perfectrec=True).shape[0]
-        if n > 0 and back != T:
-            raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
+        if not open_end:
+            keep[max(hi, 0):] = 0.0
+            back = stft(np.zeros(max(hi - lo, 0)), fsize, fshift, awin, perfectrec=True).shape[0]
+            if n > 0 and back != T:
+                raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
     S3, A3 = (S[None], A[None]) if S.ndim == 2 else (S, A)
     out = S3.astype(np.complex128)
     sig = np.empty((S3.shape[0], max(hi - lo, 0)))
@@ -456,6 +461,90 @@ def rtisi_la(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=
     if n == 0:
         out = S
     return (out, sig) if return_signal else out
+
+
+class RtisiLaStream(object):
+    """rtisi_la_dev() for frames that arrive over time (k_rtisi_stream of lws_gla.hip): push() takes the next rows, (Tc, F) -- or
+    (B, Tc, F) for `batch`=B streams side by side -- numpy or torch, and returns the rows that could be committed, a new complex64
+    torch tensor (n, F) / (B, n, F): frame m is committed once frame m + look_ahead has been pushed, so n may be 0.  finish() returns
+    the remaining look_ahead frames and ends the stream.  With return_signal both also return the float32 samples those commits
+    finalised, (k,) / (B, k).  Everything returned, concatenated, is rtisi_la(everything pushed, ..., open_end=True) (and its signal):
+    however the rows are cut into chunks, bit for bit.  The state lives on the device between calls; a call runs on the caller's current
+    torch stream and only enqueues work.  magnitudes: the targets of the pushed rows (default |S|).  iterations=0 returns the pushed rows
+    themselves, with the same latency.  close() frees the device state (also on deletion)."""
+
+    def __init__(self, fsize, fshift, awin, swin, iterations, look_ahead=3, perfectrec=False, batch=None, return_signal=False, device=0):
+        self._h = None
+        n, _ = _gla_args(iterations, 0.0)
+        self.look_ahead = _look_ahead_arg(look_ahead)
+        if batch is not None and (int(batch) != batch or batch < 1):
+            raise ValueError('batch must be None or a positive integer, got %r' % (batch,))
+        if fsize % 2:
+            raise ValueError('Odd ffts not supported.')
+        self.fsize, self.fshift, self.iterations, self.perfectrec = int(fsize), int(fshift), n, perfectrec is True
+        self.batch, self.return_signal, self.device = None if batch is None else int(batch), bool(return_signal), int(device)
+        self._B, self._F = 1 if batch is None else int(batch), int(fsize) // 2 + 1
+        self.finished = False
+        swin = np.squeeze(np.asarray(swin, dtype=np.float64))
+        self._h = _capi.rtisi_stream_create(self._B, fsize, fshift, awin, swin, self.perfectrec, n, self.look_ahead, device=self.device)
+
+    def _returns(self, out, sig, nf, ns):
+        out = out[:, :nf]
+        if self.batch is None:
+            out = out[0]
+        if not self.return_signal:
+            return out
+        sig = sig[:, :ns]
+        return out, (sig[0] if self.batch is None else sig)
+
+    def push(self, S, magnitudes=None):
+        import torch
+        if self._h is None or self.finished:
+            raise ValueError('push on a stream that has finished or been closed')
+        t = _dev_tensor(S, torch.complex64, self.device)
+        want = 2 if self.batch is None else 3
+        if t.dim() != want or t.shape[-1] != self._F or (self.batch is not None and t.shape[0] != self._B):
+            raise ValueError('expected rows of shape %s, got %s' % (('Tc', self._F) if self.batch is None else (self._B, 'Tc', self._F),
+                                                                    tuple(t.shape)))
+        A = None
+        if magnitudes is not None:
+            A = _dev_tensor(magnitudes, torch.float32, self.device)
+            if A.shape != t.shape:
+                raise ValueError('magnitudes of shape %s for rows of shape %s' % (tuple(A.shape), tuple(t.shape)))
+        Tc = t.shape[-2]
+        out = torch.empty((self._B, Tc, self._F), dtype=torch.complex64, device=t.device)
+        sig = torch.empty((self._B, Tc * self.fshift), dtype=torch.float32, device=t.device) if self.return_signal else None
+        nf, ns = 0, 0
+        if Tc > 0:
+            nf, ns = _capi.rtisi_stream_push(self._h, t.data_ptr(), None if A is None else A.data_ptr(), Tc, out.data_ptr(),
+                                             None if sig is None else sig.data_ptr(),
+                                             stream=torch.cuda.current_stream(t.device).cuda_stream)
+        return self._returns(out, sig, nf, ns)
+
+    def finish(self):
+        import torch
+        if self._h is None or self.finished:
+            raise ValueError('finish on a stream that has finished or been closed')
+        dev = torch.device("cuda", self.device)
+        out = torch.empty((self._B, self.look_ahead, self._F), dtype=torch.complex64, device=dev)
+        sig = None
+        if self.return_signal:
+            sig = torch.empty((self._B, self.fsize + self.look_ahead * self.fshift), dtype=torch.float32, device=dev)
+        nf, ns = _capi.rtisi_stream_finish(self._h, out.data_ptr() if out.numel() else None, None if sig is None else sig.data_ptr(),
+                                           stream=torch.cuda.current_stream(dev).cuda_stream)
+        self.finished = True
+        return self._returns(out, sig, nf, ns)
+
+    def close(self):
+        h, self._h = self._h, None
+        if h is not None:
+            _capi.rtisi_stream_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown
+            pass
 
 
 def rtisi_la_dev(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=None, perfectrec=False, return_signal=False,
@@ -977,17 +1066,22 @@ class lws(object):
         return misi_dev(S, mixture, self.fsize, self.fshift, self.awin, self.swin, iterations, magnitudes=magnitudes,
                         perfectrec=self.perfectrec, return_trace=return_trace, return_signals=return_signals, device=self.device)
 
-    def rtisi_la(self, S, iterations, look_ahead=None, magnitudes=None, return_signal=False):
+    def rtisi_la(self, S, iterations, look_ahead=None, magnitudes=None, return_signal=False, open_end=False):
         """Host fp64 form with this object's windows, perfectrec and (look_ahead=None) look-ahead: see the module's rtisi_la."""
         return rtisi_la(S, self.fsize, self.fshift, self.awin, self.swin, iterations,
                         look_ahead=self.look_ahead if look_ahead is None else look_ahead, magnitudes=magnitudes,
-                        perfectrec=self.perfectrec, return_signal=return_signal)
+                        perfectrec=self.perfectrec, return_signal=return_signal, open_end=open_end)
 
     def rtisi_la_dev(self, S, iterations, look_ahead=None, magnitudes=None, return_signal=False):
         """Device form: a new complex64 torch tensor, see the module's rtisi_la_dev."""
         return rtisi_la_dev(S, self.fsize, self.fshift, self.awin, self.swin, iterations,
                             look_ahead=self.look_ahead if look_ahead is None else look_ahead, magnitudes=magnitudes,
                             perfectrec=self.perfectrec, return_signal=return_signal, device=self.device)
+
+    def rtisi_la_stream(self, iterations, look_ahead=None, batch=None, return_signal=False):
+        """A RtisiLaStream with the windows, look-ahead and device of this object: push() rows as they arrive, then finish()."""
+        return RtisiLaStream(self.fsize, self.fshift, self.awin, self.swin, iterations,
+                             look_ahead=self.look_ahead if look_ahead is None else look_ahead, perfectrec=self.perfectrec, batch=batch, return_signal=return_signal, device=self.device)
 
     def misi_la(self, S, mixture, iterations, look_ahead=None, magnitudes=None, return_signals=False):
         """Host fp64 form with this object's windows, perfectrec and (look_ahead=None) look-ahead: see the module's misi_la."""
