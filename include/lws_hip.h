@@ -291,6 +291,13 @@ void lws_rtisi_stream_destroy(lws_rtisi_stream *h);
 int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, float *x_dev, int B, int K, int M, int N,
                     int fshift, const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream);
 
+/* Where the look-ahead kernels keep their state, and with how many threads they run: what lws_rtisi_la_dev and a stream (K == 0) or
+ * lws_misi_la_dev (K >= 1 sources) decide for frames of N samples at hop fshift under a look-ahead of look_ahead frames (the clamped
+ * one: min(look_ahead, M - 1) of a call).  *in_lds: 1 if ring and frame buffers sit in LDS behind the transform buffers, 0 if in
+ * device scratch; *threads: the workgroup; *lds_bytes: the dynamic LDS the launch asks for.  Any of the three may be NULL.  Host
+ * only: no device call, no check of N against the device transform.  N < 1, fshift < 1, look_ahead < 0 or K < 0: LWS_ERR_INVALID. */
+int lws_rtisi_la_placement(int N, int fshift, int look_ahead, int K, int *in_lds, int *threads, size_t *lds_bytes);
+
 /* ---- host-side construction of windows, weights and schedules (lws.pyx:10-40,160-206), fp64, no device work: what a
  *      caller without numpy needs to build a plan.  Complex outputs are interleaved (re, im) doubles. ---- */
 

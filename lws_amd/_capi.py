@@ -31,7 +31,7 @@ EXPORTS = (
     "lws_nofuture_lws_dev", "lws_online_lws_dev", "lws_residual_dev", "lws_last_kernel_time",
     "lws_last_kernel_name", "lws_generic_stage", "lws_stft_frames", "lws_istft_length", "lws_stft_dev", "lws_istft_dev", "lws_stft_zp_dev",
     "lws_consistency_dev", "lws_griffin_lim_dev", "lws_misi_dev", "lws_rtisi_la_dev", "lws_misi_la_dev",
-    "lws_rtisi_stream_create", "lws_rtisi_stream_push", "lws_rtisi_stream_finish", "lws_rtisi_stream_destroy", "lws_hann", "lws_synthwin", "lws_weights_shape", "lws_create_weights",
+    "lws_rtisi_stream_create", "lws_rtisi_stream_push", "lws_rtisi_stream_finish", "lws_rtisi_stream_destroy", "lws_rtisi_la_placement", "lws_hann", "lws_synthwin", "lws_weights_shape", "lws_create_weights",
     "lws_build_asymmetric_windows", "lws_get_thresholds", "lws_plan_create_from_windows", "lws_stream_copy",
     "lws_run_lws_dev", "lws_plan_reserve", "lws_residual", "lws_residual_allreduce_dev", "lws_weights_structure", "lws_multi_plan_create", "lws_multi_plan_destroy",
     "lws_multi_plan_shards", "lws_multi_batch_lws", "lws_multi_run_lws", "lws_multi_residual",
@@ -112,6 +112,7 @@ def load():
     lib.lws_rtisi_stream_finish.argtypes = [vp, vp, vp, C.POINTER(ip), C.POINTER(ip), vp]
     lib.lws_rtisi_stream_destroy.argtypes = [vp]
     lib.lws_rtisi_stream_destroy.restype = None
+    lib.lws_rtisi_la_placement.argtypes = [ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(C.c_size_t)]
     lib.lws_hann.argtypes = [ip, ip, ip, vp]
     lib.lws_synthwin.argtypes = [vp, ip, ip, vp, vp]
     lib.lws_weights_shape.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
@@ -550,3 +551,11 @@ def rtisi_stream_finish(h, C_out_ptr, x_out_ptr, stream=None):
 
 def rtisi_stream_destroy(h):
     load().lws_rtisi_stream_destroy(h)
+
+
+def rtisi_la_placement(fsize, fshift, look_ahead, K=0):
+    """(in_lds, threads, lds_bytes) of the launch lws_rtisi_la_dev and a stream (K = 0) or lws_misi_la_dev (K sources) make for this
+    frame size, hop and (clamped) look-ahead: whether the state sits in LDS, the workgroup, the dynamic LDS asked for.  Host only."""
+    lds, th, nb = C.c_int(-1), C.c_int(-1), C.c_size_t(0)
+    check(load().lws_rtisi_la_placement(int(fsize), int(fshift), int(look_ahead), int(K), C.byref(lds), C.byref(th), C.byref(nb)))
+    return bool(lds.value), th.value, nb.value

@@ -340,6 +340,11 @@ def lws_rtisi_stream_destroy(h):
         c.lws_rtisi_stream_destroy(<c.lws_rtisi_stream *>p)
 
 
+def lws_rtisi_la_placement(int N, int fshift, int look_ahead, int K, in_lds_ref, threads_ref, lds_bytes_ref):
+    cdef uintptr_t i = _addr(in_lds_ref), t = _addr(threads_ref), b = _addr(lds_bytes_ref)
+    return c.lws_rtisi_la_placement(N, fshift, look_ahead, K, <int *>i, <int *>t, <size_t *>b)
+
+
 def lws_hann(int n, int symmetric, int use_offset, out):
     cdef uintptr_t o = _addr(out)
     return c.lws_hann(n, symmetric, use_offset, <double *>o)

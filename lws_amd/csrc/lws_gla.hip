@@ -972,6 +972,25 @@ MisiLaPlan misi_la_plan(int N, int hop, int LA, int K) {
 
 }  // namespace
 
+extern "C" int lws_rtisi_la_placement(int N, int fshift, int look_ahead, int K, int *in_lds, int *threads, size_t *lds_bytes) {
+    if (N < 1 || fshift < 1 || look_ahead < 0 || K < 0)
+        return lws::set_error(LWS_ERR_INVALID, "placement of N = %d, hop %d, look-ahead %d, %d sources", N, fshift, look_ahead, K);
+    bool lds;
+    int th;
+    size_t bytes;
+    if (K == 0) {
+        const RtisiPlan p = rtisi_plan(N, fshift, look_ahead);
+        lds = p.in_lds; th = p.threads; bytes = p.lds_bytes;
+    } else {
+        const MisiLaPlan p = misi_la_plan(N, fshift, look_ahead, K);
+        lds = p.in_lds; th = p.threads; bytes = p.lds_bytes;
+    }
+    if (in_lds) *in_lds = lds ? 1 : 0;
+    if (threads) *threads = th;
+    if (lds_bytes) *lds_bytes = bytes;
+    return LWS_OK;
+}
+
 extern "C" int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, float *x_dev, int B, int K, int M, int N,
                                int fshift, const double *awin, const double *swin, int perfectrec, int iters, int look_ahead,
                                void *stream) {

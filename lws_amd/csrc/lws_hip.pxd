@@ -68,6 +68,7 @@ cdef extern from "lws_hip.h" nogil:
     int lws_rtisi_stream_finish(lws_rtisi_stream *h, void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out,
                                 void *stream)
     void lws_rtisi_stream_destroy(lws_rtisi_stream *h)
+    int lws_rtisi_la_placement(int N, int fshift, int look_ahead, int K, int *in_lds, int *threads, size_t *lds_bytes)
     int lws_hann(int n, int symmetric, int use_offset, double *out)
     int lws_synthwin(const double *awin, int fsize, int fshift, const double *swin, double *out)
     int lws_weights_shape(int fsize, int fshift, int use_summarized_weights, int *Qprime, int *Q)

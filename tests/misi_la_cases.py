@@ -28,6 +28,19 @@ SHAPES = {
     (128, 32, True): (20, 3),                  # the rings wrap many times, perfectrec
     (4096, 1024, False): (6, 2),               # the state does not fit in LDS: device scratch
 }
+# Placements, workgroups and overlaps SHAPES never reaches, with their own steps.  (fsize, fshift, perfectrec, T, K): (threads,
+# [(look_ahead, iterations, state in LDS)]); the GPU test asserts placement and workgroup through lws_rtisi_la_placement.  hop = N is
+# not here: with K = 2 the error model itself moves 0.5 % of the bins (tests/test_misi_la_host.py allows it 0.02 %).
+EDGE_SHAPES = {
+    (64, 40, False, 8, 2): (256, [(3, 3, True)]),                    # hop > N / 2
+    (64, 32, True, 8, 3): (256, [(3, 3, True)]),                     # Q = N / hop = 2
+    (64, 8, True, 20, 2): (256, [(3, 3, True), (9, 2, True)]),       # Q = 8; more active frames than overlap (LA + 1 > Q)
+    (600, 150, True, 7, 2): (768, [(2, 3, True)]),                   # a workgroup of 768 threads
+    (2048, 512, False, 6, 1): (1024, [(3, 2, True), (4, 2, True)]),  # N > workgroup; at LA = 4 the launch asks for 163 840 bytes: the cap
+    (1024, 256, False, 6, 2): (1024, [(3, 2, True)]),                # K = 2 in LDS ...
+    (1024, 256, False, 6, 3): (1024, [(3, 3, False)]),               # ... K = 3 in scratch (at n = 2 the model moves 0.03 % of the bins)
+    (512, 128, False, 8, 4): (512, [(5, 2, True), (6, 2, False)]),   # LA = 5 in LDS (147 968 bytes), LA = 6 in scratch
+}
 
 
 def keys():

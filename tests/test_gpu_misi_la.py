@@ -18,7 +18,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from test_gpu_misi import mixture_bound  # noqa: E402
-from test_gpu_rtisi import STEPS  # noqa: E402
+from test_gpu_rtisi import STEPS, assert_placement  # noqa: E402
 
 # per (fsize, fshift, perfectrec): [cases, max rel-L2, max rel-L2 / bar, max far fraction, max magnitude error, max |sum s - y| / bound,
 # max signal error / bar]
@@ -70,6 +70,14 @@ def test_matches_host(key):
         check_against_host(key, LA, n)
 
 
+@pytest.mark.parametrize("key", sorted(mc.EDGE_SHAPES), ids=mc.key_id)
+def test_edge_shapes_match_host(key):
+    threads, steps = mc.EDGE_SHAPES[key]
+    for LA, n, in_lds in steps:
+        assert_placement(key, LA, in_lds, threads, K=key[4])
+        check_against_host(key, LA, n)
+
+
 @pytest.mark.parametrize("key,LA,n", [((4096, 1024, False, 6, 1), 0, 3),      # N = 4096 with its state in LDS
                                       ((64, 16, True, 12, 4), 3, 3),          # four sources
                                       ((1024, 256, False, 6, 4), 3, 2)],      # four sources whose state goes to scratch
@@ -118,6 +126,29 @@ def test_stack_equals_members_and_repeats_bit_for_bit(key):
         one, one_s = p.misi_la_dev(t[b], ty[b], 3, return_signals=True)
         assert tuple(one.shape) == c0.shape[1:] and tuple(one_s.shape) == tuple(s.shape[1:])
         assert torch.equal(one, out[b]) and torch.equal(one_s, s[b])
+
+
+def test_concurrent_streams_do_not_share_windows_or_scratch():
+    """Calls with different windows and shapes -- two whose state is in the context's scratch, which each of them grows and reuses (as
+    rtisi_la_dev does: tests/test_gpu_rtisi.py), and one whose state is in LDS -- enqueued on two streams with no host synchronisation
+    in between give what they give one at a time."""
+    keys = [((4096, 1024, False, 6, 2), 3, False), ((1024, 256, False, 6, 4), 3, False), ((64, 16, True, 12, 3), 3, True)]
+    calls = []
+    for key, LA, in_lds in keys:
+        assert_placement(key, LA, in_lds, 1024 if key[0] >= 1024 else 256, K=key[4])
+        p, A, c0, y = mc.case(*key)
+        calls.append((p, torch.from_numpy(c0).cuda(), torch.from_numpy(y).cuda(), LA))
+    refs = [p.misi_la_dev(t, ty, 2, look_ahead=LA, return_signals=True) for p, t, ty, LA in calls]
+    torch.cuda.synchronize()
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    outs = []
+    for rep in range(6):
+        for i, (p, t, ty, LA) in enumerate(calls):
+            with torch.cuda.stream(streams[(rep + i) % 2]):
+                outs.append((i, p.misi_la_dev(t, ty, 2, look_ahead=LA, return_signals=True)))
+    torch.cuda.synchronize()
+    for i, (out, s) in outs:
+        assert torch.equal(out, refs[i][0]) and torch.equal(s, refs[i][1]), i
 
 
 def test_zero_iterations_and_unmodified_input():
@@ -225,9 +256,9 @@ def test_unsupported_and_invalid_arguments_raise():
 
 def test_zz_margins_actually_achieved():
     """What the cases above reached, per shape (written to $LWS_MARGINS_DIR/misi_la_margins.json when that variable names a
-    directory; profiles/misi_la_margins.json is a copy).  On an MI355X, 591 rows: rel-L2 at most 8.6e-6 and at most 7.8 % of its bar, no
-    bin beyond 1e-3 max A, magnitudes within 2.7e-7 max A, the signal sum within 6.0 % of its bound and each signal within 7.1 % of its
-    bar; the whole file in 4.7 s."""
+    directory; profiles/misi_la_margins.json is a copy).  On an MI355X, 669 rows, 78 of them at the rows of mc.EDGE_SHAPES: rel-L2 at most
+    8.6e-6 and at most 7.8 % of its bar, no bin beyond 1e-3 max A, magnitudes within 2.7e-7 max A, the signal sum within 7.1 % of its bound
+    (at lws(2048,512), K = 1) and each signal within 7.1 % of its bar; the whole file in 4.9 s."""
     if not MARGINS:
         check_against_host((64, 16, True, 12, 3), 3, 3)
     report = {"%d,%d,%s" % k: {"cases": v[0], "max_rel_l2": v[1], "max_rel_l2_over_bar": v[2], "max_far_fraction": v[3],

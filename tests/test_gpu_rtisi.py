@@ -30,6 +30,22 @@ SHAPES = {
     (4096, 1024, False): 12, (4096, 1024, True): 4,    # the state does not fit in LDS: device scratch
     (512, 128, False): 40, (128, 32, True): 33,        # the rings wrap many times
 }
+# Placements, workgroups and overlaps SHAPES never reaches.  (fsize, fshift, perfectrec, T): (threads, [(look_ahead, iterations, state
+# in LDS)]); every case asserts its placement and workgroup through lws_rtisi_la_placement before it runs.
+EDGE_SHAPES = {
+    (320, 80, True, 9): (512, [(2, 2, True), (3, 3, True)]),         # 512 threads over 320 samples, odd factor 5
+    (600, 150, False, 7): (768, [(3, 3, True), (0, 2, True)]),       # a workgroup of 768 threads, odd factor 75
+    (768, 192, True, 8): (768, [(3, 2, True)]),                      # 768 threads = N, odd factor 3
+    (1536, 384, True, 8): (1024, [(3, 3, True), (1, 2, True)]),      # N > workgroup, the state in LDS behind three transform buffers
+    (2048, 512, False, 8): (1024, [(3, 3, True), (5, 2, True), (6, 2, False)]),   # N = 2 workgroups; LA 5 in LDS, LA 6 in scratch
+    (2048, 1228, False, 8): (1024, [(5, 2, True)]),                  # 163 824 bytes of dynamic LDS: 16 under the cap
+    (2048, 1229, False, 8): (1024, [(5, 2, False)]),                 # ... and 4 over it: scratch
+    (64, 64, False, 6): (256, [(3, 3, True), (0, 2, True)]),         # hop = N: every sample final after one frame
+    (64, 40, False, 8): (256, [(3, 3, True)]),                       # hop > N / 2
+    (64, 32, True, 8): (256, [(3, 3, True), (1, 2, True)]),          # Q = N / hop = 2
+    (64, 8, True, 20): (256, [(3, 3, True), (9, 2, True)]),          # Q = 8; more active frames than overlap (LA + 1 > Q)
+    (64, 4, False, 24): (256, [(3, 2, True), (17, 2, True)]),        # Q = 16; 18 active frames
+}
 MARGINS = {}    # (fsize, fshift, perfectrec) -> [cases, max rel-L2, max rel-L2 / bar, max far fraction, max magnitude error, max signal error]
 
 
@@ -119,13 +135,28 @@ def test_matches_host(fsize, fshift, perfectrec):
         check_against_host(key, LA, n)
 
 
+def assert_placement(key, LA, in_lds, threads, K=0):
+    """The launch of this case (look-ahead clamped to its frames, as the entry points clamp it) is the one its comment claims."""
+    got = lws_amd._capi.rtisi_la_placement(key[0], key[1], min(LA, key[3] - 1), K)
+    print("placement %s LA=%d K=%d: state in %s, %d threads, %d bytes of dynamic LDS" % (key[:4], LA, K, "LDS" if got[0] else "scratch", got[1], got[2]))
+    assert got[:2] == (in_lds, threads), (key, LA, K, got)
+
+
+@pytest.mark.parametrize("key", sorted(EDGE_SHAPES))
+def test_edge_shapes_match_host(key):
+    threads, steps = EDGE_SHAPES[key]
+    for LA, n, in_lds in steps:
+        assert_placement(key, LA, in_lds, threads)
+        check_against_host(key, LA, n)
+
+
 @pytest.mark.parametrize("key", [(64, 16, True, 12), (256, 96, False, 2)])
 def test_explicit_magnitudes(key):
     check_against_host(key, 3, 3, explicit=True)
     check_against_host(key, 1, 4, explicit=True)
 
 
-@pytest.mark.parametrize("key", [(64, 16, True, 12), (512, 128, False, 40)])
+@pytest.mark.parametrize("key", [(64, 16, True, 12), (512, 128, False, 40), (64, 8, True, 20)])
 def test_causality_bit_for_bit(key):
     """Output frame m depends on no input frame later than m + LA: with explicit magnitudes, LA = 3 and n = 3, other phases in the
     input frames >= 6 leave the output frames 0..2 as they are, and change frame 3."""
@@ -140,7 +171,7 @@ def test_causality_bit_for_bit(key):
         assert not np.array_equal(a[s, 3], b[s, 3])
 
 
-@pytest.mark.parametrize("key", [(64, 16, False, 9), (1000, 250, True, 5), (4096, 1024, True, 4)])
+@pytest.mark.parametrize("key", [(64, 16, False, 9), (1000, 250, True, 5), (4096, 1024, True, 4), (2048, 512, False, 8)])
 def test_stack_equals_members_and_repeats_bit_for_bit(key):
     p, A, c0 = case(*key)
     t = torch.from_numpy(c0).cuda()
@@ -211,6 +242,28 @@ def test_method_uses_the_plans_look_ahead():
     assert torch.equal(p.rtisi_la_dev(t, 2, look_ahead=11), p.rtisi_la_dev(t, 2, look_ahead=40))   # all 12 frames active either way
 
 
+def test_concurrent_streams_do_not_share_windows_or_scratch():
+    """Calls with different windows and shapes -- two whose state is in the context's scratch, which each of them grows and reuses, and
+    one whose state is in LDS -- enqueued on two streams with no host synchronisation in between give what they give one at a time."""
+    keys = [((4096, 1024, False, 12), 3, False), ((2048, 512, False, 8), 6, False), ((64, 16, True, 12), 3, True)]
+    calls = []
+    for key, LA, in_lds in keys:
+        assert_placement(key, LA, in_lds, 1024 if key[0] >= 1024 else 256)
+        p, A, c0 = case(*key)
+        calls.append((p, torch.from_numpy(c0).cuda(), LA))
+    refs = [p.rtisi_la_dev(t, 2, look_ahead=LA, return_signal=True) for p, t, LA in calls]
+    torch.cuda.synchronize()
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    outs = []
+    for rep in range(6):
+        for i, (p, t, LA) in enumerate(calls):
+            with torch.cuda.stream(streams[(rep + i) % 2]):
+                outs.append((i, p.rtisi_la_dev(t, 2, look_ahead=LA, return_signal=True)))
+    torch.cuda.synchronize()
+    for i, (out, sig) in outs:
+        assert torch.equal(out, refs[i][0]) and torch.equal(sig, refs[i][1]), i
+
+
 def test_unsupported_and_invalid_arguments_raise():
     p = lws_amd.lws(8192, 2048)                  # beyond the LDS-resident transform (even sizes up to 4096)
     with pytest.raises(lws_amd.LwsHipError):
@@ -235,8 +288,9 @@ def test_unsupported_and_invalid_arguments_raise():
 
 def test_zz_margins_actually_achieved():
     """What the cases above reached, per shape (written to $LWS_MARGINS_DIR/rtisi_margins.json when that variable names a directory;
-    profiles/rtisi_margins.json is a copy).  On an MI355X, 309 rows: rel-L2 at most 7.5e-6 and at most 9.2 % of its bar, no bin beyond
-    1e-3 max A, magnitudes within 2.2e-7 max A, signals within 3.6e-7 max|x|; the whole file in 3.5 s."""
+    profiles/rtisi_margins.json is a copy).  On an MI355X, 372 rows, 63 of them at the 12 shapes of EDGE_SHAPES: rel-L2 at most 7.5e-6 and
+    at most 9.2 % of its bar (5.0 % at the edge shapes), no bin beyond 1e-3 max A, magnitudes within 2.2e-7 max A, signals within 3.6e-7
+    max|x|; the whole file in 4.5 s."""
     if not MARGINS:
         check_against_host((64, 16, True, 12), 3, 3)
     report = {"%d,%d,%s" % k: {"cases": v[0], "max_rel_l2": v[1], "max_rel_l2_over_bar": v[2], "max_far_fraction": v[3],

@@ -19,7 +19,7 @@ from lws_amd.lws import _perfectrec_prepad
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-from test_gpu_rtisi import case, magnitudes_of, perturbation, rel   # noqa: E402
+from test_gpu_rtisi import EDGE_SHAPES, assert_placement, case, magnitudes_of, perturbation, rel   # noqa: E402
 
 KEYS = [
     (64, 16, True, 12),        # power of two
@@ -29,7 +29,20 @@ KEYS = [
     (4096, 1024, False, 6),    # the state does not fit in LDS: scratch placement
 ]
 STEPS = [(0, 2), (1, 3), (3, 3), (5, 2)]   # (look_ahead, iterations)
+# rows of EDGE_SHAPES of tests/test_gpu_rtisi.py with their steps there: N = 2 workgroups on both sides of the LDS boundary, 16 bytes
+# under the cap, more active frames than overlap, no overlap.  (threads, [(look_ahead, iterations, state in LDS)])
+EDGE_KEYS = {k: EDGE_SHAPES[k] for k in [(2048, 512, False, 8), (2048, 1228, False, 8), (64, 8, True, 20), (64, 64, False, 6)]}
 MARGINS = {}   # "fsize,fshift,perfectrec" -> figures against the host; ["vs_rtisi_la_dev"]: against the one-shot kernel
+
+
+def steps_of(key):
+    """(look_ahead, iterations) of a key; an edge key first asserts the placement and workgroup of a stream created for each."""
+    if key not in EDGE_KEYS:
+        return STEPS
+    threads, steps = EDGE_KEYS[key]
+    for LA, n, in_lds in steps:
+        assert_placement(key, LA, in_lds, threads)
+    return [(LA, n) for LA, n, in_lds in steps]
 
 
 def chunkings(T):
@@ -121,12 +134,12 @@ def check_against_host(key, LA, n, chunks, explicit=False, rows=None):
         assert serr <= 3e-6, (b, serr)
 
 
-@pytest.mark.parametrize("key", KEYS)
+@pytest.mark.parametrize("key", KEYS + sorted(EDGE_KEYS))
 def test_chunking_changes_no_bit(key):
     """Pushed whole, a row at a time, and with a chunk shorter than LA + 1 and an empty one: the same frames, signals and counts."""
     p, A, c0 = case(*key)
     T = c0.shape[1]
-    for LA, n in STEPS:
+    for LA, n in steps_of(key):
         whole, whole_x = streamed(key, LA, n)
         assert tuple(whole.shape) == c0.shape
         for chunks in chunkings(T)[1:]:
@@ -134,9 +147,9 @@ def test_chunking_changes_no_bit(key):
             assert torch.equal(out, whole) and torch.equal(x, whole_x), (LA, n, chunks)
 
 
-@pytest.mark.parametrize("key", KEYS)
+@pytest.mark.parametrize("key", KEYS + sorted(EDGE_KEYS))
 def test_matches_host_open_end(key):
-    for LA, n in STEPS:
+    for LA, n in steps_of(key):
         check_against_host(key, LA, n, [case(*key)[2].shape[1]])
 
 
@@ -230,6 +243,18 @@ def test_fewer_frames_than_the_look_ahead(key, LA, T):
     assert tuple(s.finish().shape) == (3, T, c0.shape[2])
 
 
+@pytest.mark.parametrize("key,LA,n,T", [((4096, 1024, False, 6), 3, 3, 1), ((2048, 512, False, 8), 6, 2, 2)])
+def test_end_before_the_first_commit_changes_the_placement(key, LA, n, T):
+    """A stream created with its state in scratch that ends after T <= LA frames closes with a look-ahead of T - 1, for which the
+    state fits in LDS: the closing launch is the LDS kernel, on a state buffer sized and strided for the scratch one."""
+    assert_placement(key, LA, False, 1024)                               # as created
+    assert_placement(key[:3] + (T,), LA, True, 1024)                     # as closed: look-ahead T - 1
+    check_against_host(key, LA, n, [1] * T, rows=T)
+    p, A, c0 = case(*key)
+    a, b = run_stream(p, c0[:, :T], LA, n, [1] * T), run_stream(p, c0[:, :T], LA, n, [T])
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+
+
 def test_edges():
     p, A, c0 = case(64, 16, True, 12)
     F = c0.shape[2]
@@ -299,9 +324,10 @@ def test_c_abi_misuse_returns_invalid_and_leaves_the_library_usable():
 
 def test_zz_margins_actually_achieved():
     """What the cases above reached, per shape (written to $LWS_MARGINS_DIR/rtisi_stream_margins.json when that variable names a
-    directory; profiles/rtisi_stream_margins.json is a copy).  On an MI355X, 78 rows: rel-L2 at most 4.0e-6 and at most 4.9 % of its bar,
-    no bin beyond 1e-3 max A, magnitudes within 2.0e-7 max A, signals within 1.8e-7 max|x|; where rtisi_la_dev computes the same thing the
-    stream had its bits at every shape and step; the whole file in 3.4 s."""
+    directory; profiles/rtisi_stream_margins.json is a copy).  On an MI355X, 108 rows, 30 of them at EDGE_KEYS and at the streams that end
+    before their first commit: rel-L2 at most 4.0e-6 and at most 5.0 % of its bar, no bin beyond 1e-3 max A, magnitudes within 2.0e-7 max A,
+    signals within 1.8e-7 max|x|; where rtisi_la_dev computes the same thing the stream had its bits at every shape and step of KEYS; the
+    whole file in 3.1 s."""
     if not MARGINS:
         check_against_host((64, 16, True, 12), 3, 3, [12])
     out = os.environ.get("LWS_MARGINS_DIR", "")

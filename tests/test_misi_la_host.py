@@ -271,6 +271,20 @@ def test_error_model_moves_almost_no_bin_far(key):
     assert worst <= 2e-4
 
 
+@pytest.mark.parametrize("key", sorted(mc.EDGE_SHAPES), ids=mc.key_id)
+def test_error_model_moves_almost_no_bin_far_at_the_edge_shapes(key):
+    """The same condition on every row and step of the second table of the GPU test."""
+    p, A, c0, y = mc.case(*key)
+    worst = 0.0
+    for LA, n, _ in mc.EDGE_SHAPES[key][1]:
+        (ref, _), (per, _) = mc.host(key, LA, n)
+        assert np.isfinite(ref.view(np.float64)).all()
+        far = np.mean(np.abs(per - ref) > 1e-3 * A.max(axis=(2, 3), keepdims=True), axis=(2, 3))
+        worst = max(worst, far.max())
+        print("misi_la model %s LA=%d n=%d: far bins at most %.4f%%" % (mc.key_id(key), LA, n, 100 * far.max()))
+    assert worst <= 2e-4
+
+
 def test_entry_point_checks_its_arguments_before_any_device_call():
     lib = _capi.load()
     w = np.ones(64)
