@@ -291,8 +291,47 @@ void lws_rtisi_stream_destroy(lws_rtisi_stream *h);
 int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, float *x_dev, int B, int K, int M, int N,
                     int fshift, const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream);
 
-/* Where the look-ahead kernels keep their state, and with how many threads they run: what lws_rtisi_la_dev and a stream (K == 0) or
- * lws_misi_la_dev (K >= 1 sources) decide for frames of N samples at hop fshift under a look-ahead of look_ahead frames (the clamped
+/* Streaming online MISI (lws_gla.hip): lws_misi_la_dev for frames and mixture that arrive over time, B mixtures of K sources side by
+ * side, the state of the iteration (per source the overlap-add ring, the windowed inverse frames and the magnitudes of the look_ahead
+ * frames still active; per mixture the samples under those frames) in device memory owned by the handle.  The rows all calls return,
+ * one after another, are what one call with everything pushed would return under an open end -- lws_amd.misi_la(..., open_end=True)
+ * is the fp64 definition: as lws_misi_la_dev, except that with perfectrec the samples behind fshift M read as zero only in the
+ * returned signals, not inside the iteration, and that in the steps push runs the denominator of g sums w over every frame j >= 0
+ * that would cover a sample, as if the stream never ended (finish, which knows M, sums over 0 .. M-1: g = 1 there).  A stream has no
+ * length limit.
+ *   count  : after M frames the stream holds need(M) = fshift (M - 1) + N - lo mixture samples (need(0) = 0), every sample under
+ *            those frames; lo is the lead-in perfectrec cuts (N - fshift, or N - N % fshift if that is not 0), else 0.  A push of
+ *            `frames` rows must bring exactly samples = need(M + frames) - need(M): the first N - fshift more than frames fshift, and
+ *            with perfectrec the stream ends N - fshift samples behind what istft returns -- the zeros stft pads with, or the real
+ *            continuation.  Any other count: LWS_ERR_INVALID, the handle left as it was.
+ *   create : windows as lws_misi_la_dev takes them (the handle keeps its own device copy); synchronises once.
+ *   push   : S_dev[B][K][frames][N/2+1] (complex64) the next rows of every source, A_dev (float32, same layout) their target
+ *            magnitudes or NULL (|S|), y_dev[B][samples] (float32) the next mixture samples.  Commits every frame m with
+ *            m + look_ahead pushed: *frames_out = max(0, pushed - look_ahead) - committed rows of every source, written to
+ *            C_out_dev[B][K][frames][N/2+1] -- the row stride is the chunk's `frames`, the first *frames_out rows of each source are
+ *            valid, the rest left alone -- and, x_out_dev not NULL, the fshift samples each commit finalises, less what perfectrec
+ *            cuts at the start, s_k = done_k + (y - sum_j done_j) / K, to x_out_dev[B][K][frames fshift], *samples_out of each
+ *            source.  Both counts come from the host's counters; the call only enqueues work on `stream` and keeps no reference to
+ *            the caller's buffers.  frames == 0 (with samples == 0) does nothing.  At most (2^31 - N) / fshift - look_ahead - 2
+ *            frames per push (LWS_ERR_UNSUPPORTED beyond).
+ *   finish : commits the rest with last = min(m + look_ahead, M - 1), C_out_dev[B][K][look_ahead][N/2+1] and
+ *            x_out_dev[B][K][N + look_ahead fshift]; with fewer than look_ahead + 1 rows pushed, with look_ahead clamped to M - 1 as
+ *            one call on them would; with none, 0 and 0.  The stream takes no rows after it.
+ * Placement and workgroup are what lws_rtisi_la_placement(N, fshift, look_ahead, K >= 1, ...) says, for the stream's look_ahead.
+ * Calls on one handle are ordered by `stream`, or by an event of the handle's if `stream` changes between calls.  A null handle,
+ * frames < 0, a null S_dev / y_dev with frames > 0, a null C_out_dev with rows to return, a push or finish after finish:
+ * LWS_ERR_INVALID, nothing enqueued.  create: B < 1, K < 1, iters < 0, look_ahead < 0, null window: LWS_ERR_INVALID; frame sizes: as
+ * lws_griffin_lim_dev. */
+typedef struct lws_misi_stream lws_misi_stream;
+int lws_misi_stream_create(int device, int B, int K, int N, int fshift, const double *awin, const double *swin, int perfectrec,
+                           int iters, int look_ahead, lws_misi_stream **out);
+int lws_misi_stream_push(lws_misi_stream *h, const void *S_dev, const float *A_dev, const float *y_dev, int frames, int samples,
+                         void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out, void *stream);
+int lws_misi_stream_finish(lws_misi_stream *h, void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out, void *stream);
+void lws_misi_stream_destroy(lws_misi_stream *h);
+
+/* Where the look-ahead kernels keep their state, and with how many threads they run: what lws_rtisi_la_dev and its stream (K == 0) or
+ * lws_misi_la_dev and its stream (K >= 1 sources) decide for frames of N samples at hop fshift under a look-ahead of look_ahead frames (the clamped
  * one: min(look_ahead, M - 1) of a call).  *in_lds: 1 if ring and frame buffers sit in LDS behind the transform buffers, 0 if in
  * device scratch; *threads: the workgroup; *lds_bytes: the dynamic LDS the launch asks for.  Any of the three may be NULL.  Host
  * only: no device call, no check of N against the device transform.  N < 1, fshift < 1, look_ahead < 0 or K < 0: LWS_ERR_INVALID. */

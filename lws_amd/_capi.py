@@ -31,7 +31,8 @@ EXPORTS = (
     "lws_nofuture_lws_dev", "lws_online_lws_dev", "lws_residual_dev", "lws_last_kernel_time",
     "lws_last_kernel_name", "lws_generic_stage", "lws_stft_frames", "lws_istft_length", "lws_stft_dev", "lws_istft_dev", "lws_stft_zp_dev",
     "lws_consistency_dev", "lws_griffin_lim_dev", "lws_misi_dev", "lws_rtisi_la_dev", "lws_misi_la_dev",
-    "lws_rtisi_stream_create", "lws_rtisi_stream_push", "lws_rtisi_stream_finish", "lws_rtisi_stream_destroy", "lws_rtisi_la_placement", "lws_hann", "lws_synthwin", "lws_weights_shape", "lws_create_weights",
+    "lws_rtisi_stream_create", "lws_rtisi_stream_push", "lws_rtisi_stream_finish", "lws_rtisi_stream_destroy", "lws_rtisi_la_placement",
+    "lws_misi_stream_create", "lws_misi_stream_push", "lws_misi_stream_finish", "lws_misi_stream_destroy", "lws_hann", "lws_synthwin", "lws_weights_shape", "lws_create_weights",
     "lws_build_asymmetric_windows", "lws_get_thresholds", "lws_plan_create_from_windows", "lws_stream_copy",
     "lws_run_lws_dev", "lws_plan_reserve", "lws_residual", "lws_residual_allreduce_dev", "lws_weights_structure", "lws_multi_plan_create", "lws_multi_plan_destroy",
     "lws_multi_plan_shards", "lws_multi_batch_lws", "lws_multi_run_lws", "lws_multi_residual",
@@ -113,6 +114,11 @@ def load():
     lib.lws_rtisi_stream_destroy.argtypes = [vp]
     lib.lws_rtisi_stream_destroy.restype = None
     lib.lws_rtisi_la_placement.argtypes = [ip, ip, ip, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(C.c_size_t)]
+    lib.lws_misi_stream_create.argtypes = [ip, ip, ip, ip, ip, vp, vp, ip, ip, ip, C.POINTER(vp)]
+    lib.lws_misi_stream_push.argtypes = [vp, vp, vp, vp, ip, ip, vp, vp, C.POINTER(ip), C.POINTER(ip), vp]
+    lib.lws_misi_stream_finish.argtypes = [vp, vp, vp, C.POINTER(ip), C.POINTER(ip), vp]
+    lib.lws_misi_stream_destroy.argtypes = [vp]
+    lib.lws_misi_stream_destroy.restype = None
     lib.lws_hann.argtypes = [ip, ip, ip, vp]
     lib.lws_synthwin.argtypes = [vp, ip, ip, vp, vp]
     lib.lws_weights_shape.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
@@ -553,8 +559,41 @@ def rtisi_stream_destroy(h):
     load().lws_rtisi_stream_destroy(h)
 
 
+def misi_stream_create(B, K, fsize, fshift, awin, swin, perfectrec, iterations, look_ahead, device=0):
+    """A handle (c_void_p) for B online-MISI streams of K sources each; free it with misi_stream_destroy."""
+    a, w = _win(awin), _win(swin)
+    if a.shape != (int(fsize),) or w.shape != (int(fsize),):
+        raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
+    h = C.c_void_p()
+    check(load().lws_misi_stream_create(int(device), int(B), int(K), int(fsize), int(fshift), a.ctypes.data, w.ctypes.data,
+                                        int(bool(perfectrec)), int(iterations), int(look_ahead), C.byref(h)))
+    return h
+
+
+def misi_stream_push(h, S_ptr, A_ptr, y_ptr, frames, samples, C_out_ptr, x_out_ptr, stream=None):
+    """The next `frames` rows of every source (device complex64 [B][K][frames][F]; A_ptr: device float32 or None) and the next
+    `samples` mixture samples (device float32 [B][samples]).  Returns (rows, samples) committed per source, written to C_out_ptr
+    [B][K][frames][F] and x_out_ptr [B][K][frames*fshift] (or None).  Only enqueues."""
+    nf, ns = C.c_int(0), C.c_int(0)
+    check(load().lws_misi_stream_push(h, S_ptr, A_ptr, y_ptr, int(frames), int(samples), C_out_ptr, x_out_ptr, C.byref(nf), C.byref(ns),
+                                      stream))
+    return nf.value, ns.value
+
+
+def misi_stream_finish(h, C_out_ptr, x_out_ptr, stream=None):
+    """Commits what is left: C_out_ptr [B][K][look_ahead][F], x_out_ptr [B][K][fsize + look_ahead*fshift] (or None).  Returns (rows,
+    samples)."""
+    nf, ns = C.c_int(0), C.c_int(0)
+    check(load().lws_misi_stream_finish(h, C_out_ptr, x_out_ptr, C.byref(nf), C.byref(ns), stream))
+    return nf.value, ns.value
+
+
+def misi_stream_destroy(h):
+    load().lws_misi_stream_destroy(h)
+
+
 def rtisi_la_placement(fsize, fshift, look_ahead, K=0):
-    """(in_lds, threads, lds_bytes) of the launch lws_rtisi_la_dev and a stream (K = 0) or lws_misi_la_dev (K sources) make for this
+    """(in_lds, threads, lds_bytes) of the launch lws_rtisi_la_dev and a stream (K = 0) or lws_misi_la_dev and a stream (K sources) make for this
     frame size, hop and (clamped) look-ahead: whether the state sits in LDS, the workgroup, the dynamic LDS asked for.  Host only."""
     lds, th, nb = C.c_int(-1), C.c_int(-1), C.c_size_t(0)
     check(load().lws_rtisi_la_placement(int(fsize), int(fshift), int(look_ahead), int(K), C.byref(lds), C.byref(th), C.byref(nb)))

@@ -340,6 +340,41 @@ def lws_rtisi_stream_destroy(h):
         c.lws_rtisi_stream_destroy(<c.lws_rtisi_stream *>p)
 
 
+def lws_misi_stream_create(int device, int B, int K, int N, int fshift, awin, swin, int perfectrec, int iters, int look_ahead, out_ref):
+    cdef c.lws_misi_stream *h = NULL
+    cdef uintptr_t a = _addr(awin), w = _addr(swin)
+    cdef int rc
+    with nogil:
+        rc = c.lws_misi_stream_create(device, B, K, N, fshift, <const double *>a, <const double *>w, perfectrec, iters, look_ahead, &h)
+    out_ref._obj.value = <uintptr_t>h if h != NULL else None
+    return rc
+
+
+def lws_misi_stream_push(h, S_dev, A_dev, y_dev, int frames, int samples, C_out_dev, x_out_dev, frames_out, samples_out, stream):
+    cdef uintptr_t p = _addr(h), sd = _addr(S_dev), ad = _addr(A_dev), yd = _addr(y_dev), cd = _addr(C_out_dev), xd = _addr(x_out_dev)
+    cdef uintptr_t fo = _addr(frames_out), so = _addr(samples_out), st = _addr(stream)
+    cdef int rc
+    with nogil:
+        rc = c.lws_misi_stream_push(<c.lws_misi_stream *>p, <const void *>sd, <const float *>ad, <const float *>yd, frames, samples,
+                                    <void *>cd, <float *>xd, <int *>fo, <int *>so, <void *>st)
+    return rc
+
+
+def lws_misi_stream_finish(h, C_out_dev, x_out_dev, frames_out, samples_out, stream):
+    cdef uintptr_t p = _addr(h), cd = _addr(C_out_dev), xd = _addr(x_out_dev)
+    cdef uintptr_t fo = _addr(frames_out), so = _addr(samples_out), st = _addr(stream)
+    cdef int rc
+    with nogil:
+        rc = c.lws_misi_stream_finish(<c.lws_misi_stream *>p, <void *>cd, <float *>xd, <int *>fo, <int *>so, <void *>st)
+    return rc
+
+
+def lws_misi_stream_destroy(h):
+    cdef uintptr_t p = _addr(h)
+    with nogil:
+        c.lws_misi_stream_destroy(<c.lws_misi_stream *>p)
+
+
 def lws_rtisi_la_placement(int N, int fshift, int look_ahead, int K, in_lds_ref, threads_ref, lds_bytes_ref):
     cdef uintptr_t i = _addr(in_lds_ref), t = _addr(threads_ref), b = _addr(lds_bytes_ref)
     return c.lws_rtisi_la_placement(N, fshift, look_ahead, K, <int *>i, <int *>t, <size_t *>b)

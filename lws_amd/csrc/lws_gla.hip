@@ -707,6 +707,269 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi_stream(const float2
     }
 }
 
+// ---- Streaming online MISI: the commit steps of k_misi_la, a few per launch, as k_rtisi_stream runs those of k_rtisi.  One workgroup
+// per mixture; everything is counted from the launch's first step (frame 0 is the frame that step commits, sample 0 its first
+// sample).  Rows (S, and A per source) and mixture samples that entered in earlier calls come from the handle's `held` buffers, later
+// ones from the caller's chunk: mixture sample t is held.y[t] for t < ny_held and Y[t - ny_held] behind that, nothing beyond the
+// ny_chunk samples passed.  The denominator of the entered share g sums w over the frames from the stream's first (frame0, relative,
+// <= 0) to every frame that covers the sample while the stream is open, to Mrel - 1 in the closing launch, which knows the end: the
+// one arithmetic difference from k_misi_la; the stream computes misi_la(..., open_end=True).  State per stream in device memory,
+// K x (ring | fcur | (scratch placement only) the other frame buffer); target and xs are temporaries of a step, in LDS or, with the
+// scratch placement, in (K + 1) R floats behind the stream's state that carry nothing from launch to launch.  IN_LDS copies rings and
+// fcur_k in on entry and out on exit.  What the next launch still needs -- the rows of the frames nsteps .. nsteps + LA - 1 and the
+// R - hop mixture samples from hop nsteps on -- the launch copies into the other held buffers (two of each, as in k_rtisi_stream: a
+// launch never writes what it reads), and it does so before its first step: carried over the loops to an epilogue, those pointers and
+// counts cost the lanes that keep the SGPRs parked and 36 bytes of reserved scratch per lane.  Pairing, buffers, arithmetic and
+// barriers are k_misi_la's, step for step; the loops that enclose a barrier run over kernel arguments and counters derived from them
+// alone.  The loops over the sources stay rolled (K is an argument: unrolled on a guess they only add to the SGPRs parked).
+struct MisiStreamHeld {
+    const float2 *S;     // [B][K][rows][F]: as RtisiHeld, per source
+    const float *A;
+    const float *y;      // [B][y_rows]: the mixture samples in front of the chunk's
+    float2 *S_next;
+    float *A_next;
+    float *y_next;       // where the samples still under the active frames after this launch go (null: not kept)
+};
+struct MisiStreamArgs {
+    RtisiStreamArgs r;   // r.state_floats: stride of ONE source in `state`; the rows are [B][K][rows][F], the samples [B][K][samples]
+    int K, frame0;       // sources; the stream's first frame, counted from the first step's (clamped: no earlier frame covers sample 0)
+    int ny_held, ny_chunk, y_rows, y_keep;   // mixture samples held / in the chunk, per-stream stride of held.y, samples to keep
+    size_t stream_floats;                    // stride of a stream in `state`
+};
+
+__device__ __forceinline__ float misi_stream_y(const float *held, const float *chunk, int t, int ny_held, int ny_chunk) {
+    if (t < ny_held) return held[t];
+    const int i = t - ny_held;
+    return i < ny_chunk ? chunk[i] : 0.f;
+}
+
+template <bool IN_LDS>
+__global__ void __launch_bounds__(RTISI_MAX_THREADS) k_misi_la_stream(const float2 *S, const float *A, const float *Y, float2 *Cout,
+                                                                      float *xout, const float *awin, const float *swin, float *state,
+                                                                      MisiStreamHeld h, MisiStreamArgs p) {
+    extern __shared__ float2 lds[];
+    const RtisiStreamArgs q = p.r;
+    const int b = blockIdx.x, K = p.K, N = q.N, F = N / 2 + 1, hop = q.hop, W = q.LA + 1, R = N + q.LA * hop;
+    const RtisiArgs a{q.Mrel, N, q.odd, q.log2e, hop, q.LA, q.iters, q.zero_lo, 0, 0, 0};   // what rtisi_sample reads
+    constexpr int no_end = 0x7fffffff;   // the iteration sees no tail cut
+    float2 *bufA = lds, *bufB = lds + N, *bufC = lds + 2 * N;   // as in k_rtisi
+    float *gs = state + (size_t)b * p.stream_floats;
+    float *ls = IN_LDS ? reinterpret_cast<float *>(lds + (q.odd > 1 ? 3 : 2) * N) : gs;
+    const int sstride = IN_LDS ? R + 2 * W * N : (int)q.state_floats;   // of a source in ls
+    const int target_at = K * sstride, xs_at = target_at + R;   // target and xs within ls: indices, not pointers held across the loops
+    int cur = R, nxt = R + W * N;   // fcur and fnxt within the state of a source; its ring is at 0
+    if (IN_LDS) {
+#pragma nounroll
+        for (int k = 0; k < K; ++k)
+            for (int i = threadIdx.x; i < R + W * N; i += blockDim.x) ls[(size_t)k * sstride + i] = gs[(size_t)k * q.state_floats + i];
+    } else if (q.cur) {
+        cur = nxt;
+        nxt = R;
+    }
+    const size_t hy_at = (size_t)b * p.y_rows, cy_at = (size_t)b * p.ny_chunk;   // where the mixture samples of this stream start
+    // what the next launch still needs goes into the other held buffers, here at the start, so that nothing of it is carried over the
+    // loops: the rows of the frames nsteps .. nsteps + LA - 1, active then ...
+#pragma nounroll
+    for (int k = 0; k < K; ++k) {
+        const size_t held_at = ((size_t)b * K + k) * q.held_rows * F, chunk_at = ((size_t)b * K + k) * q.chunk_rows * F;
+        for (int i = 0; i < q.LA; ++i) {
+            if (h.A_next) {
+                const float *src = rtisi_row(h.A + held_at, A + chunk_at, q.nsteps + i, q.nheld, F);
+                float *to = h.A_next + held_at + (size_t)i * F;
+                for (int j = threadIdx.x; j < F; j += blockDim.x) to[j] = src[j];
+            }
+            if (h.S_next) {
+                const float2 *src = rtisi_row(h.S + held_at, S + chunk_at, q.nsteps + i, q.nheld, F);
+                float2 *to = h.S_next + held_at + (size_t)i * F;
+                for (int j = threadIdx.x; j < F; j += blockDim.x) to[j] = src[j];
+            }
+        }
+    }
+    // ... and the mixture samples under them
+    if (h.y_next) {
+        float *to = h.y_next + (size_t)b * p.y_rows;
+        for (int i = threadIdx.x; i < p.y_keep; i += blockDim.x)
+            to[i] = misi_stream_y(h.y + hy_at, Y + cy_at, hop * q.nsteps + i, p.ny_held, p.ny_chunk);
+    }
+    __syncthreads();
+    int base = q.base, slot_m = q.slot_m;   // slot_m: the slot of frame m
+    for (int m = 0; m < q.nsteps; ++m) {
+        const int last = m + q.LA < q.Mrel - 1 ? m + q.LA : q.Mrel - 1;
+        const bool origin = q.origin && m == 0;   // k_misi_la's m == 0: the LA + 1 first frames enter together
+        for (int d = threadIdx.x; d < R; d += blockDim.x) {
+            const int t = hop * m + d;
+            float v = 0.f;
+            if (t >= q.zero_lo) {
+                int s = p.frame0, n = t - s * hop;            // the first frame of the stream, or the first that covers t
+                if (n > N - 1) {
+                    const int skip = (n - N + hop) / hop;
+                    s += skip;
+                    n -= skip * hop;
+                }
+                int s_hi = t / hop;
+                if (q.closing && s_hi > q.Mrel - 1) s_hi = q.Mrel - 1;
+                float num = 0.f, den = 0.f;
+                for (; s <= s_hi; ++s, n -= hop) {
+                    den += awin[n] * swin[n];
+                    if (s <= last) num = den;
+                }
+                v = (den != 0.f ? num / den : 1.0f) * misi_stream_y(h.y + hy_at, Y + cy_at, t, p.ny_held, p.ny_chunk);
+            }
+            ls[target_at + d] = v;
+        }
+        for (int it = 0; it <= q.iters; ++it) {
+            if (it > 0) {
+                for (int d = threadIdx.x; d < R; d += blockDim.x) {
+                    const int t = hop * m + d;
+                    float acc = 0.f;
+#pragma nounroll
+                    for (int k = 0; k < K; ++k) {
+                        const float *sk = ls + (size_t)k * sstride;
+                        const float y = rtisi_sample(sk, sk + cur, t, m, last, slot_m, base, R, no_end, a);
+                        ls[xs_at + k * R + d] = y;
+                        acc = k ? acc + y : y;
+                    }
+                    const float delta = (ls[target_at + d] - acc) / (float)K;
+#pragma nounroll
+                    for (int k = 0; k < K; ++k) ls[xs_at + k * R + d] += delta;
+                }
+                __syncthreads();
+            }
+            const int j0 = it > 0 ? m : origin ? 0 : m + q.LA;   // as in k_rtisi_stream
+#pragma nounroll
+            for (int k = 0; k < K; ++k) {
+                float *dst = ls + (size_t)k * sstride + (it == 0 ? cur : nxt);
+                int slot = it > 0 || origin ? slot_m : slot_m == 0 ? q.LA : slot_m - 1;
+                for (int j = j0; j <= last; j += 2) {
+                    const bool two = j + 1 <= last;
+                    float2 *r = bufB;
+#pragma nounroll
+                    for (int ph = it == 0 ? 1 : 0; ph < 2; ++ph) {
+                        float2 *x = bufA, *y = bufB;
+                        if (ph == 0) {
+                            const float *xk = ls + xs_at + k * R + (j - m) * hop;
+                            for (int n = threadIdx.x; n < N; n += blockDim.x) {
+                                const float w = awin[n];
+                                x[n] = make_float2(xk[n] * w, two ? xk[hop + n] * w : 0.f);
+                            }
+                        } else if (it == 0) {
+                            int bk = b * K + k;   // where the rows of this source start, derived here: see the transform's uniforms
+                            asm volatile("" : "+s"(bk));
+                            const float2 *Sh = h.S + (size_t)bk * q.held_rows * F, *Sc = S + (size_t)bk * q.chunk_rows * F;
+                            const float2 *r0 = rtisi_row(Sh, Sc, j, q.nheld, F), *r1 = two ? rtisi_row(Sh, Sc, j + 1, q.nheld, F) : r0;
+                            for (int i = threadIdx.x; i < F; i += blockDim.x)
+                                rtisi_put_pair(x, i, N, r0[i], two ? r1[i] : make_float2(0.f, 0.f));
+                        } else {
+                            x = r == bufB ? bufA : (q.odd > 1 ? bufC : bufB);   // the buffers: as in k_rtisi
+                            y = r;
+                            const bool commit = it == q.iters && j == m;
+                            int bk = b * K + k;   // as above
+                            asm volatile("" : "+s"(bk));
+                            const float *Ah = h.A + (size_t)bk * q.held_rows * F, *Ac = A + (size_t)bk * q.chunk_rows * F;
+                            float2 *Co = Cout + (size_t)bk * q.out_rows * F;
+                            const float *A0 = rtisi_row(Ah, Ac, j, q.nheld, F), *A1 = two ? rtisi_row(Ah, Ac, j + 1, q.nheld, F) : A0;
+                            for (int i = threadIdx.x; i < F; i += blockDim.x) {
+                                const float2 zk = r[i], zn = r[i == 0 ? 0 : N - i];
+                                const float2 u = rtisi_project(make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)), A0[i]);
+                                float2 v = make_float2(0.f, 0.f);
+                                if (two) v = rtisi_project(make_float2(0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)), A1[i]);
+                                if (commit) Co[(size_t)m * F + i] = u;
+                                rtisi_put_pair(x, i, N, u, v);
+                            }
+                        }
+                        __syncthreads();
+                        // one call site for both directions and every source, its uniforms derived here: see k_rtisi.  An instance of
+                        // its own, so that those of the three kernels above stay what they were.
+                        int n_ = N, odd_ = q.odd, log2e_ = q.log2e;
+                        asm volatile("" : "+s"(n_), "+s"(odd_), "+s"(log2e_));
+                        r = fft_lds<4>(x, y, n_, odd_, log2e_, ph == 0 ? -1.0f : 1.0f);
+                    }
+                    const float inv = 1.0f / (float)N;
+                    float *o0 = dst + (size_t)slot * N, *o1 = dst + (size_t)(slot < q.LA ? slot + 1 : 0) * N;
+                    for (int n = threadIdx.x; n < N; n += blockDim.x) {
+                        const float w = inv * swin[n];
+                        o0[n] = r[n].x * w;
+                        if (two) o1[n] = r[n].y * w;
+                    }
+                    __syncthreads();   // r is the next load's buffer, dst the next reader's
+                    slot += 2;
+                    if (slot > q.LA) slot -= W;
+                    if (slot > q.LA) slot -= W;   // W == 1
+                }
+            }
+            if (it > 0) { const int t = cur; cur = nxt; nxt = t; }
+        }
+        if (q.iters == 0) {   // nothing was projected: the committed rows are the start rows
+#pragma nounroll
+            for (int k = 0; k < K; ++k) {
+                const float2 *r0 = rtisi_row(h.S + ((size_t)b * K + k) * q.held_rows * F, S + ((size_t)b * K + k) * q.chunk_rows * F, m,
+                                             q.nheld, F);
+                float2 *Co = Cout + ((size_t)b * K + k) * q.out_rows * F;
+                for (int i = threadIdx.x; i < F; i += blockDim.x) Co[(size_t)m * F + i] = r0[i];
+            }
+        }
+        // done_k += f_km; the hop samples no later frame reaches are final and g = 1 there: the signals are v_k + (y - sum_k v_k) / K,
+        // k ascending (what lies behind the last frame of the stream: below)
+        float *xb = xout ? xout + (size_t)b * K * q.out_samples : nullptr;
+        for (int n = threadIdx.x; n < N; n += blockDim.x) {
+            int pos = base + n;
+            if (pos >= R) pos -= R;
+            const int t = hop * m + n;
+            const bool out = xb && n < hop && t >= q.zero_lo && t < q.emit_end;
+            float share = 0.f;
+            if (out) {
+                float acc = 0.f;
+#pragma nounroll
+                for (int k = 0; k < K; ++k) {
+                    const float *sk = ls + (size_t)k * sstride;
+                    const float v = sk[pos] + sk[cur + slot_m * N + n];
+                    acc = k ? acc + v : v;
+                }
+                share = (misi_stream_y(h.y + hy_at, Y + cy_at, t, p.ny_held, p.ny_chunk) - acc) / (float)K;
+            }
+#pragma nounroll
+            for (int k = 0; k < K; ++k) {
+                float *sk = ls + (size_t)k * sstride;
+                const float v = sk[pos] + sk[cur + slot_m * N + n];
+                if (out) xb[(size_t)k * q.out_samples + (t - q.zero_lo)] = v + share;
+                sk[pos] = n < hop ? 0.f : v;
+            }
+        }
+        base += hop;
+        if (base >= R) base -= R;
+        if (++slot_m > q.LA) slot_m = 0;
+        __syncthreads();
+    }
+    if (q.closing && xout) {   // the N - hop samples behind the last commit: final now, also when this launch has no step (LA == 0)
+        float *xb = xout + (size_t)b * K * q.out_samples;
+        for (int d = threadIdx.x; d < N - hop; d += blockDim.x) {
+            int pos = base + d;
+            if (pos >= R) pos -= R;
+            const int t = hop * q.nsteps + d;
+            if (t >= q.zero_lo && t < q.emit_end) {
+                float acc = 0.f;
+#pragma nounroll
+                for (int k = 0; k < K; ++k) {
+                    const float v = ls[(size_t)k * sstride + pos];
+                    acc = k ? acc + v : v;
+                }
+                const float share = (misi_stream_y(h.y + hy_at, Y + cy_at, t, p.ny_held, p.ny_chunk) - acc) / (float)K;
+#pragma nounroll
+                for (int k = 0; k < K; ++k) xb[(size_t)k * q.out_samples + (t - q.zero_lo)] = ls[(size_t)k * sstride + pos] + share;
+            }
+        }
+    }
+    if (IN_LDS) {
+#pragma nounroll
+        for (int k = 0; k < K; ++k) {
+            float *gk = gs + (size_t)k * q.state_floats;
+            const float *lk = ls + (size_t)k * sstride;
+            for (int i = threadIdx.x; i < R; i += blockDim.x) gk[i] = lk[i];
+            for (int i = threadIdx.x; i < W * N; i += blockDim.x) gk[R + i] = lk[cur + i];
+        }
+    }
+}
+
 // Windows and scratch of the iteration, one set per device, serialised on the device by the event scheme of lws_stft.hip.  The
 // windows stay on the device between calls: a call with the windows of the previous one uploads nothing.
 struct GlaCtx {
@@ -1245,6 +1508,259 @@ extern "C" void lws_rtisi_stream_destroy(lws_rtisi_stream *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     for (Scratch *b : {&h->state, &h->held_s[0], &h->held_s[1], &h->held_a[0], &h->held_a[1], &h->abuf, &h->win_a, &h->win_s})
+        if (b->p) (void)hipFree(b->p);
+    if (h->last) (void)hipEventDestroy(h->last);
+    delete h;
+}
+
+// ---- Streaming online MISI: the handle.  As lws_rtisi_stream, for the K sources of each of B mixtures: besides state, held rows and
+// windows it owns the held mixture samples and, with the scratch placement, the room for target and xs -- nothing is shared with
+// other streams or with the calls on GlaCtx.
+struct lws_misi_stream {
+    int device = 0, B = 0, K = 0, N = 0, hop = 0, LA = 0, iters = 0, perfectrec = 0;
+    MisiLaPlan plan{};
+    size_t source_floats = 0;             // per source: ring, fcur and, with the scratch placement, the other frame buffer
+    size_t stream_floats = 0;             // per stream: K of those and, with the scratch placement, the (K + 1) R floats of target and xs
+    int y_rows = 0;                       // floats of a stream in held_y
+    Scratch state, held_s[2], held_a[2], held_y[2], abuf, win_a, win_s;
+    long long entered = 0, committed = 0; // frames pushed, frames committed
+    int base = 0, slot = 0, cur = 0;      // of the next step: ring offset, slot of its frame, which frame buffer is fcur
+    int held = 0;                         // which held buffers are current
+    bool ran = false, finished = false;
+    hipEvent_t last = nullptr;            // as lws_rtisi_stream
+    hipStream_t last_stream = nullptr;
+    bool busy = false;
+    std::mutex mu;
+};
+
+namespace {
+
+// mixture samples under the first M frames of a stream
+long long misi_need(const lws_misi_stream &h, long long M) {
+    return M <= 0 ? 0 : (long long)h.hop * (M - 1) + h.N - (h.perfectrec ? prepad(h.N, h.hop) : 0);
+}
+
+int misi_enter(lws_misi_stream &h, hipStream_t s) {
+    if (h.busy && s != h.last_stream) STFT_TRY(hipStreamWaitEvent(s, h.last, 0));
+    return LWS_OK;
+}
+int misi_leave(lws_misi_stream &h, hipStream_t s) {
+    STFT_TRY(hipEventRecord(h.last, s));
+    h.busy = true;
+    h.last_stream = s;
+    return LWS_OK;
+}
+
+// rows [at, at + frames) of the held buffers and the samples under them from a chunk: what arrives before the first commit can run.
+// Held sample t is sample t of the stream's timeline (the lead-in included, never read)
+int misi_stash(lws_misi_stream &h, const float2 *S, const float *A, const float *y, int frames, int samples, hipStream_t s) {
+    const size_t F = (size_t)h.N / 2 + 1, at = (size_t)h.entered, BK = (size_t)h.B * h.K;
+    const size_t y_at = (size_t)(h.perfectrec ? prepad(h.N, h.hop) : 0) + (size_t)misi_need(h, h.entered);
+    STFT_TRY(hipMemcpy2DAsync(static_cast<float2 *>(h.held_s[h.held].p) + at * F, (size_t)h.LA * F * sizeof(float2), S,
+                              (size_t)frames * F * sizeof(float2), (size_t)frames * F * sizeof(float2), BK, hipMemcpyDeviceToDevice, s));
+    if (A)
+        STFT_TRY(hipMemcpy2DAsync(static_cast<float *>(h.held_a[h.held].p) + at * F, (size_t)h.LA * F * sizeof(float), A,
+                                  (size_t)frames * F * sizeof(float), (size_t)frames * F * sizeof(float), BK, hipMemcpyDeviceToDevice, s));
+    STFT_TRY(hipMemcpy2DAsync(static_cast<float *>(h.held_y[h.held].p) + y_at, (size_t)h.y_rows * sizeof(float), y,
+                              (size_t)samples * sizeof(float), (size_t)samples * sizeof(float), h.B, hipMemcpyDeviceToDevice, s));
+    return LWS_OK;
+}
+
+// the commit steps committed .. committed + nsteps - 1; M < 0 while the stream is open, the frame count at its end
+int misi_launch(lws_misi_stream &h, const float2 *S, const float *A, const float *y, int frames, int samples, float2 *C_out,
+                float *x_out, int out_rows, int out_samples, int nsteps, long long M, hipStream_t s) {
+    const bool closing = M >= 0;
+    const int LA = (closing && !h.ran) ? (int)M - 1 : h.LA;   // an end before the first commit: no frame beyond M - 1 to look at
+    const MisiLaPlan p = misi_la_plan(h.N, h.hop, LA, h.K);
+    const Factors fc = factor(h.N);
+    const long long t0 = (long long)h.hop * h.committed, lo = h.perfectrec ? prepad(h.N, h.hop) : 0;
+    const int R = h.N + LA * h.hop, back = h.N / h.hop + 1;
+    MisiStreamArgs a{};
+    RtisiStreamArgs &q = a.r;
+    q.N = h.N; q.odd = fc.odd; q.log2e = fc.log2e; q.hop = h.hop; q.LA = LA; q.iters = h.iters;
+    q.nsteps = nsteps;
+    q.Mrel = closing ? (int)(M - h.committed) : nsteps + LA;
+    q.closing = closing;
+    q.origin = h.committed == 0;
+    q.zero_lo = lo > t0 ? (int)(lo - t0) : 0;
+    q.emit_end = closing && h.perfectrec ? (int)((long long)h.hop * M - t0) : 0x7fffffff;
+    q.base = h.base; q.slot_m = h.slot; q.cur = h.cur;
+    q.nheld = h.ran ? h.LA : (int)h.entered;   // before the first launch: the stashed frames (the chunk's are not counted yet)
+    q.held_rows = h.LA;
+    q.chunk_rows = frames; q.out_rows = out_rows; q.out_samples = out_samples;
+    q.state_floats = h.source_floats;
+    a.K = h.K;
+    a.frame0 = h.committed < back ? -(int)h.committed : -back;
+    a.ny_held = h.ran ? R - h.hop : (int)(lo + misi_need(h, h.entered));
+    a.ny_chunk = samples;
+    a.y_rows = h.y_rows;
+    a.y_keep = R - h.hop;
+    a.stream_floats = h.stream_floats;
+    const int nxt = h.held ^ 1;
+    const MisiStreamHeld held{static_cast<const float2 *>(h.held_s[h.held].p), static_cast<const float *>(h.held_a[h.held].p),
+                              static_cast<const float *>(h.held_y[h.held].p),
+                              closing || h.iters > 0 ? nullptr : static_cast<float2 *>(h.held_s[nxt].p),
+                              closing || h.iters == 0 ? nullptr : static_cast<float *>(h.held_a[nxt].p),
+                              closing ? nullptr : static_cast<float *>(h.held_y[nxt].p)};
+    const float *wa = static_cast<const float *>(h.win_a.p), *ws = static_cast<const float *>(h.win_s.p);
+    float *st = static_cast<float *>(h.state.p);
+    if (p.in_lds)
+        hipLaunchKernelGGL(k_misi_la_stream<true>, dim3(h.B), dim3(p.threads), p.lds_bytes, s, S, A, y, C_out, x_out, wa, ws, st, held, a);
+    else
+        hipLaunchKernelGGL(k_misi_la_stream<false>, dim3(h.B), dim3(p.threads), p.lds_bytes, s, S, A, y, C_out, x_out, wa, ws, st, held, a);
+    STFT_TRY(hipGetLastError());
+    h.base = (int)(((long long)h.base + (long long)h.hop * nsteps) % R);
+    h.slot = (int)(((long long)h.slot + nsteps) % (LA + 1));
+    h.cur ^= (int)(((long long)h.iters * nsteps) & 1);
+    h.held = nxt;
+    h.committed += nsteps;
+    h.ran = true;
+    return LWS_OK;
+}
+
+}  // namespace
+
+extern "C" int lws_misi_stream_create(int device, int B, int K, int N, int fshift, const double *awin, const double *swin,
+                                      int perfectrec, int iters, int look_ahead, lws_misi_stream **out) {
+    if (!out) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    *out = nullptr;
+    int rc = check_shape(device, B, 1, N, fshift);
+    if (rc) return rc;
+    if (B < 1) return lws::set_error(LWS_ERR_INVALID, "%d streams", B);
+    if (K < 1) return lws::set_error(LWS_ERR_INVALID, "%d sources", K);
+    if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
+    if (look_ahead < 0) return lws::set_error(LWS_ERR_INVALID, "look-ahead of %d frames", look_ahead);
+    if (!awin || !swin) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    if ((long long)(look_ahead + 2) * fshift + N > 0x7fffffffLL / 2)
+        return lws::set_error(LWS_ERR_UNSUPPORTED, "look-ahead of %d frames", look_ahead);
+    const MisiLaPlan plan = misi_la_plan(N, fshift, look_ahead, K);
+    const size_t frame_floats = (size_t)(look_ahead + 1) * N;
+    const size_t source_floats = plan.in_lds ? plan.source_floats - frame_floats : plan.source_floats;
+    if (2 * ((size_t)K + 1) * plan.source_floats > 0x7fffffffULL)   // the kernel indexes a stream's state, target and xs with ints
+        return lws::set_error(LWS_ERR_UNSUPPORTED, "look-ahead of %d frames", look_ahead);
+    STFT_TRY(hipSetDevice(device));
+    STFT_TRY(lws::allow_dynamic_lds<&k_misi_la_stream<true>>((int)RTISI_LDS_CAP));
+    STFT_TRY(lws::allow_dynamic_lds<&k_misi_la_stream<false>>(3 * MAXN * (int)sizeof(float2)));
+    lws_misi_stream *h = new lws_misi_stream;
+    h->device = device; h->B = B; h->K = K; h->N = N; h->hop = fshift; h->LA = look_ahead; h->iters = iters;
+    h->perfectrec = perfectrec ? 1 : 0;
+    h->plan = plan;
+    h->source_floats = source_floats;
+    h->stream_floats = (size_t)K * source_floats + (plan.in_lds ? 0 : ((size_t)K + 1) * ((size_t)N + (size_t)look_ahead * fshift));
+    const size_t F = (size_t)N / 2 + 1, R = (size_t)N + (size_t)look_ahead * fshift;
+    // held samples: the R - hop the next launch still needs; before the first launch, the lead-in (never read) and what was stashed
+    const size_t lo = perfectrec ? (size_t)prepad(N, fshift) : 0, keep = R - fshift;
+    h->y_rows = (int)(keep > lo ? keep : lo) + 1;
+    const size_t state_bytes = (size_t)B * h->stream_floats * sizeof(float), rows = (size_t)B * K * look_ahead * F;
+    const size_t y_bytes = (size_t)B * h->y_rows * sizeof(float);
+    std::vector<float> wa(N), ws(N);
+    for (int i = 0; i < N; ++i) { wa[i] = (float)awin[i]; ws[i] = (float)swin[i]; }
+    rc = h->state.ensure(state_bytes);
+    if (!rc) rc = h->win_a.ensure((size_t)N * sizeof(float));
+    if (!rc) rc = h->win_s.ensure((size_t)N * sizeof(float));
+    if (!rc) rc = h->held_y[0].ensure(y_bytes);
+    if (!rc) rc = h->held_y[1].ensure(y_bytes);
+    if (!rc) rc = h->held_s[0].ensure(rows * sizeof(float2));
+    if (!rc && iters == 0) rc = h->held_s[1].ensure(rows * sizeof(float2));
+    if (!rc && iters > 0) rc = h->held_a[0].ensure(rows * sizeof(float));
+    if (!rc && iters > 0) rc = h->held_a[1].ensure(rows * sizeof(float));
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipEventCreateWithFlags(&h->last, hipEventDisableTiming);
+    if (!rc && e == hipSuccess) e = hipMemset(h->state.p, 0, state_bytes);
+    if (!rc && e == hipSuccess) e = hipMemset(h->held_y[0].p, 0, y_bytes);
+    if (!rc && e == hipSuccess) e = hipMemset(h->held_y[1].p, 0, y_bytes);
+    if (!rc && e == hipSuccess) e = hipMemcpy(h->win_a.p, wa.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice);
+    if (!rc && e == hipSuccess) e = hipMemcpy(h->win_s.p, ws.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice);
+    if (!rc && e == hipSuccess) e = hipDeviceSynchronize();   // the state is zero before any stream of the caller's touches it
+    if (!rc && e != hipSuccess) rc = lws::set_error(LWS_ERR_HIP, "creating a stream's state failed: %s", hipGetErrorString(e));
+    if (rc) {
+        lws_misi_stream_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return LWS_OK;
+}
+
+extern "C" int lws_misi_stream_push(lws_misi_stream *h, const void *S_dev, const float *A_dev, const float *y_dev, int frames,
+                                    int samples, void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out, void *stream) {
+    if (frames_out) *frames_out = 0;
+    if (samples_out) *samples_out = 0;
+    if (!h) return lws::set_error(LWS_ERR_INVALID, "null stream handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (frames < 0) return lws::set_error(LWS_ERR_INVALID, "%d frames", frames);
+    if (h->finished) return lws::set_error(LWS_ERR_INVALID, "push after finish");
+    if (((long long)frames + h->LA + 2) * h->hop + h->N > 0x7fffffffLL)
+        return lws::set_error(LWS_ERR_UNSUPPORTED, "%d frames in one push", frames);
+    const long long entered = h->entered + frames, want = misi_need(*h, entered) - misi_need(*h, h->entered);
+    if (samples != want)
+        return lws::set_error(LWS_ERR_INVALID, "%d mixture samples for %d frames after %lld: expected %lld", samples, frames, h->entered,
+                              want);
+    if (frames == 0) return LWS_OK;
+    if (!S_dev || !y_dev) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    const long long nsteps = entered > h->LA ? entered - h->LA - h->committed : 0;
+    if (nsteps > 0 && !C_out_dev) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    STFT_TRY(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = misi_enter(*h, s);
+    if (rc) return rc;
+    const float2 *S = static_cast<const float2 *>(S_dev);
+    const size_t bins = (size_t)h->B * h->K * frames * (h->N / 2 + 1);
+    if (!A_dev && h->iters > 0) {   // |S| by the kernel lws_misi_la_dev takes it from
+        if ((rc = h->abuf.ensure(bins * sizeof(float)))) return rc;
+        hipLaunchKernelGGL(k_gla_abs, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, s, S, static_cast<float *>(h->abuf.p), bins);
+        A_dev = static_cast<const float *>(h->abuf.p);
+    }
+    if (h->iters == 0) A_dev = nullptr;
+    if (nsteps == 0) {
+        if ((rc = misi_stash(*h, S, A_dev, y_dev, frames, samples, s))) return rc;
+    } else {
+        const long long t0 = (long long)h->hop * h->committed, lo = h->perfectrec ? prepad(h->N, h->hop) : 0;
+        const long long from = lo > t0 ? lo : t0, to = (long long)h->hop * (h->committed + nsteps);
+        if ((rc = misi_launch(*h, S, A_dev, y_dev, frames, samples, static_cast<float2 *>(C_out_dev), x_out_dev, frames,
+                              frames * h->hop, (int)nsteps, -1, s)))
+            return rc;
+        if (frames_out) *frames_out = (int)nsteps;
+        if (samples_out) *samples_out = to > from ? (int)(to - from) : 0;
+    }
+    h->entered = entered;
+    return misi_leave(*h, s);
+}
+
+extern "C" int lws_misi_stream_finish(lws_misi_stream *h, void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out,
+                                      void *stream) {
+    if (frames_out) *frames_out = 0;
+    if (samples_out) *samples_out = 0;
+    if (!h) return lws::set_error(LWS_ERR_INVALID, "null stream handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->finished) return lws::set_error(LWS_ERR_INVALID, "finish after finish");
+    const long long M = h->entered, nsteps = M - h->committed;
+    // no step left (nothing pushed, or look_ahead == 0): only the samples behind the last commit, which perfectrec cuts
+    if (nsteps == 0 && (M == 0 || h->perfectrec || !x_out_dev)) {
+        h->finished = true;
+        if (samples_out && M > 0 && !h->perfectrec) *samples_out = h->N - h->hop;
+        return LWS_OK;
+    }
+    if (nsteps > 0 && !C_out_dev) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    STFT_TRY(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = misi_enter(*h, s);
+    if (rc) return rc;
+    const long long t0 = (long long)h->hop * h->committed, lo = h->perfectrec ? prepad(h->N, h->hop) : 0;
+    const long long from = lo > t0 ? lo : t0, to = h->perfectrec ? (long long)h->hop * M : (long long)h->hop * (M - 1) + h->N;
+    if ((rc = misi_launch(*h, nullptr, nullptr, nullptr, 0, 0, static_cast<float2 *>(C_out_dev), x_out_dev, h->LA,
+                          h->N + h->LA * h->hop, (int)nsteps, M, s)))
+        return rc;
+    h->finished = true;
+    if (frames_out) *frames_out = (int)nsteps;
+    if (samples_out) *samples_out = to > from ? (int)(to - from) : 0;
+    return misi_leave(*h, s);
+}
+
+extern "C" void lws_misi_stream_destroy(lws_misi_stream *h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    for (Scratch *b : {&h->state, &h->held_s[0], &h->held_s[1], &h->held_a[0], &h->held_a[1], &h->held_y[0], &h->held_y[1],
+                       &h->abuf, &h->win_a, &h->win_s})
         if (b->p) (void)hipFree(b->p);
     if (h->last) (void)hipEventDestroy(h->last);
     delete h;

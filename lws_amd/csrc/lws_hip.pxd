@@ -68,6 +68,15 @@ cdef extern from "lws_hip.h" nogil:
     int lws_rtisi_stream_finish(lws_rtisi_stream *h, void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out,
                                 void *stream)
     void lws_rtisi_stream_destroy(lws_rtisi_stream *h)
+    ctypedef struct lws_misi_stream:
+        pass
+    int lws_misi_stream_create(int device, int B, int K, int N, int fshift, const double *awin, const double *swin, int perfectrec,
+                               int iters, int look_ahead, lws_misi_stream **out)
+    int lws_misi_stream_push(lws_misi_stream *h, const void *S_dev, const float *A_dev, const float *y_dev, int frames, int samples,
+                             void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out, void *stream)
+    int lws_misi_stream_finish(lws_misi_stream *h, void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out,
+                               void *stream)
+    void lws_misi_stream_destroy(lws_misi_stream *h)
     int lws_rtisi_la_placement(int N, int fshift, int look_ahead, int K, int *in_lds, int *threads, size_t *lds_bytes)
     int lws_hann(int n, int symmetric, int use_offset, double *out)
     int lws_synthwin(const double *awin, int fsize, int fshift, const double *swin, double *out)

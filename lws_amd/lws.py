@@ -585,7 +585,7 @@ def rtisi_la_dev(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitu
 # Online MISI: the K sources of a known mixture under a look-ahead -- MISI as RTISI-LA is Griffin-Lim
 # --------------------------------------------------------------------------------------------
 def misi_la(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=None, perfectrec=False, return_signals=False,
-            _perturb=None):
+            _perturb=None, open_end=False):
     """MISI under a look-ahead from the starts S, (K, T, F) or a stack (B, K, T, F), and the real mixture(s) `mixture`, (len,) /
     (B, len) with len that of istft(S[k]), in fp64 on the host: the definition the device form is held to.  Frame m of every
     source depends on no input frame later than m + look_ahead and on no mixture sample behind the end of that frame.  On the
@@ -599,8 +599,17 @@ def misi_la(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3, mag
     |S|); zero iterations return S.  With look_ahead >= T - 1 the first commit is `iterations` steps of misi().  At
     look_ahead = 0 the last active frame is always transformed from a partial sum and the iteration moves away from a good
     start, as RTISI itself does.  return_signals: also s_k = done_k + (y - sum_j done_j) / K cut as istft cuts it, (K, len) /
-    (B, K, len), which sum to the mixture.  (_perturb(m, it, b, X) -> X: replaces the (K, last - m + 1, F) stack of projections of
-    one inner iteration; the error model of the tests.)"""
+    (B, K, len), which sum to the mixture.
+    open_end: nothing a step with m + look_ahead <= T - 1 computes depends on where the input ends, so the rows [:, :T1 - look_ahead]
+    of a run on S[:, :T1] and the mixture under those frames are those of a run on any longer input: what a stream (MisiLaStream)
+    computes.  The mixture then has fshift (T - 1) + fsize - lo samples, lo the lead-in perfectrec cuts (else 0): every sample under
+    the frames, with perfectrec the fsize - fshift more that stft reads behind what istft returns.  The tail is not read as zero
+    inside the iteration (the lead-in still is, and the returned signals are still cut as istft cuts them), the frame count need not
+    be one the round trip keeps, and the denominator of g sums w over ALL frames j >= 0 that would cover a sample, as if the input
+    never ended, in the steps with m + look_ahead <= T - 1; in the later ones, which know the end, over the frames 0 .. T-1 as
+    without open_end, so that g = 1 there and the last frames explain the whole mixture.
+    (_perturb(m, it, b, X) -> X: replaces the (K, last - m + 1, F) stack of projections of one inner iteration; the error model of
+    the tests.)"""
     n, _ = _gla_args(iterations, 0.0)
     LA = _look_ahead_arg(look_ahead)
     S = np.asarray(S)
@@ -623,24 +632,32 @@ def misi_la(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3, mag
     if perfectrec is True:
         lo, hi = _perfectrec_prepad(fsize, fshift), total - (fsize - fshift)
         keep[:lo] = 0.0
-        keep[max(hi, 0):] = 0.0
-        back = stft(np.zeros(max(hi - lo, 0)), fsize, fshift, awin, perfectrec=True).shape[0]
-        if n > 0 and back != T:
-            raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
-    length = max(hi - lo, 0)
-    if y.ndim != S.ndim - 2 or y2.shape != (B, length):
+        if not open_end:
+            keep[max(hi, 0):] = 0.0
+            back = stft(np.zeros(max(hi - lo, 0)), fsize, fshift, awin, perfectrec=True).shape[0]
+            if n > 0 and back != T:
+                raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
+    length = max(hi - lo, 0)            # of the returned signals
+    ylen = total - lo if open_end else length
+    if y.ndim != S.ndim - 2 or y2.shape != (B, ylen):
         raise ValueError('mixture of shape %s for %s spectrograms of %d frames: expected %s' %
-                         (y.shape, S.shape[:-2], T, S.shape[:-3] + (length,)))
+                         (y.shape, S.shape[:-2], T, S.shape[:-3] + (ylen,)))
     w = awin * swin
     den = np.zeros(total)
     for j in range(T):
         den[fshift * j: fshift * j + fsize] += w
+    den_open = den
+    if open_end:   # over every frame j >= 0 that would cover a sample: the frames behind T - 1 too
+        den_open = np.zeros(total + fsize)
+        for j in range(T + (fsize - 1) // fshift):
+            den_open[fshift * j: fshift * j + fsize] += w[:max(0, min(fsize, total + fsize - fshift * j))]
+        den_open = den_open[:total]
     out = S4.astype(np.complex128)
     sig = np.empty((B, K, length))
     for b in range(B if (n > 0 or return_signals) else 0):
         c, done, f, entered = out[b], np.zeros((K, total)), np.zeros((K, T, fsize)), 0
         yfull, num = np.zeros(total), np.zeros(total)
-        yfull[lo: lo + length] = y2[b]
+        yfull[lo: lo + ylen] = y2[b]
         for m in range(T):
             last = min(m + LA, T - 1)
             while entered <= last:
@@ -648,7 +665,8 @@ def misi_la(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3, mag
                     f[k, entered] = swin * np.fft.irfft(c[k, entered], fsize)
                 num[fshift * entered: fshift * entered + fsize] += w
                 entered += 1
-            target = keep * np.where(den != 0, num / np.where(den != 0, den, 1.0), 1.0) * yfull
+            dn = den_open if m + LA <= T - 1 else den
+            target = keep * np.where(dn != 0, num / np.where(dn != 0, dn, 1.0), 1.0) * yfull
             for it in range(1, n + 1):
                 yk = done.copy()
                 for j in range(m, last + 1):
@@ -717,6 +735,114 @@ def misi_la_dev(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3,
                       LA, device=int(device), stream=torch.cuda.current_stream(t4.device).cuda_stream)
     out = t4[0] if single else t4
     return (out, sig[0] if single else sig) if return_signals else out
+
+
+class MisiLaStream(object):
+    """misi_la_dev() for frames and mixture that arrive over time (k_misi_la_stream of lws_gla.hip).  push() takes the next rows of the
+    K sources, (K, Tc, F) -- or (B, K, Tc, F) for `batch`=B mixtures side by side -- and the next samples_needed(Tc) samples of the
+    mixture, (n,) / (B, n), numpy or torch: after M frames the stream has every mixture sample under them, fshift (M - 1) + fsize
+    less the lead-in perfectrec cuts, so the first push carries fsize - fshift more than the later ones per frame and, with
+    perfectrec, the last the fsize - fshift zeros stft pads with (or the real continuation).  It returns the rows that could be
+    committed, a new complex64 torch tensor (K, n_f, F) / (B, K, n_f, F): frame m is committed once frame m + look_ahead has been
+    pushed, so n_f may be 0.  finish() returns the remaining look_ahead frames and ends the stream.  With return_signals both also
+    return the float32 samples those commits finalised, (K, k) / (B, K, k), which sum to the mixture.  Everything returned,
+    concatenated, is misi_la(everything pushed, ..., open_end=True) and its signals: however the input is cut into chunks, bit for bit.
+    The state lives on the device between calls; a call runs on the caller's current torch stream, only enqueues work and keeps no
+    reference to its arguments.  magnitudes: the targets of the pushed rows (default |S|).  iterations=0 returns the pushed rows
+    themselves, with the same latency.  A push with another sample count raises ValueError and leaves the stream as it was.  close()
+    frees the device state (also on deletion)."""
+
+    def __init__(self, K, fsize, fshift, awin, swin, iterations, look_ahead=3, perfectrec=False, batch=None, return_signals=False,
+                 device=0):
+        self._h = None
+        n, _ = _gla_args(iterations, 0.0)
+        self.look_ahead = _look_ahead_arg(look_ahead)
+        if int(K) != K or K < 1:
+            raise ValueError('K must be a positive integer, got %r' % (K,))
+        if batch is not None and (int(batch) != batch or batch < 1):
+            raise ValueError('batch must be None or a positive integer, got %r' % (batch,))
+        if fsize % 2:
+            raise ValueError('Odd ffts not supported.')
+        self.K, self.fsize, self.fshift, self.iterations, self.perfectrec = int(K), int(fsize), int(fshift), n, perfectrec is True
+        self.batch, self.return_signals, self.device = None if batch is None else int(batch), bool(return_signals), int(device)
+        self._B, self._F = 1 if batch is None else int(batch), int(fsize) // 2 + 1
+        self._lo = _perfectrec_prepad(self.fsize, self.fshift) if self.perfectrec else 0
+        self._entered = 0
+        self.finished = False
+        swin = np.squeeze(np.asarray(swin, dtype=np.float64))
+        self._h = _capi.misi_stream_create(self._B, self.K, fsize, fshift, awin, swin, self.perfectrec, n, self.look_ahead,
+                                           device=self.device)
+
+    def _need(self, M):
+        return 0 if M <= 0 else self.fshift * (M - 1) + self.fsize - self._lo
+
+    def samples_needed(self, Tc):
+        """The mixture samples the next push of Tc frames must carry."""
+        return self._need(self._entered + int(Tc)) - self._need(self._entered)
+
+    def _returns(self, out, sig, nf, ns):
+        out = out[:, :, :nf]
+        if self.batch is None:
+            out = out[0]
+        if not self.return_signals:
+            return out
+        sig = sig[:, :, :ns]
+        return out, (sig[0] if self.batch is None else sig)
+
+    def push(self, S, mixture, magnitudes=None):
+        import torch
+        if self._h is None or self.finished:
+            raise ValueError('push on a stream that has finished or been closed')
+        t = _dev_tensor(S, torch.complex64, self.device)
+        want = 3 if self.batch is None else 4
+        if t.dim() != want or t.shape[-1] != self._F or t.shape[-3] != self.K or (self.batch is not None and t.shape[0] != self._B):
+            raise ValueError('expected rows of shape %s, got %s' %
+                             ((self.K, 'Tc', self._F) if self.batch is None else (self._B, self.K, 'Tc', self._F), tuple(t.shape)))
+        A = None
+        if magnitudes is not None:
+            A = _dev_tensor(magnitudes, torch.float32, self.device)
+            if A.shape != t.shape:
+                raise ValueError('magnitudes of shape %s for rows of shape %s' % (tuple(A.shape), tuple(t.shape)))
+        Tc = t.shape[-2]
+        y = _dev_tensor(mixture, torch.float32, self.device)
+        ns_in = self.samples_needed(Tc)
+        if y.dim() != want - 2 or y.shape[-1] != ns_in or (self.batch is not None and y.shape[0] != self._B):
+            raise ValueError('mixture of shape %s for %d more frames after %d: expected %s' %
+                             (tuple(y.shape), Tc, self._entered, ((ns_in,) if self.batch is None else (self._B, ns_in))))
+        out = torch.empty((self._B, self.K, Tc, self._F), dtype=torch.complex64, device=t.device)
+        sig = torch.empty((self._B, self.K, Tc * self.fshift), dtype=torch.float32, device=t.device) if self.return_signals else None
+        nf, ns = 0, 0
+        if Tc > 0:
+            nf, ns = _capi.misi_stream_push(self._h, t.data_ptr(), None if A is None else A.data_ptr(), y.data_ptr(), Tc, ns_in,
+                                            out.data_ptr(), None if sig is None else sig.data_ptr(),
+                                            stream=torch.cuda.current_stream(t.device).cuda_stream)
+            self._entered += Tc
+        return self._returns(out, sig, nf, ns)
+
+    def finish(self):
+        import torch
+        if self._h is None or self.finished:
+            raise ValueError('finish on a stream that has finished or been closed')
+        dev = torch.device("cuda", self.device)
+        out = torch.empty((self._B, self.K, self.look_ahead, self._F), dtype=torch.complex64, device=dev)
+        sig = None
+        if self.return_signals:
+            sig = torch.empty((self._B, self.K, self.fsize + self.look_ahead * self.fshift), dtype=torch.float32, device=dev)
+        nf, ns = _capi.misi_stream_finish(self._h, out.data_ptr() if out.numel() else None, None if sig is None else sig.data_ptr(),
+                                          stream=torch.cuda.current_stream(dev).cuda_stream)
+        self.finished = True
+        return self._returns(out, sig, nf, ns)
+
+    def close(self):
+        h, self._h = self._h, None
+        if h is not None:
+            _capi.misi_stream_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown
+            pass
 
 
 def extspec(S, L, Q):
@@ -1083,17 +1209,24 @@ class lws(object):
         return RtisiLaStream(self.fsize, self.fshift, self.awin, self.swin, iterations,
                              look_ahead=self.look_ahead if look_ahead is None else look_ahead, perfectrec=self.perfectrec, batch=batch, return_signal=return_signal, device=self.device)
 
-    def misi_la(self, S, mixture, iterations, look_ahead=None, magnitudes=None, return_signals=False):
+    def misi_la(self, S, mixture, iterations, look_ahead=None, magnitudes=None, return_signals=False, open_end=False):
         """Host fp64 form with this object's windows, perfectrec and (look_ahead=None) look-ahead: see the module's misi_la."""
         return misi_la(S, mixture, self.fsize, self.fshift, self.awin, self.swin, iterations,
                        look_ahead=self.look_ahead if look_ahead is None else look_ahead, magnitudes=magnitudes,
-                       perfectrec=self.perfectrec, return_signals=return_signals)
+                       perfectrec=self.perfectrec, return_signals=return_signals, open_end=open_end)
 
     def misi_la_dev(self, S, mixture, iterations, look_ahead=None, magnitudes=None, return_signals=False):
         """Device form: a new complex64 torch tensor, see the module's misi_la_dev."""
         return misi_la_dev(S, mixture, self.fsize, self.fshift, self.awin, self.swin, iterations,
                            look_ahead=self.look_ahead if look_ahead is None else look_ahead, magnitudes=magnitudes,
                            perfectrec=self.perfectrec, return_signals=return_signals, device=self.device)
+
+    def misi_la_stream(self, K, iterations, look_ahead=None, batch=None, return_signals=False):
+        """A MisiLaStream for K sources with the windows, look-ahead and device of this object: push() rows and mixture samples as
+        they arrive, then finish()."""
+        return MisiLaStream(K, self.fsize, self.fshift, self.awin, self.swin, iterations,
+                            look_ahead=self.look_ahead if look_ahead is None else look_ahead, perfectrec=self.perfectrec, batch=batch,
+                            return_signals=return_signals, device=self.device)
 
     def nofuture_lws(self, S, iterations=None, thresholds=None):
         if iterations is None:
