@@ -247,6 +247,29 @@ int lws_misi_dev(int device, void *C_dev, const float *A_dev, const float *y_dev
 int lws_rtisi_la_dev(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift,
                      const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream);
 
+/* How a frame enters the look-ahead iterations (the *_ex entry points below; the ones without _ex pass LWS_START_GIVEN).
+ *   LWS_START_GIVEN   : from the caller's start row, f_j = inv(c_j): C_dev / S_dev carry a phase.
+ *   LWS_START_OVERLAP : RTISI-LA only -- RTISI's own initial estimate.  Frames enter one at a time, j ascending; frame j, entering in
+ *                       commit step m, takes c_j = A_j X / |X| with X = fwd(keep (done + sum_{i = m..j-1} f_i) at hop j), the
+ *                       transform of the partial overlap-add sum under it (A_j + 0j where |X| == 0: frame 0, a silent sum, and
+ *                       every frame at fshift == N), then f_j = inv(c_j).
+ *   LWS_START_MIXTURE : online MISI only -- the mixture phase.  Frame j of every source k takes c_kj = A_kj X / |X| with
+ *                       X = fwd(keep y at hop j), one transform of the mixture under the frame for all K sources.
+ * Under the last two only magnitudes are read: A_dev, or |C| / |S| where it is NULL, and the phases of the start are ignored; the
+ * entry rows are a result of their own, so iters == 0 returns them (and their signals) instead of the start.  Nothing else
+ * changes: the iterations, the commits, the open end of the streams, the placement lws_rtisi_la_placement reports.  A start the
+ * function does not take: LWS_ERR_INVALID, nothing enqueued. */
+enum {
+    LWS_START_GIVEN = 0,
+    LWS_START_OVERLAP = 1,
+    LWS_START_MIXTURE = 2
+};
+
+/* lws_rtisi_la_dev with a start: LWS_START_GIVEN or LWS_START_OVERLAP.  Under LWS_START_OVERLAP C_dev is read for |C| only, and
+ * only where A_dev is NULL; every row is written, also with iters == 0. */
+int lws_rtisi_la_dev_ex(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift,
+                        const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, int start, void *stream);
+
 /* Streaming RTISI-LA (lws_gla.hip): lws_rtisi_la_dev for frames that arrive over time, B streams side by side, the state of the
  * iteration (the overlap-add ring, the windowed inverse frames and the magnitudes of the look_ahead frames still active; per stream)
  * in device memory owned by the handle.  The rows all calls return, one after another, are what one call with every pushed row
@@ -268,6 +291,12 @@ int lws_rtisi_la_dev(int device, void *C_dev, const float *A_dev, float *x_dev, 
 typedef struct lws_rtisi_stream lws_rtisi_stream;
 int lws_rtisi_stream_create(int device, int B, int N, int fshift, const double *awin, const double *swin, int perfectrec, int iters,
                             int look_ahead, lws_rtisi_stream **out);
+/* ... with a start, LWS_START_GIVEN or LWS_START_OVERLAP, for the life of the stream: the stream then computes
+ * lws_amd.rtisi_la(..., start='overlap', open_end=True).  Under LWS_START_OVERLAP push takes magnitudes alone: S_dev may be NULL
+ * where A_dev is given (and is read for |S| only where it is not); with iters == 0 the rows returned are the entry estimates.  push,
+ * finish and destroy are the same functions. */
+int lws_rtisi_stream_create_ex(int device, int B, int N, int fshift, const double *awin, const double *swin, int perfectrec, int iters,
+                               int look_ahead, int start, lws_rtisi_stream **out);
 int lws_rtisi_stream_push(lws_rtisi_stream *h, const void *S_dev, const float *A_dev, int frames, void *C_out_dev, float *x_out_dev,
                           int *frames_out, int *samples_out, void *stream);
 int lws_rtisi_stream_finish(lws_rtisi_stream *h, void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out, void *stream);
@@ -290,6 +319,11 @@ void lws_rtisi_stream_destroy(lws_rtisi_stream *h);
  * the device transform: as lws_griffin_lim_dev. */
 int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, float *x_dev, int B, int K, int M, int N,
                     int fshift, const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream);
+/* ... with a start: LWS_START_GIVEN or LWS_START_MIXTURE (above).  Under LWS_START_MIXTURE C_dev is read for |C| only, and only where
+ * A_dev is NULL; every row is written, also with iters == 0. */
+int lws_misi_la_dev_ex(int device, void *C_dev, const float *A_dev, const float *y_dev, float *x_dev, int B, int K, int M, int N,
+                       int fshift, const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, int start,
+                       void *stream);
 
 /* Streaming online MISI (lws_gla.hip): lws_misi_la_dev for frames and mixture that arrive over time, B mixtures of K sources side by
  * side, the state of the iteration (per source the overlap-add ring, the windowed inverse frames and the magnitudes of the look_ahead
@@ -325,6 +359,12 @@ int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, const float *y_
 typedef struct lws_misi_stream lws_misi_stream;
 int lws_misi_stream_create(int device, int B, int K, int N, int fshift, const double *awin, const double *swin, int perfectrec,
                            int iters, int look_ahead, lws_misi_stream **out);
+/* ... with a start, LWS_START_GIVEN or LWS_START_MIXTURE, for the life of the stream: the stream then computes
+ * lws_amd.misi_la(..., start='mixture', open_end=True); it holds every mixture sample under a pushed frame, so nothing more is
+ * passed.  Under LWS_START_MIXTURE push takes magnitudes alone: S_dev may be NULL where A_dev is given (and is read for |S| only
+ * where it is not); with iters == 0 the rows returned are the entry estimates.  push, finish and destroy are the same functions. */
+int lws_misi_stream_create_ex(int device, int B, int K, int N, int fshift, const double *awin, const double *swin, int perfectrec,
+                              int iters, int look_ahead, int start, lws_misi_stream **out);
 int lws_misi_stream_push(lws_misi_stream *h, const void *S_dev, const float *A_dev, const float *y_dev, int frames, int samples,
                          void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out, void *stream);
 int lws_misi_stream_finish(lws_misi_stream *h, void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out, void *stream);

@@ -24,6 +24,8 @@ LWS_PRECISION_FP32, LWS_PRECISION_FP64, LWS_NOFUTURE_Q4_COMPAT, LWS_FORCE_GENERI
 LWS_STORAGE_FP16 = 16
 LWS_GENERIC_PLAIN_LAYOUT = 32
 LWS_W, LWS_W_AI, LWS_W_AF = 0, 1, 2
+LWS_START_GIVEN, LWS_START_OVERLAP, LWS_START_MIXTURE = 0, 1, 2
+STARTS = {"given": LWS_START_GIVEN, "overlap": LWS_START_OVERLAP, "mixture": LWS_START_MIXTURE}
 
 EXPORTS = (
     "lws_hip_version", "lws_last_error", "lws_device_count", "lws_plan_create", "lws_plan_destroy",
@@ -31,6 +33,7 @@ EXPORTS = (
     "lws_nofuture_lws_dev", "lws_online_lws_dev", "lws_residual_dev", "lws_last_kernel_time",
     "lws_last_kernel_name", "lws_generic_stage", "lws_stft_frames", "lws_istft_length", "lws_stft_dev", "lws_istft_dev", "lws_stft_zp_dev",
     "lws_consistency_dev", "lws_griffin_lim_dev", "lws_misi_dev", "lws_rtisi_la_dev", "lws_misi_la_dev",
+    "lws_rtisi_la_dev_ex", "lws_misi_la_dev_ex", "lws_rtisi_stream_create_ex", "lws_misi_stream_create_ex",
     "lws_rtisi_stream_create", "lws_rtisi_stream_push", "lws_rtisi_stream_finish", "lws_rtisi_stream_destroy", "lws_rtisi_la_placement",
     "lws_misi_stream_create", "lws_misi_stream_push", "lws_misi_stream_finish", "lws_misi_stream_destroy", "lws_hann", "lws_synthwin", "lws_weights_shape", "lws_create_weights",
     "lws_build_asymmetric_windows", "lws_get_thresholds", "lws_plan_create_from_windows", "lws_stream_copy",
@@ -108,6 +111,10 @@ def load():
     lib.lws_misi_dev.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, vp, vp, vp]
     lib.lws_rtisi_la_dev.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, vp, vp, ip, ip, ip, vp]
     lib.lws_misi_la_dev.argtypes = [ip, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, ip, vp]
+    lib.lws_rtisi_la_dev_ex.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, vp, vp, ip, ip, ip, ip, vp]
+    lib.lws_misi_la_dev_ex.argtypes = [ip, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, ip, ip, vp]
+    lib.lws_rtisi_stream_create_ex.argtypes = [ip, ip, ip, ip, vp, vp, ip, ip, ip, ip, C.POINTER(vp)]
+    lib.lws_misi_stream_create_ex.argtypes = [ip, ip, ip, ip, ip, vp, vp, ip, ip, ip, ip, C.POINTER(vp)]
     lib.lws_rtisi_stream_create.argtypes = [ip, ip, ip, ip, vp, vp, ip, ip, ip, C.POINTER(vp)]
     lib.lws_rtisi_stream_push.argtypes = [vp, vp, vp, ip, vp, vp, C.POINTER(ip), C.POINTER(ip), vp]
     lib.lws_rtisi_stream_finish.argtypes = [vp, vp, vp, C.POINTER(ip), C.POINTER(ip), vp]
@@ -507,36 +514,61 @@ def misi_dev(C_ptr, A_ptr, y_ptr, B, K, frames, fsize, fshift, awin, swin, perfe
     return trace
 
 
-def rtisi_la_dev(C_ptr, A_ptr, x_ptr, B, frames, fsize, fshift, awin, swin, perfectrec, iterations, look_ahead, device=0, stream=None):
+def start_code(start, allowed):
+    """The LWS_START_* of a start given by name; ValueError for one that is unknown or not among `allowed`."""
+    if start not in allowed:
+        raise ValueError("start must be one of %s, got %r" % (", ".join(repr(s) for s in allowed), start))
+    return STARTS[start]
+
+
+def rtisi_la_dev(C_ptr, A_ptr, x_ptr, B, frames, fsize, fshift, awin, swin, perfectrec, iterations, look_ahead, device=0, stream=None,
+                 start="given"):
     """RTISI-LA in place on C_ptr (device complex64 [B][frames][fsize//2+1]); A_ptr: device float32 target magnitudes or None
-    (|C| on entry); x_ptr: None or device float32 [B][istft_length(...)] for the signals.  Only enqueues."""
+    (|C| on entry); x_ptr: None or device float32 [B][istft_length(...)] for the signals.  start: 'given' or 'overlap'.  Only
+    enqueues."""
+    code = start_code(start, ("given", "overlap"))
     a, w = _win(awin), _win(swin)
     if a.shape != (int(fsize),) or w.shape != (int(fsize),):
         raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
-    check(load().lws_rtisi_la_dev(int(device), C_ptr, A_ptr, x_ptr, int(B), int(frames), int(fsize), int(fshift), a.ctypes.data,
-                                  w.ctypes.data, int(bool(perfectrec)), int(iterations), int(look_ahead), stream))
+    if code == LWS_START_GIVEN:
+        check(load().lws_rtisi_la_dev(int(device), C_ptr, A_ptr, x_ptr, int(B), int(frames), int(fsize), int(fshift), a.ctypes.data,
+                                      w.ctypes.data, int(bool(perfectrec)), int(iterations), int(look_ahead), stream))
+    else:
+        check(load().lws_rtisi_la_dev_ex(int(device), C_ptr, A_ptr, x_ptr, int(B), int(frames), int(fsize), int(fshift), a.ctypes.data,
+                                         w.ctypes.data, int(bool(perfectrec)), int(iterations), int(look_ahead), code, stream))
 
 
 def misi_la_dev(C_ptr, A_ptr, y_ptr, x_ptr, B, K, frames, fsize, fshift, awin, swin, perfectrec, iterations, look_ahead, device=0,
-                stream=None):
+                stream=None, start="given"):
     """Online MISI in place on C_ptr (device complex64 [B][K][frames][fsize//2+1]); A_ptr: device float32 target magnitudes or None
     (|C| on entry); y_ptr: device float32 mixtures [B][istft_length(...)]; x_ptr: None or device float32 [B][K][length] for the
-    signals.  Only enqueues."""
+    signals.  start: 'given' or 'mixture'.  Only enqueues."""
+    code = start_code(start, ("given", "mixture"))
     a, w = _win(awin), _win(swin)
     if a.shape != (int(fsize),) or w.shape != (int(fsize),):
         raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
-    check(load().lws_misi_la_dev(int(device), C_ptr, A_ptr, y_ptr, x_ptr, int(B), int(K), int(frames), int(fsize), int(fshift),
-                                 a.ctypes.data, w.ctypes.data, int(bool(perfectrec)), int(iterations), int(look_ahead), stream))
+    if code == LWS_START_GIVEN:
+        check(load().lws_misi_la_dev(int(device), C_ptr, A_ptr, y_ptr, x_ptr, int(B), int(K), int(frames), int(fsize), int(fshift),
+                                     a.ctypes.data, w.ctypes.data, int(bool(perfectrec)), int(iterations), int(look_ahead), stream))
+    else:
+        check(load().lws_misi_la_dev_ex(int(device), C_ptr, A_ptr, y_ptr, x_ptr, int(B), int(K), int(frames), int(fsize), int(fshift),
+                                        a.ctypes.data, w.ctypes.data, int(bool(perfectrec)), int(iterations), int(look_ahead), code,
+                                        stream))
 
 
-def rtisi_stream_create(B, fsize, fshift, awin, swin, perfectrec, iterations, look_ahead, device=0):
-    """A handle (c_void_p) for B RTISI-LA streams; free it with rtisi_stream_destroy."""
+def rtisi_stream_create(B, fsize, fshift, awin, swin, perfectrec, iterations, look_ahead, device=0, start="given"):
+    """A handle (c_void_p) for B RTISI-LA streams; free it with rtisi_stream_destroy.  start: 'given' or 'overlap'."""
+    code = start_code(start, ("given", "overlap"))
     a, w = _win(awin), _win(swin)
     if a.shape != (int(fsize),) or w.shape != (int(fsize),):
         raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
     h = C.c_void_p()
-    check(load().lws_rtisi_stream_create(int(device), int(B), int(fsize), int(fshift), a.ctypes.data, w.ctypes.data,
-                                         int(bool(perfectrec)), int(iterations), int(look_ahead), C.byref(h)))
+    if code == LWS_START_GIVEN:
+        check(load().lws_rtisi_stream_create(int(device), int(B), int(fsize), int(fshift), a.ctypes.data, w.ctypes.data,
+                                             int(bool(perfectrec)), int(iterations), int(look_ahead), C.byref(h)))
+    else:
+        check(load().lws_rtisi_stream_create_ex(int(device), int(B), int(fsize), int(fshift), a.ctypes.data, w.ctypes.data,
+                                                int(bool(perfectrec)), int(iterations), int(look_ahead), code, C.byref(h)))
     return h
 
 
@@ -559,14 +591,20 @@ def rtisi_stream_destroy(h):
     load().lws_rtisi_stream_destroy(h)
 
 
-def misi_stream_create(B, K, fsize, fshift, awin, swin, perfectrec, iterations, look_ahead, device=0):
-    """A handle (c_void_p) for B online-MISI streams of K sources each; free it with misi_stream_destroy."""
+def misi_stream_create(B, K, fsize, fshift, awin, swin, perfectrec, iterations, look_ahead, device=0, start="given"):
+    """A handle (c_void_p) for B online-MISI streams of K sources each; free it with misi_stream_destroy.  start: 'given' or
+    'mixture'."""
+    code = start_code(start, ("given", "mixture"))
     a, w = _win(awin), _win(swin)
     if a.shape != (int(fsize),) or w.shape != (int(fsize),):
         raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
     h = C.c_void_p()
-    check(load().lws_misi_stream_create(int(device), int(B), int(K), int(fsize), int(fshift), a.ctypes.data, w.ctypes.data,
-                                        int(bool(perfectrec)), int(iterations), int(look_ahead), C.byref(h)))
+    if code == LWS_START_GIVEN:
+        check(load().lws_misi_stream_create(int(device), int(B), int(K), int(fsize), int(fshift), a.ctypes.data, w.ctypes.data,
+                                            int(bool(perfectrec)), int(iterations), int(look_ahead), C.byref(h)))
+    else:
+        check(load().lws_misi_stream_create_ex(int(device), int(B), int(K), int(fsize), int(fshift), a.ctypes.data, w.ctypes.data,
+                                               int(bool(perfectrec)), int(iterations), int(look_ahead), code, C.byref(h)))
     return h
 
 

@@ -294,6 +294,27 @@ def lws_rtisi_la_dev(int device, C_dev, A_dev, x_dev, int B, int M, int N, int f
     return rc
 
 
+def lws_rtisi_la_dev_ex(int device, C_dev, A_dev, x_dev, int B, int M, int N, int fshift, awin, swin, int perfectrec, int iters,
+                        int look_ahead, int start, stream):
+    cdef uintptr_t cd = _addr(C_dev), ad = _addr(A_dev), xd = _addr(x_dev), a = _addr(awin), w = _addr(swin), st = _addr(stream)
+    cdef int rc
+    with nogil:
+        rc = c.lws_rtisi_la_dev_ex(device, <void *>cd, <const float *>ad, <float *>xd, B, M, N, fshift, <const double *>a,
+                                   <const double *>w, perfectrec, iters, look_ahead, start, <void *>st)
+    return rc
+
+
+def lws_misi_la_dev_ex(int device, C_dev, A_dev, y_dev, x_dev, int B, int K, int M, int N, int fshift, awin, swin, int perfectrec,
+                       int iters, int look_ahead, int start, stream):
+    cdef uintptr_t cd = _addr(C_dev), ad = _addr(A_dev), yd = _addr(y_dev), xd = _addr(x_dev), a = _addr(awin), w = _addr(swin)
+    cdef uintptr_t st = _addr(stream)
+    cdef int rc
+    with nogil:
+        rc = c.lws_misi_la_dev_ex(device, <void *>cd, <const float *>ad, <const float *>yd, <float *>xd, B, K, M, N, fshift,
+                                  <const double *>a, <const double *>w, perfectrec, iters, look_ahead, start, <void *>st)
+    return rc
+
+
 def lws_misi_la_dev(int device, C_dev, A_dev, y_dev, x_dev, int B, int K, int M, int N, int fshift, awin, swin, int perfectrec,
                     int iters, int look_ahead, stream):
     cdef uintptr_t cd = _addr(C_dev), ad = _addr(A_dev), yd = _addr(y_dev), xd = _addr(x_dev), a = _addr(awin), w = _addr(swin)
@@ -311,6 +332,18 @@ def lws_rtisi_stream_create(int device, int B, int N, int fshift, awin, swin, in
     cdef int rc
     with nogil:
         rc = c.lws_rtisi_stream_create(device, B, N, fshift, <const double *>a, <const double *>w, perfectrec, iters, look_ahead, &h)
+    out_ref._obj.value = <uintptr_t>h if h != NULL else None
+    return rc
+
+
+def lws_rtisi_stream_create_ex(int device, int B, int N, int fshift, awin, swin, int perfectrec, int iters, int look_ahead, int start,
+                               out_ref):
+    cdef c.lws_rtisi_stream *h = NULL
+    cdef uintptr_t a = _addr(awin), w = _addr(swin)
+    cdef int rc
+    with nogil:
+        rc = c.lws_rtisi_stream_create_ex(device, B, N, fshift, <const double *>a, <const double *>w, perfectrec, iters, look_ahead,
+                                          start, &h)
     out_ref._obj.value = <uintptr_t>h if h != NULL else None
     return rc
 
@@ -346,6 +379,18 @@ def lws_misi_stream_create(int device, int B, int K, int N, int fshift, awin, sw
     cdef int rc
     with nogil:
         rc = c.lws_misi_stream_create(device, B, K, N, fshift, <const double *>a, <const double *>w, perfectrec, iters, look_ahead, &h)
+    out_ref._obj.value = <uintptr_t>h if h != NULL else None
+    return rc
+
+
+def lws_misi_stream_create_ex(int device, int B, int K, int N, int fshift, awin, swin, int perfectrec, int iters, int look_ahead,
+                              int start, out_ref):
+    cdef c.lws_misi_stream *h = NULL
+    cdef uintptr_t a = _addr(awin), w = _addr(swin)
+    cdef int rc
+    with nogil:
+        rc = c.lws_misi_stream_create_ex(device, B, K, N, fshift, <const double *>a, <const double *>w, perfectrec, iters, look_ahead,
+                                         start, &h)
     out_ref._obj.value = <uintptr_t>h if h != NULL else None
     return rc
 

@@ -270,7 +270,12 @@ __device__ __forceinline__ float2 rtisi_project(float2 X, float a) {
     return mag > 0.f ? make_float2(a * (X.x / mag), a * (X.y / mag)) : make_float2(a, 0.f);
 }
 
-template <bool IN_LDS>
+// START (lws_hip.h's LWS_START_*) is how a frame enters in pass 0.  GIVEN: f_j = inv(S_j), two frames per transform.  OVERLAP (RTISI's
+// own initial estimate): c_j = A_j X / |X| with X = fwd of the partial sum keep (done + f_m + .. + f_{j-1}) under frame j, then
+// f_j = inv(c_j) -- the forward load, projection and inverse of a later pass with last = j - 1, one frame per transform (imaginary
+// half zero), since the load of frame j + 1 reads f_j.  S is not read; without iterations c_j goes where S_j was.  A template
+// parameter, so that the GIVEN instances are the code they were: both kernels sit at the SGPR limit (see the transform call).
+template <bool IN_LDS, int START>
 __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi(float2 *C, const float *A, float *xout, const float *awin, const float *swin,
                                                         float *scratch, RtisiArgs a) {
     extern __shared__ float2 lds[];
@@ -280,35 +285,37 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi(float2 *C, const fl
     float *state = IN_LDS ? reinterpret_cast<float *>(lds + (a.odd > 1 ? 3 : 2) * N) : scratch + (size_t)b * a.state_floats;
     float *ring = state, *fcur = state + R, *fnxt = fcur + (size_t)W * N;
     float2 *Cb = C + (size_t)b * M * F;
-    const float *Ab = A ? A + (size_t)b * M * F : nullptr;   // null without iterations, and not read then
+    const float *Ab = A ? A + (size_t)b * M * F : nullptr;   // null without iterations under GIVEN, and not read then
     float *xb = xout ? xout + (size_t)b * a.len : nullptr;
     for (int i = threadIdx.x; i < R; i += blockDim.x) ring[i] = 0.f;
     __syncthreads();
     int base = 0, slot_m = 0;   // slot_m: the slot of frame m
     for (int m = 0; m < M; ++m) {
         const int last = m + a.LA < M - 1 ? m + a.LA : M - 1;
-        // pass 0: the frames that have not entered, f_j = inv(S_j) (LA + 1 frames at m = 0, one per step after that), into fcur;
-        // passes 1 .. iters: the active frames, from fcur into fnxt
+        // pass 0: the frames that have not entered, f_j = inv(S_j) or inv of the entry estimate (LA + 1 frames at m = 0, one per step
+        // after that), into fcur; passes 1 .. iters: the active frames, from fcur into fnxt
         for (int it = 0; it <= a.iters; ++it) {
             float *dst = it == 0 ? fcur : fnxt;
+            const bool entry = START == LWS_START_OVERLAP && it == 0;   // frames enter one by one, through the projection
             // pass 0 starts at frame 0 (slot 0) in the first step and at frame m + LA after that: the slot before slot_m, cyclically
             const int j0 = it > 0 ? m : m == 0 ? 0 : m + a.LA;
             int slot = it > 0 || m == 0 ? slot_m : slot_m == 0 ? a.LA : slot_m - 1;   // of frame j: j mod (LA + 1), counted, not divided
-            for (int j = j0; j <= last; j += 2) {
-                const bool two = j + 1 <= last;
+            for (int j = j0; j <= last; j += entry ? 1 : 2) {
+                const bool two = !entry && j + 1 <= last;
+                const int upto = entry ? j - 1 : last;   // the frames in the sum the forward load gathers
                 // one transform call for both directions (ph 0: forward, not in pass 0; ph 1: inverse): its uniform state once
                 float2 *r = bufB;
 #pragma nounroll
-                for (int ph = it == 0 ? 1 : 0; ph < 2; ++ph) {
+                for (int ph = it == 0 && !entry ? 1 : 0; ph < 2; ++ph) {
                     float2 *x = bufA, *y = bufB;
                     if (ph == 0) {
                         for (int n = threadIdx.x; n < N; n += blockDim.x) {
                             const float w = awin[n];
-                            const float re = rtisi_sample(ring, fcur, j * hop + n, m, last, slot_m, base, R, t_end, a) * w;
-                            const float im = two ? rtisi_sample(ring, fcur, (j + 1) * hop + n, m, last, slot_m, base, R, t_end, a) * w : 0.f;
+                            const float re = rtisi_sample(ring, fcur, j * hop + n, m, upto, slot_m, base, R, t_end, a) * w;
+                            const float im = two ? rtisi_sample(ring, fcur, (j + 1) * hop + n, m, upto, slot_m, base, R, t_end, a) * w : 0.f;
                             x[n] = make_float2(re, im);
                         }
-                    } else if (it == 0) {
+                    } else if (it == 0 && !entry) {
                         const float2 *r0 = Cb + (size_t)j * F, *r1 = r0 + F;
                         for (int k = threadIdx.x; k < F; k += blockDim.x)
                             rtisi_put_pair(x, k, N, r0[k], two ? r1[k] : make_float2(0.f, 0.f));
@@ -318,14 +325,15 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi(float2 *C, const fl
                         // table bufB)
                         x = r == bufB ? bufA : (a.odd > 1 ? bufC : bufB);
                         y = r;
-                        const bool commit = it == a.iters && j == m;
+                        // an entry row is the result only where nothing iterates on it
+                        const bool commit = entry ? a.iters == 0 : it == a.iters && j == m;
                         const float *A0 = Ab + (size_t)j * F, *A1 = A0 + F;
                         for (int k = threadIdx.x; k < F; k += blockDim.x) {
                             const float2 zk = r[k], zn = r[k == 0 ? 0 : N - k];
                             const float2 u = rtisi_project(make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)), A0[k]);
                             float2 v = make_float2(0.f, 0.f);
                             if (two) v = rtisi_project(make_float2(0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)), A1[k]);
-                            if (commit) Cb[(size_t)m * F + k] = u;
+                            if (commit) Cb[(size_t)(entry ? j : m) * F + k] = u;
                             rtisi_put_pair(x, k, N, u, v);
                         }
                     }
@@ -334,7 +342,7 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi(float2 *C, const fl
                     // values the compiler cannot see through: hoisted over all five loops they cost more SGPRs than a wave has
                     int n_ = N, odd_ = a.odd, log2e_ = a.log2e;
                     asm volatile("" : "+s"(n_), "+s"(odd_), "+s"(log2e_));
-                    r = fft_lds<1>(x, y, n_, odd_, log2e_, ph == 0 ? -1.0f : 1.0f);
+                    r = fft_lds<START == LWS_START_GIVEN ? 1 : 5>(x, y, n_, odd_, log2e_, ph == 0 ? -1.0f : 1.0f);
                 }
                 // times the synthesis window, into the slots of frames j and j + 1
                 const float inv = 1.0f / (float)N;
@@ -345,7 +353,7 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi(float2 *C, const fl
                     if (two) o1[n] = r[n].y * w;
                 }
                 __syncthreads();   // r is the next load's buffer, dst the next reader's
-                slot += 2;
+                slot += entry ? 1 : 2;
                 if (slot > a.LA) slot -= W;
                 if (slot > a.LA) slot -= W;   // W == 1
             }
@@ -390,7 +398,22 @@ struct MisiLaArgs {
     size_t all_floats;   // K r.state_floats + (K + 1) R: the scratch slice of a workgroup
 };
 
-template <bool IN_LDS>
+// The bins k = threadIdx.x + i blockDim.x of one frame that a thread holds in registers: F <= blockDim.x up to N = 1024, and
+// blockDim.x = RTISI_MAX_THREADS above (rtisi_plan)
+constexpr int RTISI_BINS = (MAXN / 2 + 1 + RTISI_MAX_THREADS - 1) / RTISI_MAX_THREADS;
+
+// the unit phasor rtisi_project scales: (1, 0) where X == 0
+__device__ __forceinline__ float2 rtisi_phasor(float2 X) {
+    const float mag = sqrtf(X.x * X.x + X.y * X.y);
+    return mag > 0.f ? make_float2(X.x / mag, X.y / mag) : make_float2(1.f, 0.f);
+}
+
+// START (lws_hip.h's LWS_START_*) is how a frame enters in pass 0.  GIVEN: f_kj = inv(S_kj), two frames per transform, source by
+// source.  MIXTURE: c_kj = A_kj X / |X| with X = fwd(keep y under frame j), ONE forward transform per entering frame for all K
+// sources -- its phasors X / |X| wait in registers (RTISI_BINS bins per thread) while the K inverse transforms take the transform
+// buffers -- then f_kj = inv(c_kj), one frame per transform.  S is not read; without iterations c_kj goes where S_kj was.  A template
+// parameter with a block of its own, so that the GIVEN instances are the code they were.
+template <bool IN_LDS, int START>
 __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_misi_la(float2 *C, const float *A, const float *Y, float *xout, const float *awin,
                                                                const float *swin, float *scratch, MisiLaArgs q) {
     extern __shared__ float2 lds[];
@@ -428,9 +451,64 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_misi_la(float2 *C, const 
             }
             target[d] = v;
         }
+        if (START == LWS_START_MIXTURE) {   // pass 0, in front of the passes
+            int slot = m == 0 ? slot_m : slot_m == 0 ? a.LA : slot_m - 1;
+            for (int j = m == 0 ? 0 : m + a.LA; j <= last; ++j) {
+                float2 P[RTISI_BINS];   // X / |X| of frame j
+                float2 *r = bufB;
+                // one transform call: ph 0 forward, the mixture under frame j; ph 1 + k inverse, source k
+#pragma nounroll
+                for (int ph = 0; ph <= K; ++ph) {
+                    float2 *x = bufA, *y = bufB;
+                    if (ph == 0) {
+                        for (int n = threadIdx.x; n < N; n += blockDim.x) {
+                            const int t = j * hop + n, i = t - a.zero_lo;
+                            const float v = t >= a.zero_lo && t < t_end && i < a.len ? yb[i] : 0.f;
+                            x[n] = make_float2(v * awin[n], 0.f);
+                        }
+                    } else {
+                        if (ph == 1) {   // the forward result is read here and not again: the later inverses take bufA, bufB
+                            x = r == bufB ? bufA : (a.odd > 1 ? bufC : bufB);   // the buffers: as in k_rtisi
+                            y = r;
+#pragma unroll
+                            for (int c = 0; c < RTISI_BINS; ++c) {
+                                const int i = threadIdx.x + c * blockDim.x;
+                                if (i < F) {
+                                    const float2 zk = r[i], zn = r[i == 0 ? 0 : N - i];
+                                    P[c] = rtisi_phasor(make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)));
+                                }
+                            }
+                        }
+                        const float *Ak = Ab + ((size_t)(ph - 1) * M + j) * F;
+                        float2 *Ck = Cb + ((size_t)(ph - 1) * M + j) * F;
+#pragma unroll
+                        for (int c = 0; c < RTISI_BINS; ++c) {
+                            const int i = threadIdx.x + c * blockDim.x;
+                            if (i < F) {
+                                const float mag = Ak[i];
+                                const float2 u = make_float2(mag * P[c].x, mag * P[c].y);
+                                if (a.iters == 0) Ck[i] = u;   // an entry row is the result only where nothing iterates on it
+                                rtisi_put_pair(x, i, N, u, make_float2(0.f, 0.f));
+                            }
+                        }
+                    }
+                    __syncthreads();
+                    int n_ = N, odd_ = a.odd, log2e_ = a.log2e;   // derived at the call: see k_rtisi.  An instance of its own, as in the passes
+                    asm volatile("" : "+s"(n_), "+s"(odd_), "+s"(log2e_));
+                    r = fft_lds<7>(x, y, n_, odd_, log2e_, ph == 0 ? -1.0f : 1.0f);
+                    if (ph > 0) {
+                        const float inv = 1.0f / (float)N;
+                        float *o0 = state + (size_t)(ph - 1) * a.state_floats + cur + (size_t)slot * N;
+                        for (int n = threadIdx.x; n < N; n += blockDim.x) o0[n] = r[n].x * (inv * swin[n]);
+                        __syncthreads();   // r is the next load's buffer
+                    }
+                }
+                if (++slot > a.LA) slot = 0;
+            }
+        }
         // pass 0: the frames that have not entered, f_kj = inv(S_kj), into fcur_k; passes 1 .. iters: the active frames of every source,
         // from xs into fnxt_k
-        for (int it = 0; it <= a.iters; ++it) {
+        for (int it = START == LWS_START_MIXTURE ? 1 : 0; it <= a.iters; ++it) {
             if (it > 0) {
                 for (int d = threadIdx.x; d < R; d += blockDim.x) {
                     const int t = hop * m + d;
@@ -566,7 +644,10 @@ template <class T> __device__ __forceinline__ const T *rtisi_row(const T *held, 
     return j < nheld ? held + (size_t)j * F : chunk + (size_t)(j - nheld) * F;
 }
 
-template <bool IN_LDS>
+// START: as in k_rtisi.  Under OVERLAP the handle holds no start rows; without iterations the entry row of frame j is the row the
+// stream returns, so it goes to Cout where this launch commits frame j (j < nsteps) and into the next held rows (S_next) otherwise,
+// and so do, before the first step, the rows held from earlier launches.
+template <bool IN_LDS, int START>
 __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi_stream(const float2 *S, const float *A, float2 *Cout, float *xout,
                                                                     const float *awin, const float *swin, float *state, RtisiHeld h,
                                                                     RtisiStreamArgs q) {
@@ -587,6 +668,15 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi_stream(const float2
     }
     // where the rows of this stream start (offsets and, for the frame buffers, indices: pointers held across the loops cost SGPR pairs)
     const size_t held_at = (size_t)b * q.held_rows * F, chunk_at = (size_t)b * q.chunk_rows * F;
+    if (START != LWS_START_GIVEN && q.iters == 0 && !q.origin) {
+        // the entry rows of the frames that entered in earlier launches go where those of this launch go at entry, here at the start
+        // so that nothing of it is carried over the loops
+        for (int j = 0; j < q.nheld; ++j) {
+            const float2 *src = h.S + held_at + (size_t)j * F;
+            float2 *to = j < q.nsteps ? Cout + ((size_t)b * q.out_rows + j) * F : h.S_next + held_at + (size_t)(j - q.nsteps) * F;
+            for (int k = threadIdx.x; k < F; k += blockDim.x) to[k] = src[k];
+        }
+    }
     __syncthreads();
     int base = q.base, slot_m = q.slot_m;   // slot_m: the slot of frame m
     for (int m = 0; m < q.nsteps; ++m) {
@@ -595,22 +685,24 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi_stream(const float2
         for (int it = 0; it <= q.iters; ++it) {
             const float *fcur = ls + cur;
             float *dst = ls + (it == 0 ? cur : nxt);
+            const bool entry = START == LWS_START_OVERLAP && it == 0;   // as in k_rtisi
             const int j0 = it > 0 ? m : origin ? 0 : m + q.LA;
             int slot = it > 0 || origin ? slot_m : slot_m == 0 ? q.LA : slot_m - 1;
-            for (int j = j0; j <= last; j += 2) {
-                const bool two = j + 1 <= last;
+            for (int j = j0; j <= last; j += entry ? 1 : 2) {
+                const bool two = !entry && j + 1 <= last;
+                const int upto = entry ? j - 1 : last;
                 float2 *r = bufB;
 #pragma nounroll
-                for (int ph = it == 0 ? 1 : 0; ph < 2; ++ph) {
+                for (int ph = it == 0 && !entry ? 1 : 0; ph < 2; ++ph) {
                     float2 *x = bufA, *y = bufB;
                     if (ph == 0) {
                         for (int n = threadIdx.x; n < N; n += blockDim.x) {
                             const float w = awin[n];
-                            const float re = rtisi_sample(ring, fcur, j * hop + n, m, last, slot_m, base, R, no_end, a) * w;
-                            const float im = two ? rtisi_sample(ring, fcur, (j + 1) * hop + n, m, last, slot_m, base, R, no_end, a) * w : 0.f;
+                            const float re = rtisi_sample(ring, fcur, j * hop + n, m, upto, slot_m, base, R, no_end, a) * w;
+                            const float im = two ? rtisi_sample(ring, fcur, (j + 1) * hop + n, m, upto, slot_m, base, R, no_end, a) * w : 0.f;
                             x[n] = make_float2(re, im);
                         }
-                    } else if (it == 0) {
+                    } else if (it == 0 && !entry) {
                         const float2 *Sh = h.S + held_at, *Sc = S + chunk_at;
                         const float2 *r0 = rtisi_row(Sh, Sc, j, q.nheld, F), *r1 = two ? rtisi_row(Sh, Sc, j + 1, q.nheld, F) : r0;
                         for (int k = threadIdx.x; k < F; k += blockDim.x)
@@ -618,9 +710,14 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi_stream(const float2
                     } else {
                         x = r == bufB ? bufA : (q.odd > 1 ? bufC : bufB);   // the buffers: as in k_rtisi
                         y = r;
-                        const bool commit = it == q.iters && j == m;
+                        const bool commit = entry ? q.iters == 0 : it == q.iters && j == m;
                         const float *Ah = h.A + held_at, *Ac = A + chunk_at;
                         float2 *Co = Cout + (size_t)b * q.out_rows * F;
+                        if (entry) {   // row m of Co, written below, is the place of frame j (derived here: see the transform's uniforms)
+                            int row = j - q.nsteps;
+                            asm volatile("" : "+s"(row));
+                            Co = row < 0 ? Co + (size_t)(j - m) * F : h.S_next + held_at + (ptrdiff_t)(row - m) * F;
+                        }
                         const float *A0 = rtisi_row(Ah, Ac, j, q.nheld, F), *A1 = two ? rtisi_row(Ah, Ac, j + 1, q.nheld, F) : A0;
                         for (int k = threadIdx.x; k < F; k += blockDim.x) {
                             const float2 zk = r[k], zn = r[k == 0 ? 0 : N - k];
@@ -636,7 +733,7 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi_stream(const float2
                     // k_rtisi's and k_misi_la's stay what they were.
                     int n_ = N, odd_ = q.odd, log2e_ = q.log2e;
                     asm volatile("" : "+s"(n_), "+s"(odd_), "+s"(log2e_));
-                    r = fft_lds<3>(x, y, n_, odd_, log2e_, ph == 0 ? -1.0f : 1.0f);
+                    r = fft_lds<START == LWS_START_GIVEN ? 3 : 6>(x, y, n_, odd_, log2e_, ph == 0 ? -1.0f : 1.0f);
                 }
                 const float inv = 1.0f / (float)N;
                 float *o0 = dst + (size_t)slot * N, *o1 = dst + (size_t)(slot < q.LA ? slot + 1 : 0) * N;
@@ -646,13 +743,13 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi_stream(const float2
                     if (two) o1[n] = r[n].y * w;
                 }
                 __syncthreads();   // r is the next load's buffer, dst the next reader's
-                slot += 2;
+                slot += entry ? 1 : 2;
                 if (slot > q.LA) slot -= W;
                 if (slot > q.LA) slot -= W;   // W == 1
             }
             if (it > 0) { const int t = cur; cur = nxt; nxt = t; }
         }
-        if (q.iters == 0) {   // nothing was projected: the committed row is the start row
+        if (START == LWS_START_GIVEN && q.iters == 0) {   // nothing was projected: the committed row is the start row
             const float2 *r0 = rtisi_row(h.S + held_at, S + chunk_at, m, q.nheld, F);
             float2 *Co = Cout + (size_t)b * q.out_rows * F;
             for (int k = threadIdx.x; k < F; k += blockDim.x) Co[(size_t)m * F + k] = r0[k];
@@ -699,7 +796,7 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi_stream(const float2
             float *to = h.A_next + held_at + (size_t)i * F;
             for (int k = threadIdx.x; k < F; k += blockDim.x) to[k] = src[k];
         }
-        if (h.S_next) {
+        if (START == LWS_START_GIVEN && h.S_next) {
             const float2 *src = rtisi_row(Sh, Sc, q.nsteps + i, q.nheld, F);
             float2 *to = h.S_next + held_at + (size_t)i * F;
             for (int k = threadIdx.x; k < F; k += blockDim.x) to[k] = src[k];
@@ -743,7 +840,10 @@ __device__ __forceinline__ float misi_stream_y(const float *held, const float *c
     return i < ny_chunk ? chunk[i] : 0.f;
 }
 
-template <bool IN_LDS>
+// START: as in k_misi_la, the mixture under frame j read as the target reads it.  Under MIXTURE the handle holds no start rows;
+// without iterations the entry rows of frame j are the rows the stream returns, so they go to Cout where this launch commits frame j
+// (j < nsteps) and into the next held rows (S_next) otherwise, and so do, before the first step, the rows held from earlier launches.
+template <bool IN_LDS, int START>
 __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_misi_la_stream(const float2 *S, const float *A, const float *Y, float2 *Cout,
                                                                       float *xout, const float *awin, const float *swin, float *state,
                                                                       MisiStreamHeld h, MisiStreamArgs p) {
@@ -778,10 +878,22 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_misi_la_stream(const floa
                 float *to = h.A_next + held_at + (size_t)i * F;
                 for (int j = threadIdx.x; j < F; j += blockDim.x) to[j] = src[j];
             }
-            if (h.S_next) {
+            if (START == LWS_START_GIVEN && h.S_next) {
                 const float2 *src = rtisi_row(h.S + held_at, S + chunk_at, q.nsteps + i, q.nheld, F);
                 float2 *to = h.S_next + held_at + (size_t)i * F;
                 for (int j = threadIdx.x; j < F; j += blockDim.x) to[j] = src[j];
+            }
+        }
+    }
+    // ... the entry rows of the frames that entered in earlier launches, to where those of this launch go at entry ...
+    if (START != LWS_START_GIVEN && q.iters == 0 && !q.origin) {
+#pragma nounroll
+        for (int k = 0; k < K; ++k) {
+            const size_t held_at = ((size_t)b * K + k) * q.held_rows * F;
+            for (int j = 0; j < q.nheld; ++j) {
+                const float2 *src = h.S + held_at + (size_t)j * F;
+                float2 *to = j < q.nsteps ? Cout + (((size_t)b * K + k) * q.out_rows + j) * F : h.S_next + held_at + (size_t)(j - q.nsteps) * F;
+                for (int i = threadIdx.x; i < F; i += blockDim.x) to[i] = src[i];
             }
         }
     }
@@ -817,7 +929,65 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_misi_la_stream(const floa
             }
             ls[target_at + d] = v;
         }
-        for (int it = 0; it <= q.iters; ++it) {
+        if (START == LWS_START_MIXTURE) {   // pass 0 in front of the passes: k_misi_la's block, on the stream's rows and samples
+            int slot = origin ? slot_m : slot_m == 0 ? q.LA : slot_m - 1;
+            for (int j = origin ? 0 : m + q.LA; j <= last; ++j) {
+                float2 P[RTISI_BINS];
+                float2 *r = bufB;
+#pragma nounroll
+                for (int ph = 0; ph <= K; ++ph) {
+                    float2 *x = bufA, *y = bufB;
+                    if (ph == 0) {
+                        for (int n = threadIdx.x; n < N; n += blockDim.x) {
+                            const int t = j * hop + n;
+                            const float v = t >= q.zero_lo ? misi_stream_y(h.y + hy_at, Y + cy_at, t, p.ny_held, p.ny_chunk) : 0.f;
+                            x[n] = make_float2(v * awin[n], 0.f);
+                        }
+                    } else {
+                        if (ph == 1) {
+                            x = r == bufB ? bufA : (q.odd > 1 ? bufC : bufB);
+                            y = r;
+#pragma unroll
+                            for (int c = 0; c < RTISI_BINS; ++c) {
+                                const int i = threadIdx.x + c * blockDim.x;
+                                if (i < F) {
+                                    const float2 zk = r[i], zn = r[i == 0 ? 0 : N - i];
+                                    P[c] = rtisi_phasor(make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)));
+                                }
+                            }
+                        }
+                        int bk = b * K + ph - 1;   // where the rows of this source start, derived here: see the transform's uniforms
+                        asm volatile("" : "+s"(bk));
+                        const float *Ak = rtisi_row(h.A + (size_t)bk * q.held_rows * F, A + (size_t)bk * q.chunk_rows * F, j, q.nheld, F);
+                        int row = j - q.nsteps;
+                        asm volatile("" : "+s"(row));
+                        float2 *Co = row < 0 ? Cout + ((size_t)bk * q.out_rows + j) * F : h.S_next + ((size_t)bk * q.held_rows + row) * F;
+#pragma unroll
+                        for (int c = 0; c < RTISI_BINS; ++c) {
+                            const int i = threadIdx.x + c * blockDim.x;
+                            if (i < F) {
+                                const float mag = Ak[i];
+                                const float2 u = make_float2(mag * P[c].x, mag * P[c].y);
+                                if (q.iters == 0) Co[i] = u;
+                                rtisi_put_pair(x, i, N, u, make_float2(0.f, 0.f));
+                            }
+                        }
+                    }
+                    __syncthreads();
+                    int n_ = N, odd_ = q.odd, log2e_ = q.log2e;   // derived at the call: see k_rtisi.  An instance of its own, as in the passes
+                    asm volatile("" : "+s"(n_), "+s"(odd_), "+s"(log2e_));
+                    r = fft_lds<8>(x, y, n_, odd_, log2e_, ph == 0 ? -1.0f : 1.0f);
+                    if (ph > 0) {
+                        const float inv = 1.0f / (float)N;
+                        float *o0 = ls + (size_t)(ph - 1) * sstride + cur + slot * N;
+                        for (int n = threadIdx.x; n < N; n += blockDim.x) o0[n] = r[n].x * (inv * swin[n]);
+                        __syncthreads();   // r is the next load's buffer
+                    }
+                }
+                if (++slot > q.LA) slot = 0;
+            }
+        }
+        for (int it = START == LWS_START_MIXTURE ? 1 : 0; it <= q.iters; ++it) {
             if (it > 0) {
                 for (int d = threadIdx.x; d < R; d += blockDim.x) {
                     const int t = hop * m + d;
@@ -899,7 +1069,7 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_misi_la_stream(const floa
             }
             if (it > 0) { const int t = cur; cur = nxt; nxt = t; }
         }
-        if (q.iters == 0) {   // nothing was projected: the committed rows are the start rows
+        if (START == LWS_START_GIVEN && q.iters == 0) {   // nothing was projected: the committed rows are the start rows
 #pragma nounroll
             for (int k = 0; k < K; ++k) {
                 const float2 *r0 = rtisi_row(h.S + ((size_t)b * K + k) * q.held_rows * F, S + ((size_t)b * K + k) * q.chunk_rows * F, m,
@@ -1171,28 +1341,39 @@ RtisiPlan rtisi_plan(int N, int hop, int LA) {
 
 extern "C" int lws_rtisi_la_dev(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift,
                                 const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream) {
+    return lws_rtisi_la_dev_ex(device, C_dev, A_dev, x_dev, B, M, N, fshift, awin, swin, perfectrec, iters, look_ahead, LWS_START_GIVEN,
+                               stream);
+}
+
+extern "C" int lws_rtisi_la_dev_ex(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift,
+                                   const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, int start,
+                                   void *stream) {
     int rc = check_shape(device, B, M, N, fshift);
     if (rc) return rc;
+    if (start != LWS_START_GIVEN && start != LWS_START_OVERLAP) return lws::set_error(LWS_ERR_INVALID, "start %d for RTISI-LA", start);
+    const bool given = start == LWS_START_GIVEN;
     if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
     if (look_ahead < 0) return lws::set_error(LWS_ERR_INVALID, "look-ahead of %d frames", look_ahead);
     if (!C_dev || !awin || !swin) return lws::set_error(LWS_ERR_INVALID, "null pointer");
     if (iters > 0 && (rc = check_round_trip(M, N, fshift, perfectrec))) return rc;
     const int len = lws_istft_length(M, N, fshift, perfectrec);
-    if (B == 0 || (iters == 0 && (!x_dev || len < 1))) return LWS_OK;
+    if (B == 0 || (given && iters == 0 && (!x_dev || len < 1))) return LWS_OK;   // an entry estimate is a result without iterations too
     STFT_TRY(hipSetDevice(device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     std::lock_guard<std::mutex> lk(g_mu);
     GlaCtx &c = g_ctx[device];
     if ((rc = ctx_enter(c, s))) return rc;
-    STFT_TRY(lws::allow_dynamic_lds<&k_rtisi<true>>((int)RTISI_LDS_CAP));
-    STFT_TRY(lws::allow_dynamic_lds<&k_rtisi<false>>(3 * MAXN * (int)sizeof(float2)));
+    STFT_TRY((lws::allow_dynamic_lds<&k_rtisi<true, LWS_START_GIVEN>>((int)RTISI_LDS_CAP)));
+    STFT_TRY((lws::allow_dynamic_lds<&k_rtisi<false, LWS_START_GIVEN>>(3 * MAXN * (int)sizeof(float2))));
+    STFT_TRY((lws::allow_dynamic_lds<&k_rtisi<true, LWS_START_OVERLAP>>((int)RTISI_LDS_CAP)));
+    STFT_TRY((lws::allow_dynamic_lds<&k_rtisi<false, LWS_START_OVERLAP>>(3 * MAXN * (int)sizeof(float2))));
     if ((rc = upload_window(c.win_a, c.host_a, awin, N, s))) return rc;
     if ((rc = upload_window(c.win_s, c.host_s, swin, N, s))) return rc;
     const int F = N / 2 + 1, LA = look_ahead < M - 1 ? look_ahead : M - 1;   // no frame beyond M - 1 to look at
     const size_t bins = (size_t)B * M * F;
     const RtisiPlan p = rtisi_plan(N, fshift, LA);
     if (!p.in_lds && (rc = c.state.ensure((size_t)B * p.state_floats * sizeof(float)))) return rc;
-    if (!A_dev && iters > 0) {
+    if (!A_dev && (iters > 0 || !given)) {   // the entry projection reads A
         if ((rc = c.a.ensure(bins * sizeof(float)))) return rc;
         hipLaunchKernelGGL(k_gla_abs, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, s, static_cast<const float2 *>(C_dev),
                            static_cast<float *>(c.a.p), bins);
@@ -1203,12 +1384,10 @@ extern "C" int lws_rtisi_la_dev(int device, void *C_dev, const float *A_dev, flo
                       len, p.state_floats};
     float2 *C = static_cast<float2 *>(C_dev);
     const float *wa = static_cast<const float *>(c.win_a.p), *ws = static_cast<const float *>(c.win_s.p);
-    if (p.in_lds)
-        hipLaunchKernelGGL(k_rtisi<true>, dim3(B), dim3(p.threads), p.lds_bytes, s, C, A_dev, len < 1 ? nullptr : x_dev, wa, ws,
-                           static_cast<float *>(nullptr), a);
-    else
-        hipLaunchKernelGGL(k_rtisi<false>, dim3(B), dim3(p.threads), p.lds_bytes, s, C, A_dev, len < 1 ? nullptr : x_dev, wa, ws,
-                           static_cast<float *>(c.state.p), a);
+    float *x = len < 1 ? nullptr : x_dev, *scratch = p.in_lds ? nullptr : static_cast<float *>(c.state.p);
+    auto *kernel = p.in_lds ? (given ? k_rtisi<true, LWS_START_GIVEN> : k_rtisi<true, LWS_START_OVERLAP>)
+                            : (given ? k_rtisi<false, LWS_START_GIVEN> : k_rtisi<false, LWS_START_OVERLAP>);
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(p.threads), p.lds_bytes, s, C, A_dev, x, wa, ws, scratch, a);
     STFT_TRY(hipGetLastError());
     return ctx_leave(c, s);
 }
@@ -1257,8 +1436,17 @@ extern "C" int lws_rtisi_la_placement(int N, int fshift, int look_ahead, int K, 
 extern "C" int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, float *x_dev, int B, int K, int M, int N,
                                int fshift, const double *awin, const double *swin, int perfectrec, int iters, int look_ahead,
                                void *stream) {
+    return lws_misi_la_dev_ex(device, C_dev, A_dev, y_dev, x_dev, B, K, M, N, fshift, awin, swin, perfectrec, iters, look_ahead,
+                              LWS_START_GIVEN, stream);
+}
+
+extern "C" int lws_misi_la_dev_ex(int device, void *C_dev, const float *A_dev, const float *y_dev, float *x_dev, int B, int K, int M,
+                                  int N, int fshift, const double *awin, const double *swin, int perfectrec, int iters, int look_ahead,
+                                  int start, void *stream) {
     int rc = check_shape(device, B, M, N, fshift);
     if (rc) return rc;
+    if (start != LWS_START_GIVEN && start != LWS_START_MIXTURE) return lws::set_error(LWS_ERR_INVALID, "start %d for online MISI", start);
+    const bool given = start == LWS_START_GIVEN;
     if (K < 1) return lws::set_error(LWS_ERR_INVALID, "%d sources", K);
     if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
     if (look_ahead < 0) return lws::set_error(LWS_ERR_INVALID, "look-ahead of %d frames", look_ahead);
@@ -1266,21 +1454,23 @@ extern "C" int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, cons
     const int len = lws_istft_length(M, N, fshift, perfectrec);
     if (len < 1) return lws::set_error(LWS_ERR_INVALID, "%d frames leave no samples", M);
     if (iters > 0 && (rc = check_round_trip(M, N, fshift, perfectrec))) return rc;
-    if (B == 0 || (iters == 0 && !x_dev)) return LWS_OK;
+    if (B == 0 || (given && iters == 0 && !x_dev)) return LWS_OK;   // an entry estimate is a result without iterations too
     STFT_TRY(hipSetDevice(device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     std::lock_guard<std::mutex> lk(g_mu);
     GlaCtx &c = g_ctx[device];
     if ((rc = ctx_enter(c, s))) return rc;
-    STFT_TRY(lws::allow_dynamic_lds<&k_misi_la<true>>((int)RTISI_LDS_CAP));
-    STFT_TRY(lws::allow_dynamic_lds<&k_misi_la<false>>(3 * MAXN * (int)sizeof(float2)));
+    STFT_TRY((lws::allow_dynamic_lds<&k_misi_la<true, LWS_START_GIVEN>>((int)RTISI_LDS_CAP)));
+    STFT_TRY((lws::allow_dynamic_lds<&k_misi_la<false, LWS_START_GIVEN>>(3 * MAXN * (int)sizeof(float2))));
+    STFT_TRY((lws::allow_dynamic_lds<&k_misi_la<true, LWS_START_MIXTURE>>((int)RTISI_LDS_CAP)));
+    STFT_TRY((lws::allow_dynamic_lds<&k_misi_la<false, LWS_START_MIXTURE>>(3 * MAXN * (int)sizeof(float2))));
     if ((rc = upload_window(c.win_a, c.host_a, awin, N, s))) return rc;
     if ((rc = upload_window(c.win_s, c.host_s, swin, N, s))) return rc;
     const int F = N / 2 + 1, LA = look_ahead < M - 1 ? look_ahead : M - 1;   // no frame beyond M - 1 to look at
     const size_t bins = (size_t)B * K * M * F;
     const MisiLaPlan p = misi_la_plan(N, fshift, LA, K);
     if (!p.in_lds && (rc = c.state.ensure((size_t)B * p.all_floats * sizeof(float)))) return rc;
-    if (!A_dev && iters > 0) {
+    if (!A_dev && (iters > 0 || !given)) {   // the entry projection reads A
         if ((rc = c.a.ensure(bins * sizeof(float)))) return rc;
         hipLaunchKernelGGL(k_gla_abs, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, s, static_cast<const float2 *>(C_dev),
                            static_cast<float *>(c.a.p), bins);
@@ -1292,12 +1482,10 @@ extern "C" int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, cons
                        K, p.all_floats};
     float2 *C = static_cast<float2 *>(C_dev);
     const float *wa = static_cast<const float *>(c.win_a.p), *ws = static_cast<const float *>(c.win_s.p);
-    if (p.in_lds)
-        hipLaunchKernelGGL(k_misi_la<true>, dim3(B), dim3(p.threads), p.lds_bytes, s, C, A_dev, y_dev, x_dev, wa, ws,
-                           static_cast<float *>(nullptr), q);
-    else
-        hipLaunchKernelGGL(k_misi_la<false>, dim3(B), dim3(p.threads), p.lds_bytes, s, C, A_dev, y_dev, x_dev, wa, ws,
-                           static_cast<float *>(c.state.p), q);
+    float *scratch = p.in_lds ? nullptr : static_cast<float *>(c.state.p);
+    auto *kernel = p.in_lds ? (given ? k_misi_la<true, LWS_START_GIVEN> : k_misi_la<true, LWS_START_MIXTURE>)
+                            : (given ? k_misi_la<false, LWS_START_GIVEN> : k_misi_la<false, LWS_START_MIXTURE>);
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(p.threads), p.lds_bytes, s, C, A_dev, y_dev, x_dev, wa, ws, scratch, q);
     STFT_TRY(hipGetLastError());
     return ctx_leave(c, s);
 }
@@ -1305,7 +1493,7 @@ extern "C" int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, cons
 // ---- Streaming RTISI-LA: the handle.  Everything a stream carries between calls is its own -- state, held rows, windows, the
 // magnitudes of a chunk given without them -- so streams share nothing with each other or with the calls on GlaCtx.
 struct lws_rtisi_stream {
-    int device = 0, B = 0, N = 0, hop = 0, LA = 0, iters = 0, perfectrec = 0;
+    int device = 0, B = 0, N = 0, hop = 0, LA = 0, iters = 0, perfectrec = 0, start = LWS_START_GIVEN;
     RtisiPlan plan{};
     size_t state_floats = 0;              // per stream: ring, fcur and, with the scratch placement, the other frame buffer
     Scratch state, held_s[2], held_a[2], abuf, win_a, win_s;
@@ -1335,8 +1523,10 @@ int stream_leave(lws_rtisi_stream &h, hipStream_t s) {
 // rows [at, at + frames) of the held buffers from a chunk: the frames that arrive before the first commit can run
 int stream_stash(lws_rtisi_stream &h, const float2 *S, const float *A, int frames, hipStream_t s) {
     const size_t F = (size_t)h.N / 2 + 1, at = (size_t)h.entered;
-    STFT_TRY(hipMemcpy2DAsync(static_cast<float2 *>(h.held_s[h.held].p) + at * F, (size_t)h.LA * F * sizeof(float2), S,
-                              (size_t)frames * F * sizeof(float2), (size_t)frames * F * sizeof(float2), h.B, hipMemcpyDeviceToDevice, s));
+    if (h.start == LWS_START_GIVEN)   // no other start reads the rows
+        STFT_TRY(hipMemcpy2DAsync(static_cast<float2 *>(h.held_s[h.held].p) + at * F, (size_t)h.LA * F * sizeof(float2), S,
+                                  (size_t)frames * F * sizeof(float2), (size_t)frames * F * sizeof(float2), h.B, hipMemcpyDeviceToDevice,
+                                  s));
     if (A)
         STFT_TRY(hipMemcpy2DAsync(static_cast<float *>(h.held_a[h.held].p) + at * F, (size_t)h.LA * F * sizeof(float), A,
                                   (size_t)frames * F * sizeof(float), (size_t)frames * F * sizeof(float), h.B, hipMemcpyDeviceToDevice, s));
@@ -1365,15 +1555,15 @@ int stream_launch(lws_rtisi_stream &h, const float2 *S, const float *A, int fram
     q.chunk_rows = frames; q.out_rows = out_rows; q.out_samples = out_samples;
     q.state_floats = h.state_floats;
     const int nxt = h.held ^ 1;
+    const bool given = h.start == LWS_START_GIVEN;   // any other start projects at entry: it keeps the magnitudes without iterations too
     const RtisiHeld held{static_cast<const float2 *>(h.held_s[h.held].p), static_cast<const float *>(h.held_a[h.held].p),
                          closing || h.iters > 0 ? nullptr : static_cast<float2 *>(h.held_s[nxt].p),
-                         closing || h.iters == 0 ? nullptr : static_cast<float *>(h.held_a[nxt].p)};
+                         closing || (given && h.iters == 0) ? nullptr : static_cast<float *>(h.held_a[nxt].p)};
     const float *wa = static_cast<const float *>(h.win_a.p), *ws = static_cast<const float *>(h.win_s.p);
     float *st = static_cast<float *>(h.state.p);
-    if (p.in_lds)
-        hipLaunchKernelGGL(k_rtisi_stream<true>, dim3(h.B), dim3(p.threads), p.lds_bytes, s, S, A, C_out, x_out, wa, ws, st, held, q);
-    else
-        hipLaunchKernelGGL(k_rtisi_stream<false>, dim3(h.B), dim3(p.threads), p.lds_bytes, s, S, A, C_out, x_out, wa, ws, st, held, q);
+    auto *kernel = p.in_lds ? (given ? k_rtisi_stream<true, LWS_START_GIVEN> : k_rtisi_stream<true, LWS_START_OVERLAP>)
+                            : (given ? k_rtisi_stream<false, LWS_START_GIVEN> : k_rtisi_stream<false, LWS_START_OVERLAP>);
+    hipLaunchKernelGGL(kernel, dim3(h.B), dim3(p.threads), p.lds_bytes, s, S, A, C_out, x_out, wa, ws, st, held, q);
     STFT_TRY(hipGetLastError());
     const int R = h.N + LA * h.hop;
     h.base = (int)(((long long)h.base + (long long)h.hop * nsteps) % R);
@@ -1389,10 +1579,17 @@ int stream_launch(lws_rtisi_stream &h, const float2 *S, const float *A, int fram
 
 extern "C" int lws_rtisi_stream_create(int device, int B, int N, int fshift, const double *awin, const double *swin, int perfectrec,
                                        int iters, int look_ahead, lws_rtisi_stream **out) {
+    return lws_rtisi_stream_create_ex(device, B, N, fshift, awin, swin, perfectrec, iters, look_ahead, LWS_START_GIVEN, out);
+}
+
+extern "C" int lws_rtisi_stream_create_ex(int device, int B, int N, int fshift, const double *awin, const double *swin, int perfectrec,
+                                          int iters, int look_ahead, int start, lws_rtisi_stream **out) {
     if (!out) return lws::set_error(LWS_ERR_INVALID, "null pointer");
     *out = nullptr;
     int rc = check_shape(device, B, 1, N, fshift);
     if (rc) return rc;
+    if (start != LWS_START_GIVEN && start != LWS_START_OVERLAP) return lws::set_error(LWS_ERR_INVALID, "start %d for RTISI-LA", start);
+    const bool given = start == LWS_START_GIVEN;
     if (B < 1) return lws::set_error(LWS_ERR_INVALID, "%d streams", B);
     if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
     if (look_ahead < 0) return lws::set_error(LWS_ERR_INVALID, "look-ahead of %d frames", look_ahead);
@@ -1400,9 +1597,12 @@ extern "C" int lws_rtisi_stream_create(int device, int B, int N, int fshift, con
     if ((long long)(look_ahead + 2) * fshift + N > 0x7fffffffLL / 2)
         return lws::set_error(LWS_ERR_UNSUPPORTED, "look-ahead of %d frames", look_ahead);
     STFT_TRY(hipSetDevice(device));
-    STFT_TRY(lws::allow_dynamic_lds<&k_rtisi_stream<true>>((int)RTISI_LDS_CAP));
-    STFT_TRY(lws::allow_dynamic_lds<&k_rtisi_stream<false>>(3 * MAXN * (int)sizeof(float2)));
+    STFT_TRY((lws::allow_dynamic_lds<&k_rtisi_stream<true, LWS_START_GIVEN>>((int)RTISI_LDS_CAP)));
+    STFT_TRY((lws::allow_dynamic_lds<&k_rtisi_stream<false, LWS_START_GIVEN>>(3 * MAXN * (int)sizeof(float2))));
+    STFT_TRY((lws::allow_dynamic_lds<&k_rtisi_stream<true, LWS_START_OVERLAP>>((int)RTISI_LDS_CAP)));
+    STFT_TRY((lws::allow_dynamic_lds<&k_rtisi_stream<false, LWS_START_OVERLAP>>(3 * MAXN * (int)sizeof(float2))));
     lws_rtisi_stream *h = new lws_rtisi_stream;
+    h->start = start;
     h->device = device; h->B = B; h->N = N; h->hop = fshift; h->LA = look_ahead; h->iters = iters; h->perfectrec = perfectrec ? 1 : 0;
     h->plan = rtisi_plan(N, fshift, look_ahead);
     const size_t F = (size_t)N / 2 + 1, frame_floats = (size_t)(look_ahead + 1) * N;
@@ -1413,10 +1613,10 @@ extern "C" int lws_rtisi_stream_create(int device, int B, int N, int fshift, con
     rc = h->state.ensure(state_bytes);
     if (!rc) rc = h->win_a.ensure((size_t)N * sizeof(float));
     if (!rc) rc = h->win_s.ensure((size_t)N * sizeof(float));
-    if (!rc) rc = h->held_s[0].ensure(rows * sizeof(float2));
+    if (!rc && (given || iters == 0)) rc = h->held_s[0].ensure(rows * sizeof(float2));   // start rows, or entry rows to return
     if (!rc && iters == 0) rc = h->held_s[1].ensure(rows * sizeof(float2));
-    if (!rc && iters > 0) rc = h->held_a[0].ensure(rows * sizeof(float));
-    if (!rc && iters > 0) rc = h->held_a[1].ensure(rows * sizeof(float));
+    if (!rc && (iters > 0 || !given)) rc = h->held_a[0].ensure(rows * sizeof(float));
+    if (!rc && (iters > 0 || !given)) rc = h->held_a[1].ensure(rows * sizeof(float));
     hipError_t e = hipSuccess;
     if (!rc) e = hipEventCreateWithFlags(&h->last, hipEventDisableTiming);
     if (!rc && e == hipSuccess) e = hipMemset(h->state.p, 0, state_bytes);
@@ -1441,7 +1641,8 @@ extern "C" int lws_rtisi_stream_push(lws_rtisi_stream *h, const void *S_dev, con
     if (frames < 0) return lws::set_error(LWS_ERR_INVALID, "%d frames", frames);
     if (h->finished) return lws::set_error(LWS_ERR_INVALID, "push after finish");
     if (frames == 0) return LWS_OK;
-    if (!S_dev) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    const bool given = h->start == LWS_START_GIVEN;
+    if (!S_dev && (given || !A_dev)) return lws::set_error(LWS_ERR_INVALID, "null pointer");   // magnitudes alone serve any other start
     if (((long long)frames + h->LA + 2) * h->hop + h->N > 0x7fffffffLL)
         return lws::set_error(LWS_ERR_UNSUPPORTED, "%d frames in one push", frames);
     const long long entered = h->entered + frames;
@@ -1453,12 +1654,12 @@ extern "C" int lws_rtisi_stream_push(lws_rtisi_stream *h, const void *S_dev, con
     if (rc) return rc;
     const float2 *S = static_cast<const float2 *>(S_dev);
     const size_t bins = (size_t)h->B * frames * (h->N / 2 + 1);
-    if (!A_dev && h->iters > 0) {   // |S| by the kernel lws_rtisi_la_dev takes it from
+    if (!A_dev && (h->iters > 0 || !given)) {   // |S| by the kernel lws_rtisi_la_dev takes it from
         if ((rc = h->abuf.ensure(bins * sizeof(float)))) return rc;
         hipLaunchKernelGGL(k_gla_abs, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, s, S, static_cast<float *>(h->abuf.p), bins);
         A_dev = static_cast<const float *>(h->abuf.p);
     }
-    if (h->iters == 0) A_dev = nullptr;
+    if (given && h->iters == 0) A_dev = nullptr;
     if (nsteps == 0) {
         if ((rc = stream_stash(*h, S, A_dev, frames, s))) return rc;
     } else {
@@ -1517,7 +1718,7 @@ extern "C" void lws_rtisi_stream_destroy(lws_rtisi_stream *h) {
 // windows it owns the held mixture samples and, with the scratch placement, the room for target and xs -- nothing is shared with
 // other streams or with the calls on GlaCtx.
 struct lws_misi_stream {
-    int device = 0, B = 0, K = 0, N = 0, hop = 0, LA = 0, iters = 0, perfectrec = 0;
+    int device = 0, B = 0, K = 0, N = 0, hop = 0, LA = 0, iters = 0, perfectrec = 0, start = LWS_START_GIVEN;
     MisiLaPlan plan{};
     size_t source_floats = 0;             // per source: ring, fcur and, with the scratch placement, the other frame buffer
     size_t stream_floats = 0;             // per stream: K of those and, with the scratch placement, the (K + 1) R floats of target and xs
@@ -1556,8 +1757,10 @@ int misi_leave(lws_misi_stream &h, hipStream_t s) {
 int misi_stash(lws_misi_stream &h, const float2 *S, const float *A, const float *y, int frames, int samples, hipStream_t s) {
     const size_t F = (size_t)h.N / 2 + 1, at = (size_t)h.entered, BK = (size_t)h.B * h.K;
     const size_t y_at = (size_t)(h.perfectrec ? prepad(h.N, h.hop) : 0) + (size_t)misi_need(h, h.entered);
-    STFT_TRY(hipMemcpy2DAsync(static_cast<float2 *>(h.held_s[h.held].p) + at * F, (size_t)h.LA * F * sizeof(float2), S,
-                              (size_t)frames * F * sizeof(float2), (size_t)frames * F * sizeof(float2), BK, hipMemcpyDeviceToDevice, s));
+    if (h.start == LWS_START_GIVEN)   // no other start reads the rows
+        STFT_TRY(hipMemcpy2DAsync(static_cast<float2 *>(h.held_s[h.held].p) + at * F, (size_t)h.LA * F * sizeof(float2), S,
+                                  (size_t)frames * F * sizeof(float2), (size_t)frames * F * sizeof(float2), BK, hipMemcpyDeviceToDevice,
+                                  s));
     if (A)
         STFT_TRY(hipMemcpy2DAsync(static_cast<float *>(h.held_a[h.held].p) + at * F, (size_t)h.LA * F * sizeof(float), A,
                                   (size_t)frames * F * sizeof(float), (size_t)frames * F * sizeof(float), BK, hipMemcpyDeviceToDevice, s));
@@ -1597,17 +1800,17 @@ int misi_launch(lws_misi_stream &h, const float2 *S, const float *A, const float
     a.y_keep = R - h.hop;
     a.stream_floats = h.stream_floats;
     const int nxt = h.held ^ 1;
+    const bool given = h.start == LWS_START_GIVEN;   // any other start projects at entry: it keeps the magnitudes without iterations too
     const MisiStreamHeld held{static_cast<const float2 *>(h.held_s[h.held].p), static_cast<const float *>(h.held_a[h.held].p),
                               static_cast<const float *>(h.held_y[h.held].p),
                               closing || h.iters > 0 ? nullptr : static_cast<float2 *>(h.held_s[nxt].p),
-                              closing || h.iters == 0 ? nullptr : static_cast<float *>(h.held_a[nxt].p),
+                              closing || (given && h.iters == 0) ? nullptr : static_cast<float *>(h.held_a[nxt].p),
                               closing ? nullptr : static_cast<float *>(h.held_y[nxt].p)};
     const float *wa = static_cast<const float *>(h.win_a.p), *ws = static_cast<const float *>(h.win_s.p);
     float *st = static_cast<float *>(h.state.p);
-    if (p.in_lds)
-        hipLaunchKernelGGL(k_misi_la_stream<true>, dim3(h.B), dim3(p.threads), p.lds_bytes, s, S, A, y, C_out, x_out, wa, ws, st, held, a);
-    else
-        hipLaunchKernelGGL(k_misi_la_stream<false>, dim3(h.B), dim3(p.threads), p.lds_bytes, s, S, A, y, C_out, x_out, wa, ws, st, held, a);
+    auto *kernel = p.in_lds ? (given ? k_misi_la_stream<true, LWS_START_GIVEN> : k_misi_la_stream<true, LWS_START_MIXTURE>)
+                            : (given ? k_misi_la_stream<false, LWS_START_GIVEN> : k_misi_la_stream<false, LWS_START_MIXTURE>);
+    hipLaunchKernelGGL(kernel, dim3(h.B), dim3(p.threads), p.lds_bytes, s, S, A, y, C_out, x_out, wa, ws, st, held, a);
     STFT_TRY(hipGetLastError());
     h.base = (int)(((long long)h.base + (long long)h.hop * nsteps) % R);
     h.slot = (int)(((long long)h.slot + nsteps) % (LA + 1));
@@ -1622,10 +1825,17 @@ int misi_launch(lws_misi_stream &h, const float2 *S, const float *A, const float
 
 extern "C" int lws_misi_stream_create(int device, int B, int K, int N, int fshift, const double *awin, const double *swin,
                                       int perfectrec, int iters, int look_ahead, lws_misi_stream **out) {
+    return lws_misi_stream_create_ex(device, B, K, N, fshift, awin, swin, perfectrec, iters, look_ahead, LWS_START_GIVEN, out);
+}
+
+extern "C" int lws_misi_stream_create_ex(int device, int B, int K, int N, int fshift, const double *awin, const double *swin,
+                                         int perfectrec, int iters, int look_ahead, int start, lws_misi_stream **out) {
     if (!out) return lws::set_error(LWS_ERR_INVALID, "null pointer");
     *out = nullptr;
     int rc = check_shape(device, B, 1, N, fshift);
     if (rc) return rc;
+    if (start != LWS_START_GIVEN && start != LWS_START_MIXTURE) return lws::set_error(LWS_ERR_INVALID, "start %d for online MISI", start);
+    const bool given = start == LWS_START_GIVEN;
     if (B < 1) return lws::set_error(LWS_ERR_INVALID, "%d streams", B);
     if (K < 1) return lws::set_error(LWS_ERR_INVALID, "%d sources", K);
     if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
@@ -1639,9 +1849,12 @@ extern "C" int lws_misi_stream_create(int device, int B, int K, int N, int fshif
     if (2 * ((size_t)K + 1) * plan.source_floats > 0x7fffffffULL)   // the kernel indexes a stream's state, target and xs with ints
         return lws::set_error(LWS_ERR_UNSUPPORTED, "look-ahead of %d frames", look_ahead);
     STFT_TRY(hipSetDevice(device));
-    STFT_TRY(lws::allow_dynamic_lds<&k_misi_la_stream<true>>((int)RTISI_LDS_CAP));
-    STFT_TRY(lws::allow_dynamic_lds<&k_misi_la_stream<false>>(3 * MAXN * (int)sizeof(float2)));
+    STFT_TRY((lws::allow_dynamic_lds<&k_misi_la_stream<true, LWS_START_GIVEN>>((int)RTISI_LDS_CAP)));
+    STFT_TRY((lws::allow_dynamic_lds<&k_misi_la_stream<false, LWS_START_GIVEN>>(3 * MAXN * (int)sizeof(float2))));
+    STFT_TRY((lws::allow_dynamic_lds<&k_misi_la_stream<true, LWS_START_MIXTURE>>((int)RTISI_LDS_CAP)));
+    STFT_TRY((lws::allow_dynamic_lds<&k_misi_la_stream<false, LWS_START_MIXTURE>>(3 * MAXN * (int)sizeof(float2))));
     lws_misi_stream *h = new lws_misi_stream;
+    h->start = start;
     h->device = device; h->B = B; h->K = K; h->N = N; h->hop = fshift; h->LA = look_ahead; h->iters = iters;
     h->perfectrec = perfectrec ? 1 : 0;
     h->plan = plan;
@@ -1660,10 +1873,10 @@ extern "C" int lws_misi_stream_create(int device, int B, int K, int N, int fshif
     if (!rc) rc = h->win_s.ensure((size_t)N * sizeof(float));
     if (!rc) rc = h->held_y[0].ensure(y_bytes);
     if (!rc) rc = h->held_y[1].ensure(y_bytes);
-    if (!rc) rc = h->held_s[0].ensure(rows * sizeof(float2));
+    if (!rc && (given || iters == 0)) rc = h->held_s[0].ensure(rows * sizeof(float2));   // start rows, or entry rows to return
     if (!rc && iters == 0) rc = h->held_s[1].ensure(rows * sizeof(float2));
-    if (!rc && iters > 0) rc = h->held_a[0].ensure(rows * sizeof(float));
-    if (!rc && iters > 0) rc = h->held_a[1].ensure(rows * sizeof(float));
+    if (!rc && (iters > 0 || !given)) rc = h->held_a[0].ensure(rows * sizeof(float));
+    if (!rc && (iters > 0 || !given)) rc = h->held_a[1].ensure(rows * sizeof(float));
     hipError_t e = hipSuccess;
     if (!rc) e = hipEventCreateWithFlags(&h->last, hipEventDisableTiming);
     if (!rc && e == hipSuccess) e = hipMemset(h->state.p, 0, state_bytes);
@@ -1696,7 +1909,9 @@ extern "C" int lws_misi_stream_push(lws_misi_stream *h, const void *S_dev, const
         return lws::set_error(LWS_ERR_INVALID, "%d mixture samples for %d frames after %lld: expected %lld", samples, frames, h->entered,
                               want);
     if (frames == 0) return LWS_OK;
-    if (!S_dev || !y_dev) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    const bool given = h->start == LWS_START_GIVEN;
+    if ((!S_dev && (given || !A_dev)) || !y_dev)   // magnitudes alone serve any other start
+        return lws::set_error(LWS_ERR_INVALID, "null pointer");
     const long long nsteps = entered > h->LA ? entered - h->LA - h->committed : 0;
     if (nsteps > 0 && !C_out_dev) return lws::set_error(LWS_ERR_INVALID, "null pointer");
     STFT_TRY(hipSetDevice(h->device));
@@ -1705,12 +1920,12 @@ extern "C" int lws_misi_stream_push(lws_misi_stream *h, const void *S_dev, const
     if (rc) return rc;
     const float2 *S = static_cast<const float2 *>(S_dev);
     const size_t bins = (size_t)h->B * h->K * frames * (h->N / 2 + 1);
-    if (!A_dev && h->iters > 0) {   // |S| by the kernel lws_misi_la_dev takes it from
+    if (!A_dev && (h->iters > 0 || !given)) {   // |S| by the kernel lws_misi_la_dev takes it from
         if ((rc = h->abuf.ensure(bins * sizeof(float)))) return rc;
         hipLaunchKernelGGL(k_gla_abs, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, s, S, static_cast<float *>(h->abuf.p), bins);
         A_dev = static_cast<const float *>(h->abuf.p);
     }
-    if (h->iters == 0) A_dev = nullptr;
+    if (given && h->iters == 0) A_dev = nullptr;
     if (nsteps == 0) {
         if ((rc = misi_stash(*h, S, A_dev, y_dev, frames, samples, s))) return rc;
     } else {

@@ -59,6 +59,16 @@ cdef extern from "lws_hip.h" nogil:
                          const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream)
     int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, float *x_dev, int B, int K, int M, int N,
                         int fshift, const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream)
+    int lws_rtisi_la_dev_ex(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift,
+                            const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, int start,
+                            void *stream)
+    int lws_misi_la_dev_ex(int device, void *C_dev, const float *A_dev, const float *y_dev, float *x_dev, int B, int K, int M, int N,
+                           int fshift, const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, int start,
+                           void *stream)
+    int lws_rtisi_stream_create_ex(int device, int B, int N, int fshift, const double *awin, const double *swin, int perfectrec,
+                                   int iters, int look_ahead, int start, lws_rtisi_stream **out)
+    int lws_misi_stream_create_ex(int device, int B, int K, int N, int fshift, const double *awin, const double *swin, int perfectrec,
+                                  int iters, int look_ahead, int start, lws_misi_stream **out)
     ctypedef struct lws_rtisi_stream:
         pass
     int lws_rtisi_stream_create(int device, int B, int N, int fshift, const double *awin, const double *swin, int perfectrec,

@@ -394,8 +394,14 @@ def _rtisi_project(X, A):
     return np.where(mag > 0, A * X / np.where(mag > 0, mag, 1.0), A + 0j)
 
 
+def _start_arg(start, allowed):
+    if start not in allowed:
+        raise ValueError('start must be one of %s, got %r' % (', '.join(repr(a) for a in allowed), start))
+    return start
+
+
 def rtisi_la(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=None, perfectrec=False, return_signal=False,
-             _perturb=None, open_end=False):
+             _perturb=None, open_end=False, start='given'):
     """Real-Time Iterative Spectrogram Inversion with Look-Ahead from the start S, (T, F) or a stack (B, T, F), in fp64 on the
     host: the definition the device form is held to.  Frame m of the result depends on no input frame later than m + look_ahead.
     With inv(c) = swin irfft(c) and fwd(y) = rfft(awin y) on the timeline of fshift (T - 1) + fsize samples -- where, with
@@ -409,9 +415,16 @@ def rtisi_la(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=
     not read as zero (the lead-in still is, and the returned signal is still cut as istft cuts it), and the frame count need not be
     one the round trip keeps -- so the rows [:T1 - look_ahead] of a run on S[:T1] are those of a run on any longer S: what a stream
     (RtisiLaStream) computes.  Without perfectrec it changes nothing.
-    (_perturb(m, it, b, X) -> X: replaces the stacked projections of one inner iteration; the error model of the tests.)"""
+    start: how a frame enters.  'given' (the default): from S, as above.  'overlap': RTISI's own initial estimate, from magnitudes
+    alone -- frames enter one at a time, j ascending, and frame j, entering in commit step m, does not compute f_j = inv(S_j) but
+    y = keep (done + sum_{i = m..j-1} f_i) (i ascending), X = fwd(y[fshift j : fshift j + fsize]), c_j = A_j X / |X| (A_j + 0j
+    where |X| == 0: frame 0, every frame under a silent sum, every frame at fshift == fsize), f_j = inv(c_j).  Only A is read --
+    the phases of S are not, and S may be a real array -- and zero iterations return the entry estimates, not S.
+    (_perturb(m, it, b, X) -> X: replaces the stacked projections of one inner iteration, and with it = 0 and X[None] the projection
+    of an entering frame; the error model of the tests.)"""
     n, _ = _gla_args(iterations, 0.0)
     LA = _look_ahead_arg(look_ahead)
+    overlap = _start_arg(start, ('given', 'overlap')) == 'overlap'
     S = np.asarray(S)
     if S.ndim not in (2, 3):
         raise ValueError('expected a (T, F) spectrogram or a (B, T, F) stack')
@@ -434,13 +447,22 @@ def rtisi_la(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=
             if n > 0 and back != T:
                 raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
     S3, A3 = (S[None], A[None]) if S.ndim == 2 else (S, A)
-    out = S3.astype(np.complex128)
+    out = (A3 + 0j) if overlap else S3.astype(np.complex128)
     sig = np.empty((S3.shape[0], max(hi - lo, 0)))
-    for b in range(S3.shape[0] if (n > 0 or return_signal) else 0):
+    for b in range(S3.shape[0] if (n > 0 or return_signal or overlap) else 0):
         c, done, f, entered = out[b], np.zeros(total), np.zeros((T, fsize)), 0
         for m in range(T):
             last = min(m + LA, T - 1)
             while entered <= last:
+                if overlap:
+                    y = done.copy()
+                    for i in range(m, entered):
+                        y[fshift * i: fshift * i + fsize] += f[i]
+                    y *= keep
+                    X = np.fft.rfft(awin * y[fshift * entered: fshift * entered + fsize])
+                    if _perturb is not None:
+                        X = _perturb(m, 0, b, X[None])[0]
+                    c[entered] = _rtisi_project(X, A3[b, entered])
                 f[entered] = swin * np.fft.irfft(c[entered], fsize)
                 entered += 1
             for it in range(1, n + 1):
@@ -458,9 +480,22 @@ def rtisi_la(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=
         sig[b] = (keep * done)[lo: max(hi, lo)]
     if S.ndim == 2:
         out, sig = out[0], sig[0]
-    if n == 0:
+    if n == 0 and not overlap:
         out = S
     return (out, sig) if return_signal else out
+
+
+def _start_rows(S, magnitudes, start, device):
+    """The device tensors a look-ahead call passes down: (rows, magnitudes or None).  Under start='given' the rows are complex64.
+    Under another start only magnitudes are read, so rows that are real stay real (float32) and serve as the magnitudes themselves
+    -- their absolute values -- when none are given."""
+    import torch
+    A = None if magnitudes is None else _dev_tensor(magnitudes, torch.float32, device)
+    real = start != 'given' and not (S.is_complex() if torch.is_tensor(S) else np.iscomplexobj(S))
+    t = _dev_tensor(S, torch.float32 if real else torch.complex64, device)
+    if real and A is None:
+        A = t.abs()
+    return t, A
 
 
 class RtisiLaStream(object):
@@ -471,12 +506,16 @@ class RtisiLaStream(object):
     finalised, (k,) / (B, k).  Everything returned, concatenated, is rtisi_la(everything pushed, ..., open_end=True) (and its signal):
     however the rows are cut into chunks, bit for bit.  The state lives on the device between calls; a call runs on the caller's current
     torch stream and only enqueues work.  magnitudes: the targets of the pushed rows (default |S|).  iterations=0 returns the pushed rows
-    themselves, with the same latency.  close() frees the device state (also on deletion)."""
+    themselves, with the same latency.  start='overlap' drives the stream from magnitudes alone, as rtisi_la(..., start='overlap')
+    does: push(A) then takes real or complex rows, reads only their magnitudes (or `magnitudes`), and iterations=0 returns the entry
+    estimates.  close() frees the device state (also on deletion)."""
 
-    def __init__(self, fsize, fshift, awin, swin, iterations, look_ahead=3, perfectrec=False, batch=None, return_signal=False, device=0):
+    def __init__(self, fsize, fshift, awin, swin, iterations, look_ahead=3, perfectrec=False, batch=None, return_signal=False, device=0,
+                 start='given'):
         self._h = None
         n, _ = _gla_args(iterations, 0.0)
         self.look_ahead = _look_ahead_arg(look_ahead)
+        self.start = _start_arg(start, ('given', 'overlap'))
         if batch is not None and (int(batch) != batch or batch < 1):
             raise ValueError('batch must be None or a positive integer, got %r' % (batch,))
         if fsize % 2:
@@ -486,7 +525,8 @@ class RtisiLaStream(object):
         self._B, self._F = 1 if batch is None else int(batch), int(fsize) // 2 + 1
         self.finished = False
         swin = np.squeeze(np.asarray(swin, dtype=np.float64))
-        self._h = _capi.rtisi_stream_create(self._B, fsize, fshift, awin, swin, self.perfectrec, n, self.look_ahead, device=self.device)
+        self._h = _capi.rtisi_stream_create(self._B, fsize, fshift, awin, swin, self.perfectrec, n, self.look_ahead, device=self.device,
+                                            start=self.start)
 
     def _returns(self, out, sig, nf, ns):
         out = out[:, :nf]
@@ -501,22 +541,20 @@ class RtisiLaStream(object):
         import torch
         if self._h is None or self.finished:
             raise ValueError('push on a stream that has finished or been closed')
-        t = _dev_tensor(S, torch.complex64, self.device)
+        t, A = _start_rows(S, magnitudes, self.start, self.device)
         want = 2 if self.batch is None else 3
         if t.dim() != want or t.shape[-1] != self._F or (self.batch is not None and t.shape[0] != self._B):
             raise ValueError('expected rows of shape %s, got %s' % (('Tc', self._F) if self.batch is None else (self._B, 'Tc', self._F),
                                                                     tuple(t.shape)))
-        A = None
-        if magnitudes is not None:
-            A = _dev_tensor(magnitudes, torch.float32, self.device)
-            if A.shape != t.shape:
-                raise ValueError('magnitudes of shape %s for rows of shape %s' % (tuple(A.shape), tuple(t.shape)))
+        if A is not None and A.shape != t.shape:
+            raise ValueError('magnitudes of shape %s for rows of shape %s' % (tuple(A.shape), tuple(t.shape)))
         Tc = t.shape[-2]
         out = torch.empty((self._B, Tc, self._F), dtype=torch.complex64, device=t.device)
         sig = torch.empty((self._B, Tc * self.fshift), dtype=torch.float32, device=t.device) if self.return_signal else None
         nf, ns = 0, 0
         if Tc > 0:
-            nf, ns = _capi.rtisi_stream_push(self._h, t.data_ptr(), None if A is None else A.data_ptr(), Tc, out.data_ptr(),
+            nf, ns = _capi.rtisi_stream_push(self._h, None if t.dtype != torch.complex64 else t.data_ptr(),
+                                             None if A is None else A.data_ptr(), Tc, out.data_ptr(),
                                              None if sig is None else sig.data_ptr(),
                                              stream=torch.cuda.current_stream(t.device).cuda_stream)
         return self._returns(out, sig, nf, ns)
@@ -548,19 +586,23 @@ class RtisiLaStream(object):
 
 
 def rtisi_la_dev(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=None, perfectrec=False, return_signal=False,
-                 device=0):
+                 device=0, start='given'):
     """rtisi_la() above on the device (lws_gla.hip: float32, one workgroup per spectrogram marching over the frames with its
     state in LDS, one launch): S (T, F) or (B, T, F), numpy or torch; returns a new complex64 torch tensor (S itself is not
     modified), and with return_signal also the float32 signals (len,) / (B, len).  Runs on the caller's current torch stream
-    and only enqueues work.  Raises ValueError, as rtisi_la() does, for a frame count the round trip does not keep."""
+    and only enqueues work.  start: 'given', or 'overlap' for RTISI's own initial estimate from magnitudes alone (S real or complex,
+    its phases not read), as rtisi_la() defines it.  Raises ValueError, as rtisi_la() does, for a frame count the round trip does
+    not keep."""
     import torch
     n, _ = _gla_args(iterations, 0.0)
     LA = _look_ahead_arg(look_ahead)
-    t = _dev_tensor(S, torch.complex64, device)
+    start = _start_arg(start, ('given', 'overlap'))
+    t, A = _start_rows(S, magnitudes, start, device)
     if t.dim() not in (2, 3):
         raise ValueError('expected a (T, F) spectrogram or a (B, T, F) stack')
     single = t.dim() == 2
-    t3 = (t[None] if single else t).clone()
+    t3 = t[None] if single else t
+    t3 = t3.clone() if t3.dtype == torch.complex64 else torch.empty(t3.shape, dtype=torch.complex64, device=t3.device)
     B, T, F = t3.shape
     if F != fsize // 2 + 1:
         raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
@@ -568,15 +610,12 @@ def rtisi_la_dev(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitu
     back = _capi.stft_frames(length, fsize, fshift, perfectrec)
     if n > 0 and perfectrec and back != T:
         raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
-    A = None
-    if magnitudes is not None:
-        A = _dev_tensor(magnitudes, torch.float32, device)
-        if A.shape != t.shape:
-            raise ValueError('magnitudes of shape %s for a spectrogram of shape %s' % (tuple(A.shape), tuple(t.shape)))
+    if A is not None and A.shape != t.shape:
+        raise ValueError('magnitudes of shape %s for a spectrogram of shape %s' % (tuple(A.shape), tuple(t.shape)))
     sig = torch.empty((B, max(length, 0)), dtype=torch.float32, device=t3.device) if return_signal else None
     _capi.rtisi_la_dev(t3.data_ptr(), None if A is None else A.data_ptr(), None if sig is None or sig.numel() == 0 else sig.data_ptr(),
                        B, T, fsize, fshift, awin, swin, perfectrec, n, LA, device=int(device),
-                       stream=torch.cuda.current_stream(t3.device).cuda_stream)
+                       stream=torch.cuda.current_stream(t3.device).cuda_stream, start=start)
     out = t3[0] if single else t3
     return (out, sig[0] if single else sig) if return_signal else out
 
@@ -585,7 +624,7 @@ def rtisi_la_dev(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitu
 # Online MISI: the K sources of a known mixture under a look-ahead -- MISI as RTISI-LA is Griffin-Lim
 # --------------------------------------------------------------------------------------------
 def misi_la(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=None, perfectrec=False, return_signals=False,
-            _perturb=None, open_end=False):
+            _perturb=None, open_end=False, start='given'):
     """MISI under a look-ahead from the starts S, (K, T, F) or a stack (B, K, T, F), and the real mixture(s) `mixture`, (len,) /
     (B, len) with len that of istft(S[k]), in fp64 on the host: the definition the device form is held to.  Frame m of every
     source depends on no input frame later than m + look_ahead and on no mixture sample behind the end of that frame.  On the
@@ -608,10 +647,16 @@ def misi_la(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3, mag
     be one the round trip keeps, and the denominator of g sums w over ALL frames j >= 0 that would cover a sample, as if the input
     never ended, in the steps with m + look_ahead <= T - 1; in the later ones, which know the end, over the frames 0 .. T-1 as
     without open_end, so that g = 1 there and the last frames explain the whole mixture.
-    (_perturb(m, it, b, X) -> X: replaces the (K, last - m + 1, F) stack of projections of one inner iteration; the error model of
-    the tests.)"""
+    start: how a frame enters.  'given' (the default): from S, as above.  'mixture': with the phase of the mixture, from magnitudes
+    alone -- frame j of every source takes c_kj = A_kj X / |X| (A_kj + 0j where |X| == 0) with X = fwd(keep y[fshift j :
+    fshift j + fsize]), one transform for all sources, y on the timeline as placed and cut above (open_end included).  Only A is
+    read -- the phases of S are not, and S may be a real array -- and zero iterations return these rows, not S.  An entry does not
+    depend on the state, so this is misi_la(S0, ...) with S0 built the same way.
+    (_perturb(m, it, b, X) -> X: replaces the (K, last - m + 1, F) stack of projections of one inner iteration, and with it = 0 and
+    the (1, 1, F) transform that of an entering frame; the error model of the tests.)"""
     n, _ = _gla_args(iterations, 0.0)
     LA = _look_ahead_arg(look_ahead)
+    mix = _start_arg(start, ('given', 'mixture')) == 'mixture'
     S = np.asarray(S)
     if S.ndim not in (3, 4):
         raise ValueError('expected (K, T, F) spectrograms of the sources or a (B, K, T, F) stack')
@@ -652,15 +697,20 @@ def misi_la(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3, mag
         for j in range(T + (fsize - 1) // fshift):
             den_open[fshift * j: fshift * j + fsize] += w[:max(0, min(fsize, total + fsize - fshift * j))]
         den_open = den_open[:total]
-    out = S4.astype(np.complex128)
+    out = (A4 + 0j) if mix else S4.astype(np.complex128)
     sig = np.empty((B, K, length))
-    for b in range(B if (n > 0 or return_signals) else 0):
+    for b in range(B if (n > 0 or return_signals or mix) else 0):
         c, done, f, entered = out[b], np.zeros((K, total)), np.zeros((K, T, fsize)), 0
         yfull, num = np.zeros(total), np.zeros(total)
         yfull[lo: lo + ylen] = y2[b]
         for m in range(T):
             last = min(m + LA, T - 1)
             while entered <= last:
+                if mix:
+                    X = np.fft.rfft(awin * (keep * yfull)[fshift * entered: fshift * entered + fsize])[None, None]
+                    if _perturb is not None:
+                        X = _perturb(m, 0, b, X)
+                    c[:, entered] = _rtisi_project(X[0], A4[b, :, entered])
                 for k in range(K):
                     f[k, entered] = swin * np.fft.irfft(c[k, entered], fsize)
                 num[fshift * entered: fshift * entered + fsize] += w
@@ -689,7 +739,7 @@ def misi_la(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3, mag
         for k in range(1, K):
             tot += done[k]
         sig[b] = (keep * done + keep * (yfull - tot) / K)[:, lo: lo + length]
-    if n == 0:
+    if n == 0 and not mix:
         out = S4
     if S.ndim == 3:
         out, sig = out[0], sig[0]
@@ -697,30 +747,30 @@ def misi_la(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3, mag
 
 
 def misi_la_dev(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=None, perfectrec=False,
-                return_signals=False, device=0):
+                return_signals=False, device=0, start='given'):
     """misi_la() above on the device (lws_gla.hip: float32, one workgroup per mixture marching over the frames, its sources one
     after another, the state in LDS when it fits; one launch): S (K, T, F) or (B, K, T, F) and mixture (len,) / (B, len), numpy or
     torch; returns a new complex64 torch tensor (S itself is not modified), and with return_signals also the float32 signals
-    (K, len) / (B, K, len).  Runs on the caller's current torch stream and only enqueues work.  Raises ValueError, as misi_la()
-    does, for a frame count the round trip does not keep."""
+    (K, len) / (B, K, len).  Runs on the caller's current torch stream and only enqueues work.  start: 'given', or 'mixture' for the
+    phase of the mixture from magnitudes alone (S real or complex, its phases not read), as misi_la() defines it.  Raises ValueError,
+    as misi_la() does, for a frame count the round trip does not keep."""
     import torch
     n, _ = _gla_args(iterations, 0.0)
     LA = _look_ahead_arg(look_ahead)
-    t = _dev_tensor(S, torch.complex64, device)
+    start = _start_arg(start, ('given', 'mixture'))
+    t, A = _start_rows(S, magnitudes, start, device)
     if t.dim() not in (3, 4):
         raise ValueError('expected (K, T, F) spectrograms of the sources or a (B, K, T, F) stack')
     single = t.dim() == 3
-    t4 = (t[None] if single else t).clone()
+    t4 = t[None] if single else t
+    t4 = t4.clone() if t4.dtype == torch.complex64 else torch.empty(t4.shape, dtype=torch.complex64, device=t4.device)
     B, K, T, F = t4.shape
     if K < 1:
         raise ValueError('no sources')
     if F != fsize // 2 + 1:
         raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
-    A = None
-    if magnitudes is not None:
-        A = _dev_tensor(magnitudes, torch.float32, device)
-        if A.shape != t.shape:
-            raise ValueError('magnitudes of shape %s for spectrograms of shape %s' % (tuple(A.shape), tuple(t.shape)))
+    if A is not None and A.shape != t.shape:
+        raise ValueError('magnitudes of shape %s for spectrograms of shape %s' % (tuple(A.shape), tuple(t.shape)))
     y = _dev_tensor(mixture, torch.float32, device)
     length = max(_capi.istft_length(T, fsize, fshift, perfectrec), 0)
     if y.dim() != t.dim() - 2 or tuple(y.shape)[-1:] != (length,) or (not single and y.shape[0] != B):
@@ -732,7 +782,7 @@ def misi_la_dev(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3,
     sig = torch.empty((B, K, length), dtype=torch.float32, device=t4.device) if return_signals else None
     _capi.misi_la_dev(t4.data_ptr(), None if A is None else A.data_ptr(), y.data_ptr(),
                       None if sig is None or sig.numel() == 0 else sig.data_ptr(), B, K, T, fsize, fshift, awin, swin, perfectrec, n,
-                      LA, device=int(device), stream=torch.cuda.current_stream(t4.device).cuda_stream)
+                      LA, device=int(device), stream=torch.cuda.current_stream(t4.device).cuda_stream, start=start)
     out = t4[0] if single else t4
     return (out, sig[0] if single else sig) if return_signals else out
 
@@ -749,14 +799,17 @@ class MisiLaStream(object):
     concatenated, is misi_la(everything pushed, ..., open_end=True) and its signals: however the input is cut into chunks, bit for bit.
     The state lives on the device between calls; a call runs on the caller's current torch stream, only enqueues work and keeps no
     reference to its arguments.  magnitudes: the targets of the pushed rows (default |S|).  iterations=0 returns the pushed rows
-    themselves, with the same latency.  A push with another sample count raises ValueError and leaves the stream as it was.  close()
-    frees the device state (also on deletion)."""
+    themselves, with the same latency.  start='mixture' drives the stream from magnitudes alone, as misi_la(..., start='mixture') does:
+    push(A, mixture) then takes real or complex rows, reads only their magnitudes (or `magnitudes`), and iterations=0 returns the
+    entry estimates.  A push with another sample count raises ValueError and leaves the stream as it was.  close() frees the device
+    state (also on deletion)."""
 
     def __init__(self, K, fsize, fshift, awin, swin, iterations, look_ahead=3, perfectrec=False, batch=None, return_signals=False,
-                 device=0):
+                 device=0, start='given'):
         self._h = None
         n, _ = _gla_args(iterations, 0.0)
         self.look_ahead = _look_ahead_arg(look_ahead)
+        self.start = _start_arg(start, ('given', 'mixture'))
         if int(K) != K or K < 1:
             raise ValueError('K must be a positive integer, got %r' % (K,))
         if batch is not None and (int(batch) != batch or batch < 1):
@@ -771,7 +824,7 @@ class MisiLaStream(object):
         self.finished = False
         swin = np.squeeze(np.asarray(swin, dtype=np.float64))
         self._h = _capi.misi_stream_create(self._B, self.K, fsize, fshift, awin, swin, self.perfectrec, n, self.look_ahead,
-                                           device=self.device)
+                                           device=self.device, start=self.start)
 
     def _need(self, M):
         return 0 if M <= 0 else self.fshift * (M - 1) + self.fsize - self._lo
@@ -793,16 +846,13 @@ class MisiLaStream(object):
         import torch
         if self._h is None or self.finished:
             raise ValueError('push on a stream that has finished or been closed')
-        t = _dev_tensor(S, torch.complex64, self.device)
+        t, A = _start_rows(S, magnitudes, self.start, self.device)
         want = 3 if self.batch is None else 4
         if t.dim() != want or t.shape[-1] != self._F or t.shape[-3] != self.K or (self.batch is not None and t.shape[0] != self._B):
             raise ValueError('expected rows of shape %s, got %s' %
                              ((self.K, 'Tc', self._F) if self.batch is None else (self._B, self.K, 'Tc', self._F), tuple(t.shape)))
-        A = None
-        if magnitudes is not None:
-            A = _dev_tensor(magnitudes, torch.float32, self.device)
-            if A.shape != t.shape:
-                raise ValueError('magnitudes of shape %s for rows of shape %s' % (tuple(A.shape), tuple(t.shape)))
+        if A is not None and A.shape != t.shape:
+            raise ValueError('magnitudes of shape %s for rows of shape %s' % (tuple(A.shape), tuple(t.shape)))
         Tc = t.shape[-2]
         y = _dev_tensor(mixture, torch.float32, self.device)
         ns_in = self.samples_needed(Tc)
@@ -813,7 +863,8 @@ class MisiLaStream(object):
         sig = torch.empty((self._B, self.K, Tc * self.fshift), dtype=torch.float32, device=t.device) if self.return_signals else None
         nf, ns = 0, 0
         if Tc > 0:
-            nf, ns = _capi.misi_stream_push(self._h, t.data_ptr(), None if A is None else A.data_ptr(), y.data_ptr(), Tc, ns_in,
+            nf, ns = _capi.misi_stream_push(self._h, None if t.dtype != torch.complex64 else t.data_ptr(),
+                                            None if A is None else A.data_ptr(), y.data_ptr(), Tc, ns_in,
                                             out.data_ptr(), None if sig is None else sig.data_ptr(),
                                             stream=torch.cuda.current_stream(t.device).cuda_stream)
             self._entered += Tc
@@ -1192,41 +1243,42 @@ class lws(object):
         return misi_dev(S, mixture, self.fsize, self.fshift, self.awin, self.swin, iterations, magnitudes=magnitudes,
                         perfectrec=self.perfectrec, return_trace=return_trace, return_signals=return_signals, device=self.device)
 
-    def rtisi_la(self, S, iterations, look_ahead=None, magnitudes=None, return_signal=False, open_end=False):
+    def rtisi_la(self, S, iterations, look_ahead=None, magnitudes=None, return_signal=False, open_end=False, start='given'):
         """Host fp64 form with this object's windows, perfectrec and (look_ahead=None) look-ahead: see the module's rtisi_la."""
         return rtisi_la(S, self.fsize, self.fshift, self.awin, self.swin, iterations,
                         look_ahead=self.look_ahead if look_ahead is None else look_ahead, magnitudes=magnitudes,
-                        perfectrec=self.perfectrec, return_signal=return_signal, open_end=open_end)
+                        perfectrec=self.perfectrec, return_signal=return_signal, open_end=open_end, start=start)
 
-    def rtisi_la_dev(self, S, iterations, look_ahead=None, magnitudes=None, return_signal=False):
+    def rtisi_la_dev(self, S, iterations, look_ahead=None, magnitudes=None, return_signal=False, start='given'):
         """Device form: a new complex64 torch tensor, see the module's rtisi_la_dev."""
         return rtisi_la_dev(S, self.fsize, self.fshift, self.awin, self.swin, iterations,
                             look_ahead=self.look_ahead if look_ahead is None else look_ahead, magnitudes=magnitudes,
-                            perfectrec=self.perfectrec, return_signal=return_signal, device=self.device)
+                            perfectrec=self.perfectrec, return_signal=return_signal, device=self.device, start=start)
 
-    def rtisi_la_stream(self, iterations, look_ahead=None, batch=None, return_signal=False):
+    def rtisi_la_stream(self, iterations, look_ahead=None, batch=None, return_signal=False, start='given'):
         """A RtisiLaStream with the windows, look-ahead and device of this object: push() rows as they arrive, then finish()."""
         return RtisiLaStream(self.fsize, self.fshift, self.awin, self.swin, iterations,
-                             look_ahead=self.look_ahead if look_ahead is None else look_ahead, perfectrec=self.perfectrec, batch=batch, return_signal=return_signal, device=self.device)
+                             look_ahead=self.look_ahead if look_ahead is None else look_ahead, perfectrec=self.perfectrec, batch=batch,
+                             return_signal=return_signal, device=self.device, start=start)
 
-    def misi_la(self, S, mixture, iterations, look_ahead=None, magnitudes=None, return_signals=False, open_end=False):
+    def misi_la(self, S, mixture, iterations, look_ahead=None, magnitudes=None, return_signals=False, open_end=False, start='given'):
         """Host fp64 form with this object's windows, perfectrec and (look_ahead=None) look-ahead: see the module's misi_la."""
         return misi_la(S, mixture, self.fsize, self.fshift, self.awin, self.swin, iterations,
                        look_ahead=self.look_ahead if look_ahead is None else look_ahead, magnitudes=magnitudes,
-                       perfectrec=self.perfectrec, return_signals=return_signals, open_end=open_end)
+                       perfectrec=self.perfectrec, return_signals=return_signals, open_end=open_end, start=start)
 
-    def misi_la_dev(self, S, mixture, iterations, look_ahead=None, magnitudes=None, return_signals=False):
+    def misi_la_dev(self, S, mixture, iterations, look_ahead=None, magnitudes=None, return_signals=False, start='given'):
         """Device form: a new complex64 torch tensor, see the module's misi_la_dev."""
         return misi_la_dev(S, mixture, self.fsize, self.fshift, self.awin, self.swin, iterations,
                            look_ahead=self.look_ahead if look_ahead is None else look_ahead, magnitudes=magnitudes,
-                           perfectrec=self.perfectrec, return_signals=return_signals, device=self.device)
+                           perfectrec=self.perfectrec, return_signals=return_signals, device=self.device, start=start)
 
-    def misi_la_stream(self, K, iterations, look_ahead=None, batch=None, return_signals=False):
+    def misi_la_stream(self, K, iterations, look_ahead=None, batch=None, return_signals=False, start='given'):
         """A MisiLaStream for K sources with the windows, look-ahead and device of this object: push() rows and mixture samples as
         they arrive, then finish()."""
         return MisiLaStream(K, self.fsize, self.fshift, self.awin, self.swin, iterations,
                             look_ahead=self.look_ahead if look_ahead is None else look_ahead, perfectrec=self.perfectrec, batch=batch,
-                            return_signals=return_signals, device=self.device)
+                            return_signals=return_signals, device=self.device, start=start)
 
     def nofuture_lws(self, S, iterations=None, thresholds=None):
         if iterations is None:
