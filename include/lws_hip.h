@@ -232,6 +232,26 @@ int lws_griffin_lim_dev(int device, void *C_dev, const float *A_dev, int B, int 
 int lws_misi_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, int B, int K, int M, int N, int fshift,
                  const double *awin, const double *swin, int perfectrec, int iters, float *x_dev, double *trace, void *stream);
 
+/* Training through MISI (unfolded MISI under a waveform loss, Wang, Le Roux & Hershey 2018): lws_misi_dev with a tape, and its
+ * backward pass.  lws_misi_tape_dev takes the arguments of lws_misi_dev without the trace and with A_dev required, runs the same
+ * launches -- C_dev and x_dev come back with the bits of lws_misi_dev -- and also writes the X_k of every step, before their
+ * projection, to tape_dev[iters][B][K][M][N/2+1] (complex64; required if iters > 0).
+ * lws_misi_backward_dev: from the cotangents gC_dev[B][K][M][N/2+1] (complex64) of the returned C and gx_dev[B][K][len] (float32) of
+ * the signals -- either may be NULL: zeros -- the gradients of the loss with respect to the magnitudes, gA_out[B][K][M][N/2+1]
+ * (float32, required), the start, gS_out[B][K][M][N/2+1] (complex64), and the mixtures, gy_out[B][len] (float32); gS_out and gy_out
+ * may be NULL: not stored.  Complex gradients are g = dL/dRe + j dL/dIm (dL = Re sum conj(g) dz).  A_dev and tape_dev are those of the
+ * forward call.  Backward from i = iters to 1, with u = X / |X| of the tape: gA += Re(conj(u) gc), gX = j u (A / |X|) Im(conj(u) gc)
+ * (u = 1 and gX = 0 where |X| == 0); gv_k = N istft(gX / 2, Re gX at the bins 0 and N/2; window awin); m = mean_k gv_k (k ascending),
+ * gy += m; gc_k = (2/N) stft(gv_k - m; window swin) (1/N and no imaginary part at the bins 0 and N/2); on entry
+ * gc = gC + that of gx, and the gc left over is gS.  iters == 0: gA = 0, gS and gy from the entry alone.  Three launches per
+ * iteration, no atomics, every sum in a fixed order: results repeat bit for bit.  The calls only enqueue work on `stream`.  Argument
+ * errors and status codes as lws_misi_dev; a null A_dev, gA_out or (iters > 0) tape_dev: LWS_ERR_INVALID. */
+int lws_misi_tape_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, int B, int K, int M, int N, int fshift,
+                      const double *awin, const double *swin, int perfectrec, int iters, float *x_dev, void *tape_dev, void *stream);
+int lws_misi_backward_dev(int device, const void *gC_dev, const float *gx_dev, const float *A_dev, const void *tape_dev, int B, int K,
+                          int M, int N, int fshift, const double *awin, const double *swin, int perfectrec, int iters, float *gA_out,
+                          void *gS_out, float *gy_out, void *stream);
+
 /* RTISI-LA (Real-Time Iterative Spectrogram Inversion with Look-Ahead, Zhu, Beauregard & Wyse 2007), device resident (lws_gla.hip;
  * what the reference's online sweeps approximate): Griffin-Lim under a look-ahead, frame m of the result depending on no input
  * frame later than m + look_ahead.  With inv(c) = swin irfft(c) and fwd(y) = rfft(awin y) on the uncut timeline of hop (M - 1) + N

@@ -33,6 +33,7 @@ EXPORTS = (
     "lws_nofuture_lws_dev", "lws_online_lws_dev", "lws_residual_dev", "lws_last_kernel_time",
     "lws_last_kernel_name", "lws_generic_stage", "lws_stft_frames", "lws_istft_length", "lws_stft_dev", "lws_istft_dev", "lws_stft_zp_dev",
     "lws_consistency_dev", "lws_griffin_lim_dev", "lws_misi_dev", "lws_rtisi_la_dev", "lws_misi_la_dev",
+    "lws_misi_tape_dev", "lws_misi_backward_dev",
     "lws_rtisi_la_dev_ex", "lws_misi_la_dev_ex", "lws_rtisi_stream_create_ex", "lws_misi_stream_create_ex",
     "lws_rtisi_stream_create", "lws_rtisi_stream_push", "lws_rtisi_stream_finish", "lws_rtisi_stream_destroy", "lws_rtisi_la_placement",
     "lws_misi_stream_create", "lws_misi_stream_push", "lws_misi_stream_finish", "lws_misi_stream_destroy", "lws_hann", "lws_synthwin", "lws_weights_shape", "lws_create_weights",
@@ -109,6 +110,8 @@ def load():
     dp = C.c_double
     lib.lws_griffin_lim_dev.argtypes = [ip, vp, vp, ip, ip, ip, ip, vp, vp, ip, ip, dp, vp, vp]
     lib.lws_misi_dev.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, vp, vp, vp]
+    lib.lws_misi_tape_dev.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, vp, vp, vp]
+    lib.lws_misi_backward_dev.argtypes = [ip, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, vp, vp, vp, vp]
     lib.lws_rtisi_la_dev.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, vp, vp, ip, ip, ip, vp]
     lib.lws_misi_la_dev.argtypes = [ip, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, ip, vp]
     lib.lws_rtisi_la_dev_ex.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, vp, vp, ip, ip, ip, ip, vp]
@@ -512,6 +515,31 @@ def misi_dev(C_ptr, A_ptr, y_ptr, B, K, frames, fsize, fshift, awin, swin, perfe
                               w.ctypes.data, int(bool(perfectrec)), int(iterations), x_ptr,
                               trace.ctypes.data if (want_trace and trace.size) else None, stream))
     return trace
+
+
+def misi_tape_dev(C_ptr, A_ptr, y_ptr, B, K, frames, fsize, fshift, awin, swin, perfectrec, iterations, x_ptr, tape_ptr, device=0,
+                  stream=None):
+    """misi_dev with a tape: A_ptr is required, tape_ptr is device complex64 [iterations][B][K][frames][fsize//2+1] for the X_k of
+    every step before their projection (None only with zero iterations).  C and the signals get the bits misi_dev gives them.
+    Only enqueues."""
+    a, w = _win(awin), _win(swin)
+    if a.shape != (int(fsize),) or w.shape != (int(fsize),):
+        raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
+    check(load().lws_misi_tape_dev(int(device), C_ptr, A_ptr, y_ptr, int(B), int(K), int(frames), int(fsize), int(fshift),
+                                   a.ctypes.data, w.ctypes.data, int(bool(perfectrec)), int(iterations), x_ptr, tape_ptr, stream))
+
+
+def misi_backward_dev(gC_ptr, gx_ptr, A_ptr, tape_ptr, B, K, frames, fsize, fshift, awin, swin, perfectrec, iterations, gA_ptr,
+                      gS_ptr=None, gy_ptr=None, device=0, stream=None):
+    """The backward pass of misi_tape_dev: cotangents gC_ptr (device complex64, as C) and gx_ptr (device float32, as the signals),
+    either None for zeros; A_ptr and tape_ptr those of the forward call; results to gA_ptr (float32, as A), gS_ptr (complex64, as
+    the start) and gy_ptr (float32, as the mixtures), the last two None to leave them out.  Only enqueues."""
+    a, w = _win(awin), _win(swin)
+    if a.shape != (int(fsize),) or w.shape != (int(fsize),):
+        raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
+    check(load().lws_misi_backward_dev(int(device), gC_ptr, gx_ptr, A_ptr, tape_ptr, int(B), int(K), int(frames), int(fsize),
+                                       int(fshift), a.ctypes.data, w.ctypes.data, int(bool(perfectrec)), int(iterations), gA_ptr,
+                                       gS_ptr, gy_ptr, stream))
 
 
 def start_code(start, allowed):

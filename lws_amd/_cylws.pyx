@@ -284,6 +284,29 @@ def lws_misi_dev(int device, C_dev, A_dev, y_dev, int B, int K, int M, int N, in
     return rc
 
 
+def lws_misi_tape_dev(int device, C_dev, A_dev, y_dev, int B, int K, int M, int N, int fshift, awin, swin, int perfectrec, int iters,
+                      x_dev, tape_dev, stream):
+    cdef uintptr_t cd = _addr(C_dev), ad = _addr(A_dev), yd = _addr(y_dev), a = _addr(awin), w = _addr(swin), xd = _addr(x_dev)
+    cdef uintptr_t t = _addr(tape_dev), st = _addr(stream)
+    cdef int rc
+    with nogil:
+        rc = c.lws_misi_tape_dev(device, <void *>cd, <const float *>ad, <const float *>yd, B, K, M, N, fshift, <const double *>a,
+                                 <const double *>w, perfectrec, iters, <float *>xd, <void *>t, <void *>st)
+    return rc
+
+
+def lws_misi_backward_dev(int device, gC_dev, gx_dev, A_dev, tape_dev, int B, int K, int M, int N, int fshift, awin, swin,
+                          int perfectrec, int iters, gA_out, gS_out, gy_out, stream):
+    cdef uintptr_t gcd = _addr(gC_dev), gxd = _addr(gx_dev), ad = _addr(A_dev), t = _addr(tape_dev), a = _addr(awin), w = _addr(swin)
+    cdef uintptr_t ga = _addr(gA_out), gs = _addr(gS_out), gy = _addr(gy_out), st = _addr(stream)
+    cdef int rc
+    with nogil:
+        rc = c.lws_misi_backward_dev(device, <const void *>gcd, <const float *>gxd, <const float *>ad, <const void *>t, B, K, M, N,
+                                     fshift, <const double *>a, <const double *>w, perfectrec, iters, <float *>ga, <void *>gs,
+                                     <float *>gy, <void *>st)
+    return rc
+
+
 def lws_rtisi_la_dev(int device, C_dev, A_dev, x_dev, int B, int M, int N, int fshift, awin, swin, int perfectrec, int iters,
                      int look_ahead, stream):
     cdef uintptr_t cd = _addr(C_dev), ad = _addr(A_dev), xd = _addr(x_dev), a = _addr(awin), w = _addr(swin), st = _addr(stream)

@@ -187,9 +187,11 @@ __global__ void __launch_bounds__(256) k_misi_residual(const float *frames, cons
 
 // k_gla_forward for source blockIdx.y % K of mixture blockIdx.y / K with the shared mixture error in its load,
 // (OLA_k(t) + delta[t]) awin[n], OLA_k as k_misi_residual stored it; the epilogue is the magnitude projection alone (gla_bin without
-// momentum or sums).
+// momentum or sums).  TAPE: X as it stands before the projection also goes to tape[B K][M][F], for the backward pass.
+template <bool TAPE>
 __global__ void __launch_bounds__(FFT_THREADS) k_misi_forward(const float *sig, const float *delta, const float *awin, float2 *C,
-                                                               const float *A, int K, int M, int N, int odd, int log2e, int hop) {
+                                                               const float *A, int K, int M, int N, int odd, int log2e, int hop,
+                                                               float2 *tape) {
     extern __shared__ float2 lds[];
     const int m0 = 2 * blockIdx.x, bk = blockIdx.y, F = N / 2 + 1;
     const bool two = m0 + 1 < M;
@@ -210,6 +212,10 @@ __global__ void __launch_bounds__(FFT_THREADS) k_misi_forward(const float *sig, 
     double p = 0, e = 0;
     for (int k = threadIdx.x; k < F; k += blockDim.x) {
         const float2 zk = r[k], zn = r[k == 0 ? 0 : N - k];
+        if constexpr (TAPE) {
+            tape[base + k] = make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y));
+            if (two) tape[base + F + k] = make_float2(0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x));
+        }
         gla_bin<false>(make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)), C, A, nullptr, base + k, st, p, e);
         if (two) gla_bin<false>(make_float2(0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)), C, A, nullptr, base + F + k, st, p, e);
     }
@@ -1140,11 +1146,130 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) k_misi_la_stream(const floa
     }
 }
 
+// ---- MISI, backward: the gradient of a loss on the final C and on the signals with respect to A, the start and the mixture, from
+// the tape of k_misi_forward<true>.  Complex gradients are g = dL/dRe + j dL/dIm.  An iteration runs its three launches the other
+// way: k_misi_bwd_project (the projection's derivative per bin, then the adjoint of the forward transform: a raw inverse transform
+// times awin), k_misi_bwd_share (the adjoint of sharing the mixture error out), k_misi_bwd_frames (the adjoint of the inverse
+// transform: a forward transform of the frames times swin, weighted).  No atomics: every sum has one owner and a fixed order.
+
+// Step 3 for one bin: gc the gradient on c = A X / |X|, X from the tape.  gA gets Re(conj(u) gc), u = X / |X| (u = 1 where |X| == 0,
+// as the forward gives A + 0j there), written on the first visit and added after that; returns what the inverse transform takes in
+// this bin, gX / 2 (Re gX at the bins 0 and N/2, which have no mirror image) with gX = j u (A / |X|) Im(conj(u) gc).
+__device__ __forceinline__ float2 misi_bwd_bin(const float2 *gc, const float2 *tape, const float *A, float *gA, size_t i, bool edge,
+                                               int first) {
+    const float2 g = gc[i], X = tape[i];
+    const float mag = sqrtf(X.x * X.x + X.y * X.y);
+    float ga = g.x;
+    float2 gX = make_float2(0.f, 0.f);
+    if (mag > 0.f) {
+        const float ux = X.x / mag, uy = X.y / mag;
+        ga = ux * g.x + uy * g.y;
+        const float s = (A[i] / mag) * (ux * g.y - uy * g.x);
+        gX = make_float2(-uy * s, ux * s);
+    }
+    gA[i] = first ? ga : gA[i] + ga;
+    return edge ? make_float2(gX.x, 0.f) : make_float2(0.5f * gX.x, 0.5f * gX.y);
+}
+
+// Steps 3 and 4 for the frames m0 = 2 blockIdx.x and m0 + 1 of source blockIdx.y: Z = G_m + j G_{m+1} on the Hermitian-completed
+// bins as k_gla_inverse builds it, one raw inverse transform (the N of the adjoint and the 1/N of the inverse cancel), times awin,
+// into the frame buffer; k_misi_bwd_share overlap-adds it.
+__global__ void __launch_bounds__(FFT_THREADS) k_misi_bwd_project(const float2 *gc, const float2 *tape, const float *A, float *gA,
+                                                                   float *frames, const float *awin, int M, int N, int odd, int log2e,
+                                                                   int first) {
+    extern __shared__ float2 lds[];
+    const int m0 = 2 * blockIdx.x, bk = blockIdx.y, F = N / 2 + 1;
+    const bool two = m0 + 1 < M;
+    const size_t base = ((size_t)bk * M + m0) * F;
+    float2 *x = lds, *y = lds + N;
+    for (int k = threadIdx.x; k < F; k += blockDim.x) {
+        const bool edge = k == 0 || k == N / 2;
+        const float2 u = misi_bwd_bin(gc, tape, A, gA, base + k, edge, first);
+        const float2 v = two ? misi_bwd_bin(gc, tape, A, gA, base + F + k, edge, first) : make_float2(0.f, 0.f);
+        rtisi_put_pair(x, k, N, u, v);
+    }
+    __syncthreads();
+    const float2 *r = fft_lds<9>(x, y, N, odd, log2e, 1.0f);
+    float *o0 = frames + ((size_t)bk * M + m0) * N, *o1 = o0 + N;
+    for (int n = threadIdx.x; n < N; n += blockDim.x) {
+        const float w = awin[n];
+        o0[n] = r[n].x * w;
+        if (two) o1[n] = r[n].y * w;
+    }
+}
+
+// Step 1 per sample t of the uncut timeline: gv_k(t) is the overlap-add of the frames k_misi_bwd_project left (gla_sample: ascending
+// frames, zero in the perfectrec cuts) or, ENTRY, the cotangent gs of the signals itself ([B][K][len], null: zeros); m = mean_k gv_k
+// (k ascending), gsig[b][k][t] = gv_k - m, and gy[b][t - zero_lo] = m (first) or += m.  gy may be null.
+template <bool ENTRY>
+__global__ void __launch_bounds__(256) k_misi_bwd_share(const float *src, float *gsig, float *gy, int K, int M, int N, int hop,
+                                                        int zero_lo, int zero_hi, int first) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    const int Tfull = hop * (M - 1) + N, t_end = Tfull - zero_hi, len = t_end - zero_lo;
+    if (t >= Tfull) return;
+    const bool kept = t >= zero_lo && t < t_end;
+    float acc = 0.f;
+    for (int k = 0; k < K; ++k) {
+        const size_t bk = (size_t)b * K + k;
+        float g;
+        if (ENTRY) g = (kept && src) ? src[bk * len + (t - zero_lo)] : 0.f;
+        else g = gla_sample(src + bk * M * N, t, M, N, hop, zero_lo, t_end);
+        gsig[bk * Tfull + t] = g;
+        acc = k ? acc + g : g;
+    }
+    const float m = acc / (float)K;
+    for (int k = 0; k < K; ++k) gsig[((size_t)b * K + k) * Tfull + t] -= m;
+    if (kept && gy) {
+        float *o = gy + (size_t)b * len + (t - zero_lo);
+        *o = first ? m : *o + m;
+    }
+}
+
+// Step 2 for the frames m0, m0 + 1 of source blockIdx.y: z = (gsig at hop m0 + j gsig at hop (m0 + 1)) swin, one forward transform,
+// the pair separated as k_gla_forward separates it, times 2/N (1/N at the bins 0 and N/2, whose imaginary parts the forward never
+// reads: zero), plus the cotangent gC of the final C where one is given (the entry pass).
+__global__ void __launch_bounds__(FFT_THREADS) k_misi_bwd_frames(const float *gsig, const float *swin, const float2 *gC, float2 *gc,
+                                                                  int M, int N, int odd, int log2e, int hop) {
+    extern __shared__ float2 lds[];
+    const int m0 = 2 * blockIdx.x, bk = blockIdx.y, F = N / 2 + 1;
+    const bool two = m0 + 1 < M;
+    const int Tfull = hop * (M - 1) + N;
+    const float *sg = gsig + (size_t)bk * Tfull;
+    float2 *xa = lds, *ya = lds + N;
+    for (int n = threadIdx.x; n < N; n += blockDim.x) {
+        const float w = swin[n];
+        const int t0 = m0 * hop + n, t1 = t0 + hop;
+        xa[n] = make_float2(sg[t0] * w, two ? sg[t1] * w : 0.f);
+    }
+    __syncthreads();
+    const float2 *r = fft_lds<9>(xa, ya, N, odd, log2e, -1.0f);
+    const size_t base = ((size_t)bk * M + m0) * F;
+    const float inv = 1.0f / (float)N;
+    for (int k = threadIdx.x; k < F; k += blockDim.x) {
+        const float2 zk = r[k], zn = r[k == 0 ? 0 : N - k];
+        const bool edge = k == 0 || k == N / 2;
+        const float w = edge ? 0.5f * inv : inv;             // (1/2 of the separation) (2/N, or 1/N)
+        float2 g0 = make_float2(w * (zk.x + zn.x), edge ? 0.f : w * (zk.y - zn.y));
+        float2 g1 = make_float2(w * (zk.y + zn.y), edge ? 0.f : w * (zn.x - zk.x));
+        if (gC) {
+            const float2 c0 = gC[base + k];
+            g0 = make_float2(g0.x + c0.x, g0.y + c0.y);
+            if (two) {
+                const float2 c1 = gC[base + F + k];
+                g1 = make_float2(g1.x + c1.x, g1.y + c1.y);
+            }
+        }
+        gc[base + k] = g0;
+        if (two) gc[base + F + k] = g1;
+    }
+}
+
 // Windows and scratch of the iteration, one set per device, serialised on the device by the event scheme of lws_stft.hip.  The
 // windows stay on the device between calls: a call with the windows of the previous one uploads nothing.
 struct GlaCtx {
     Scratch frames, t, a, rows, trace, win_a, win_s;
     Scratch delta, sig;                   // MISI: the shared mixture error, and the K overlap-added signals
+    Scratch gc;                           // MISI backward: the gradient on the iterate, between the iterations
     Scratch state;                        // RTISI-LA: ring and frames of the workgroups whose state does not fit in LDS
     std::vector<double> host_a, host_s;   // what win_a / win_s hold
     hipEvent_t last = nullptr;
@@ -1182,7 +1307,10 @@ int allow_lds_all() {
     STFT_TRY(lws::allow_dynamic_lds<&k_gla_inverse>(bytes));
     STFT_TRY(lws::allow_dynamic_lds<&k_gla_forward<true>>(bytes));
     STFT_TRY(lws::allow_dynamic_lds<&k_gla_forward<false>>(bytes));
-    STFT_TRY(lws::allow_dynamic_lds<&k_misi_forward>(bytes));
+    STFT_TRY(lws::allow_dynamic_lds<&k_misi_forward<false>>(bytes));
+    STFT_TRY(lws::allow_dynamic_lds<&k_misi_forward<true>>(bytes));
+    STFT_TRY(lws::allow_dynamic_lds<&k_misi_bwd_project>(bytes));
+    STFT_TRY(lws::allow_dynamic_lds<&k_misi_bwd_frames>(bytes));
     return LWS_OK;
 }
 
@@ -1249,14 +1377,18 @@ extern "C" int lws_griffin_lim_dev(int device, void *C_dev, const float *A_dev, 
     return ctx_leave(c, s);
 }
 
-extern "C" int lws_misi_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, int B, int K, int M, int N, int fshift,
-                            const double *awin, const double *swin, int perfectrec, int iters, float *x_dev, double *trace,
-                            void *stream) {
+namespace {
+
+// lws_misi_dev, and with a tape (taped) lws_misi_tape_dev: the same launches, the forward one writing X as well
+int misi_run(int device, void *C_dev, const float *A_dev, const float *y_dev, int B, int K, int M, int N, int fshift,
+             const double *awin, const double *swin, int perfectrec, int iters, float *x_dev, double *trace, float2 *tape, bool taped,
+             void *stream) {
     int rc = check_shape(device, B, M, N, fshift);
     if (rc) return rc;
     if (K < 1) return lws::set_error(LWS_ERR_INVALID, "%d sources", K);
     if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
     if (!C_dev || !y_dev || !awin || !swin) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    if (taped && (!A_dev || (iters > 0 && !tape))) return lws::set_error(LWS_ERR_INVALID, "null magnitudes or tape");
     if ((long long)B * K > 65535) return lws::set_error(LWS_ERR_UNSUPPORTED, "%d x %d spectrograms in one call (at most 65535)", B, K);
     const int len = lws_istft_length(M, N, fshift, perfectrec);
     if (len < 1) return lws::set_error(LWS_ERR_INVALID, "%d frames leave no samples", M);
@@ -1302,7 +1434,12 @@ extern "C" int lws_misi_dev(int device, void *C_dev, const float *A_dev, const f
             hipLaunchKernelGGL(k_misi_residual<false>, rgrid, dim3(256), 0, s, frames, y_dev, delta, sig, static_cast<double *>(nullptr), K,
                                M, N, fshift, zero_lo, zero_hi);
         }
-        hipLaunchKernelGGL(k_misi_forward, grid, dim3(FFT_THREADS), lds, s, sig, delta, wa, C, A_dev, K, M, N, fc.odd, fc.log2e, fshift);
+        if (taped)
+            hipLaunchKernelGGL(k_misi_forward<true>, grid, dim3(FFT_THREADS), lds, s, sig, delta, wa, C, A_dev, K, M, N, fc.odd, fc.log2e,
+                               fshift, tape + (size_t)(i - 1) * bins);
+        else
+            hipLaunchKernelGGL(k_misi_forward<false>, grid, dim3(FFT_THREADS), lds, s, sig, delta, wa, C, A_dev, K, M, N, fc.odd, fc.log2e,
+                               fshift, static_cast<float2 *>(nullptr));
     }
     if (x_dev) {   // the signals of the final iterate, with their own residual shared out
         hipLaunchKernelGGL(k_gla_inverse, grid, dim3(FFT_THREADS), lds, s, C, frames, ws, M, N, fc.odd, fc.log2e);
@@ -1315,6 +1452,76 @@ extern "C" int lws_misi_dev(int device, void *C_dev, const float *A_dev, const f
         STFT_TRY(hipMemcpyAsync(trace, c.trace.p, (size_t)iters * B * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
         STFT_TRY(hipStreamSynchronize(s));
     }
+    return ctx_leave(c, s);
+}
+
+}  // namespace
+
+extern "C" int lws_misi_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, int B, int K, int M, int N, int fshift,
+                            const double *awin, const double *swin, int perfectrec, int iters, float *x_dev, double *trace,
+                            void *stream) {
+    return misi_run(device, C_dev, A_dev, y_dev, B, K, M, N, fshift, awin, swin, perfectrec, iters, x_dev, trace, nullptr, false, stream);
+}
+
+extern "C" int lws_misi_tape_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, int B, int K, int M, int N, int fshift,
+                                 const double *awin, const double *swin, int perfectrec, int iters, float *x_dev, void *tape_dev,
+                                 void *stream) {
+    return misi_run(device, C_dev, A_dev, y_dev, B, K, M, N, fshift, awin, swin, perfectrec, iters, x_dev, nullptr,
+                    static_cast<float2 *>(tape_dev), true, stream);
+}
+
+extern "C" int lws_misi_backward_dev(int device, const void *gC_dev, const float *gx_dev, const float *A_dev, const void *tape_dev, int B,
+                                     int K, int M, int N, int fshift, const double *awin, const double *swin, int perfectrec, int iters,
+                                     float *gA_out, void *gS_out, float *gy_out, void *stream) {
+    int rc = check_shape(device, B, M, N, fshift);
+    if (rc) return rc;
+    if (K < 1) return lws::set_error(LWS_ERR_INVALID, "%d sources", K);
+    if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
+    if (!A_dev || !gA_out || !awin || !swin || (iters > 0 && !tape_dev)) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    if ((long long)B * K > 65535) return lws::set_error(LWS_ERR_UNSUPPORTED, "%d x %d spectrograms in one call (at most 65535)", B, K);
+    const int len = lws_istft_length(M, N, fshift, perfectrec);
+    if (len < 1) return lws::set_error(LWS_ERR_INVALID, "%d frames leave no samples", M);
+    if (iters > 0 && (rc = check_round_trip(M, N, fshift, perfectrec))) return rc;
+    if (B == 0) return LWS_OK;
+    STFT_TRY(hipSetDevice(device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> lk(g_mu);
+    GlaCtx &c = g_ctx[device];
+    if ((rc = ctx_enter(c, s))) return rc;
+    if ((rc = allow_lds_all())) return rc;
+    if ((rc = upload_window(c.win_a, c.host_a, awin, N, s))) return rc;
+    if ((rc = upload_window(c.win_s, c.host_s, swin, N, s))) return rc;
+    const int F = N / 2 + 1, BK = B * K, Tfull = fshift * (M - 1) + N, nblk = (Tfull + 255) / 256;
+    const size_t bins = (size_t)BK * M * F;
+    if (iters > 0 && (rc = c.frames.ensure((size_t)BK * M * N * sizeof(float)))) return rc;
+    if ((rc = c.sig.ensure((size_t)BK * Tfull * sizeof(float)))) return rc;
+    if (iters > 0 && (rc = c.gc.ensure(bins * sizeof(float2)))) return rc;
+    float *frames = static_cast<float *>(c.frames.p), *gsig = static_cast<float *>(c.sig.p);
+    float2 *gc = static_cast<float2 *>(c.gc.p), *gS = static_cast<float2 *>(gS_out);
+    const float2 *gC = static_cast<const float2 *>(gC_dev), *tape = static_cast<const float2 *>(tape_dev);
+    const float *wa = static_cast<const float *>(c.win_a.p), *ws = static_cast<const float *>(c.win_s.p);
+    const Factors fc = factor(N);
+    const dim3 grid((M + 1) / 2, BK), rgrid(nblk, B);
+    const size_t lds = fft_lds_bytes(N);
+    const int zero_lo = perfectrec ? prepad(N, fshift) : 0, zero_hi = perfectrec ? N - fshift : 0;   // as in lws_griffin_lim_dev
+    if (iters == 0) STFT_TRY(hipMemsetAsync(gA_out, 0, bins * sizeof(float), s));
+    // the gradient on c_i, i = iters .. 0: from the cotangents on entry, through one iteration each after that; the one on c_0 is
+    // the result for the start and goes to the caller (or nowhere)
+    for (int i = iters; i >= 0; --i) {
+        const bool entry = i == iters;
+        if (!entry)
+            hipLaunchKernelGGL(k_misi_bwd_project, grid, dim3(FFT_THREADS), lds, s, gc, tape + (size_t)i * bins, A_dev, gA_out, frames,
+                               wa, M, N, fc.odd, fc.log2e, i + 1 == iters ? 1 : 0);
+        if (i == 0 && !gS && !gy_out) break;
+        if (entry)
+            hipLaunchKernelGGL(k_misi_bwd_share<true>, rgrid, dim3(256), 0, s, gx_dev, gsig, gy_out, K, M, N, fshift, zero_lo, zero_hi, 1);
+        else
+            hipLaunchKernelGGL(k_misi_bwd_share<false>, rgrid, dim3(256), 0, s, frames, gsig, gy_out, K, M, N, fshift, zero_lo, zero_hi, 0);
+        if (i == 0 && !gS) break;
+        hipLaunchKernelGGL(k_misi_bwd_frames, grid, dim3(FFT_THREADS), lds, s, gsig, ws, entry ? gC : static_cast<const float2 *>(nullptr),
+                           i == 0 ? gS : gc, M, N, fc.odd, fc.log2e, fshift);
+    }
+    STFT_TRY(hipGetLastError());
     return ctx_leave(c, s);
 }
 

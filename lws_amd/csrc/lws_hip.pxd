@@ -55,6 +55,12 @@ cdef extern from "lws_hip.h" nogil:
                             const double *swin, int perfectrec, int iters, double alpha, double *trace, void *stream)
     int lws_misi_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, int B, int K, int M, int N, int fshift,
                      const double *awin, const double *swin, int perfectrec, int iters, float *x_dev, double *trace, void *stream)
+    int lws_misi_tape_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, int B, int K, int M, int N, int fshift,
+                          const double *awin, const double *swin, int perfectrec, int iters, float *x_dev, void *tape_dev,
+                          void *stream)
+    int lws_misi_backward_dev(int device, const void *gC_dev, const float *gx_dev, const float *A_dev, const void *tape_dev, int B,
+                              int K, int M, int N, int fshift, const double *awin, const double *swin, int perfectrec, int iters,
+                              float *gA_out, void *gS_out, float *gy_out, void *stream)
     int lws_rtisi_la_dev(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift,
                          const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream)
     int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, float *x_dev, int B, int K, int M, int N,

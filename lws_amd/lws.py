@@ -381,6 +381,234 @@ def misi_dev(S, mixture, fsize, fshift, awin, swin, iterations, magnitudes=None,
 
 
 # --------------------------------------------------------------------------------------------
+# Training through MISI (unfolded MISI, Wang, Le Roux & Hershey 2018): the gradient of a loss on misi()'s results, host fp64
+# definition and device form.  Complex gradients are g = dL/dRe + j dL/dIm (torch's convention), so that dL = Re sum conj(g) dz.
+# --------------------------------------------------------------------------------------------
+def _misi_cuts(T, fsize, fshift, perfectrec):
+    """(Tfull, lo, hi): istft returns the samples lo..hi of the uncut timeline of Tfull = fshift (T - 1) + fsize samples."""
+    full = fshift * (T - 1) + fsize
+    if perfectrec is True:
+        return full, _perfectrec_prepad(fsize, fshift), full - (fsize - fshift)
+    return full, 0, full
+
+
+def _misi_istft_adjoint(gx, T, fsize, fshift, swin, perfectrec):
+    """The gradient on c, (T, F), of a loss whose gradient on istft(c; swin) is gx: (w / N) stft(gx; window swin) with w = 2 on the
+    interior bins and 1 at the bins 0 and N/2, whose imaginary parts istft never reads (zero).  gx sits where istft cut it from."""
+    full, lo, hi = _misi_cuts(T, fsize, fshift, perfectrec)
+    x = np.zeros(full)
+    x[lo:hi] = gx
+    idx = fshift * np.arange(T)[:, None] + np.arange(fsize)[None, :]
+    g = np.fft.fft(x[idx] * np.asarray(swin, dtype=np.float64)[None, :], axis=1)[:, : fsize // 2 + 1] * (2.0 / fsize)
+    g[:, 0] = 0.5 * g[:, 0].real
+    g[:, -1] = 0.5 * g[:, -1].real
+    return g
+
+
+def _misi_stft_adjoint(gX, fsize, fshift, awin, perfectrec):
+    """The gradient on v of a loss whose gradient on stft(v; awin) is gX: N istft(G; window awin) with G = gX / 2 on the interior
+    bins and Re gX at the bins 0 and N/2; istft's cut is the adjoint of the zeros stft pads with perfectrec."""
+    G = 0.5 * np.asarray(gX, dtype=np.complex128)
+    G[:, 0] = gX[:, 0].real
+    G[:, -1] = gX[:, -1].real
+    return fsize * istft(G, fshift, np.asarray(awin, dtype=np.float64), perfectrec=perfectrec)
+
+
+def _misi_backward(tape, A, grad_out, grad_signals, fsize, fshift, awin, swin, perfectrec=False, _perturb=None):
+    """The backward pass of misi() from a tape of its projections' arguments: tape (n, B, K, T, F) the X_k of the steps 1..n, A
+    (B, K, T, F), and the cotangents grad_out (B, K, T, F) complex of the returned spectrograms and grad_signals (B, K, len) of
+    the signals, either None for zeros.  Returns (gA, gS, gy); see misi_grad, which records the tape and calls this."""
+    tape, A = np.asarray(tape, dtype=np.complex128), np.asarray(A, dtype=np.float64)
+    B, K, T, F = A.shape
+    n = tape.shape[0]
+    _, lo, hi = _misi_cuts(T, fsize, fshift, perfectrec)
+    length = hi - lo
+    gA, gS, gy = np.zeros(A.shape), np.zeros(A.shape, dtype=np.complex128), np.zeros((B, length))
+
+    def share_back(gv, b):              # step 1: v_k = x_k + (y - sum_j x_j) / K
+        m = gv[0].copy()
+        for k in range(1, K):
+            m += gv[k]
+        m /= K
+        gy[b] += m
+        return gv - m
+
+    def frames_back(gsig, i, b):        # step 2, for the K sources
+        gc = np.stack([_misi_istft_adjoint(gsig[k], T, fsize, fshift, swin, perfectrec) for k in range(K)])
+        if _perturb is not None:
+            gc = np.stack([_perturb('gc', i, b, k, gc[k]) for k in range(K)])
+        return gc
+
+    for b in range(B):
+        gv = np.zeros((K, length)) if grad_signals is None else np.array(grad_signals[b], dtype=np.float64)
+        gc = frames_back(share_back(gv, b), n, b)
+        if grad_out is not None:
+            gc = gc + np.asarray(grad_out[b], dtype=np.complex128)
+        for i in range(n, 0, -1):
+            gv = np.empty((K, length))
+            for k in range(K):
+                X = tape[i - 1, b, k]
+                mag = np.abs(X)
+                u = np.where(mag > 0, X / np.where(mag > 0, mag, 1.0), 1.0 + 0j)      # step 3
+                q = np.conj(u) * gc[k]
+                gA[b, k] += q.real
+                gX = np.where(mag > 0, 1j * u * (A[b, k] / np.where(mag > 0, mag, 1.0)) * q.imag, 0j)
+                v = _misi_stft_adjoint(gX, fsize, fshift, awin, perfectrec)            # step 4
+                gv[k] = v if _perturb is None else np.real(_perturb('gv', i, b, k, v))
+            gc = frames_back(share_back(gv, b), i - 1, b)
+        gS[b] = gc
+    return gA, gS, gy
+
+
+def misi_grad(S, mixture, fsize, fshift, awin, swin, iterations, magnitudes, grad_out=None, grad_signals=None, perfectrec=False,
+              _perturb=None, _tape=None):
+    """The gradient of a loss L on the results of misi(S, mixture, ..., magnitudes=A, return_signals=True), in fp64 on the host:
+    the definition the device backward pass (misi_layer) is held to.  grad_out: the cotangent dL/dRe + j dL/dIm of the returned
+    spectrograms, shaped as S; grad_signals: that of the signals, (K, len) / (B, K, len); either None for zeros.  Returns
+    (gA, gS, gy), the gradients on the magnitudes (real), on the start S (complex, same convention) and on the mixture, shaped as
+    their arguments.  A is a variable of its own here: `magnitudes` is required.
+
+    Backward through step i = n..1 of misi(), gc being the gradient on c_i and X the argument of that step's projection:
+      3. u = X / |X|, q = conj(u) gc;  gA += Re q;  gX = j u (A / |X|) Im q   (where |X| == 0 the forward gives A + 0j: u = 1, gX = 0)
+      4. gv_k = N istft(G; window awin), G = gX / 2 on the interior bins and Re gX at the bins 0 and N/2
+      1. m = mean_k gv_k (k ascending);  gsig_k = gv_k - m;  gy += m   (the perfectrec cuts carry no gradient)
+      2. gc_k = (w / N) stft(gsig_k; window swin), w = 2 on the interior bins, 1 and no imaginary part at the bins 0 and N/2
+    and on entry gc = (1 and 2 applied to grad_signals) + grad_out; the gc left at the end is gS.  Zero iterations: gA = 0.
+    (_perturb(kind, i, b, k, Z) -> Z: replaces each projection argument, kind 'X', step i; each result of 2, kind 'gc', the
+    gradient on c_i; each result of 4, kind 'gv', step i, of which the real part is taken.  The error model of the tests.
+    _tape: (n, K, T, F) / (n, B, K, T, F), the X of every step from elsewhere -- a device run's -- instead of this function's own
+    forward pass: the backward pass alone, teacher-forced.)"""
+    n, _ = _gla_args(iterations, 0.0)
+    S = np.asarray(S)
+    if S.ndim not in (3, 4):
+        raise ValueError('expected (K, T, F) spectrograms of the sources or a (B, K, T, F) stack')
+    if magnitudes is None:
+        raise ValueError('misi_grad differentiates with respect to the magnitudes: give them')
+    A = np.asarray(magnitudes, dtype=np.float64)
+    if A.shape != S.shape:
+        raise ValueError('magnitudes of shape %s for spectrograms of shape %s' % (A.shape, S.shape))
+    single = S.ndim == 3
+    S4, A4 = (S[None], A[None]) if single else (S, A)
+    y = np.asarray(mixture, dtype=np.float64)
+    B, K, T, F = S4.shape
+    tape = np.empty((n,) + S4.shape, dtype=np.complex128)
+
+    def record(i, b, k, X):
+        if _perturb is not None:
+            X = _perturb('X', i, b, k, X)
+        tape[i - 1, b, k] = X
+        return X
+
+    if _tape is None:
+        misi(S4, y[None] if single else y, fsize, fshift, awin, swin, n, magnitudes=A4, perfectrec=perfectrec, _perturb=record)
+    else:
+        tape[...] = np.asarray(_tape).reshape(tape.shape)
+    _, lo, hi = _misi_cuts(T, fsize, fshift, perfectrec)
+    length = hi - lo
+    gC = gs = None
+    if grad_out is not None:
+        gC = np.asarray(grad_out, dtype=np.complex128)
+        if gC.shape != S.shape:
+            raise ValueError('grad_out of shape %s for spectrograms of shape %s' % (gC.shape, S.shape))
+        gC = gC[None] if single else gC
+    if grad_signals is not None:
+        gs = np.asarray(grad_signals, dtype=np.float64)
+        if gs.shape != S.shape[:-2] + (length,):
+            raise ValueError('grad_signals of shape %s: expected %s' % (gs.shape, S.shape[:-2] + (length,)))
+        gs = gs[None] if single else gs
+    gA, gS, gy = _misi_backward(tape, A4, gC, gs, fsize, fshift, awin, swin, perfectrec=perfectrec, _perturb=_perturb)
+    return (gA[0], gS[0], gy[0]) if single else (gA, gS, gy)
+
+
+_misi_function = None
+
+
+def _misi_autograd_function():
+    """The torch.autograd.Function behind misi_layer, made on first use: importing this module needs no torch."""
+    global _misi_function
+    if _misi_function is not None:
+        return _misi_function
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class MisiLayer(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, A, S, y, fsize, fshift, awin, swin, n, perfectrec):
+            dev = S.device
+            B, K, T, F = (1,) + tuple(S.shape) if S.dim() == 3 else tuple(S.shape)
+            length = _capi.istft_length(T, fsize, fshift, perfectrec)
+            A, y = A.detach().contiguous(), y.detach().contiguous()
+            C = S.detach().clone(memory_format=torch.contiguous_format)          # the iteration is in place: never on the caller's storage
+            sig = torch.empty(tuple(S.shape[:-2]) + (length,), dtype=torch.float32, device=dev)
+            tape = torch.empty((n, B, K, T, F), dtype=torch.complex64, device=dev)
+            _capi.misi_tape_dev(C.data_ptr(), A.data_ptr(), y.data_ptr(), B, K, T, fsize, fshift, awin, swin, perfectrec, n,
+                                sig.data_ptr(), tape.data_ptr() if n else None, device=dev.index,
+                                stream=torch.cuda.current_stream(dev).cuda_stream)
+            ctx.save_for_backward(A, tape)
+            ctx.set_materialize_grads(False)
+            ctx.misi = (B, K, T, fsize, fshift, awin, swin, perfectrec, n, tuple(y.shape))
+            return C, sig
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gC, gs):
+            A, tape = ctx.saved_tensors
+            B, K, T, fsize, fshift, awin, swin, perfectrec, n, y_shape = ctx.misi
+            dev = A.device
+            if gC is not None:
+                gC = gC.to(torch.complex64).contiguous()
+            if gs is not None:
+                gs = gs.to(torch.float32).contiguous()
+            gA = torch.empty_like(A)
+            gS = torch.empty(A.shape, dtype=torch.complex64, device=dev) if ctx.needs_input_grad[1] else None
+            gy = torch.empty(y_shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
+            ptr = lambda t: None if t is None else t.data_ptr()
+            _capi.misi_backward_dev(ptr(gC), ptr(gs), A.data_ptr(), tape.data_ptr() if n else None, B, K, T, fsize, fshift, awin,
+                                    swin, perfectrec, n, gA.data_ptr(), ptr(gS), ptr(gy), device=dev.index,
+                                    stream=torch.cuda.current_stream(dev).cuda_stream)
+            return (gA if ctx.needs_input_grad[0] else None, gS, gy) + (None,) * 6
+
+    _misi_function = MisiLayer
+    return MisiLayer
+
+
+def misi_layer(A, S, mixture, fsize, fshift, awin, swin, iterations, perfectrec=False):
+    """misi_dev(S, mixture, ..., magnitudes=A, return_signals=True) as a differentiable torch operation, for training through MISI:
+    returns (C, s), the spectrograms after `iterations` steps and their signals, with the bits misi_dev gives them, and
+    loss.backward() reaches whichever of A, S and mixture require grad (the others get None).  Takes device tensors, A float32
+    and S complex64 of shape (K, T, F) or (B, K, T, F), mixture float32 (len,) / (B, len); does not modify them; runs on the
+    current torch stream and only enqueues work, forward and backward.  Once differentiable.  The forward pass keeps the argument
+    of every projection for the backward pass: a complex64 tape of `iterations` times the size of S, held by the autograd graph
+    until backward() has run (or the results are dropped).  The backward pass is three launches per iteration, as the forward
+    pass (lws_gla.hip), and repeats bit for bit; its definition is misi_grad.  Zero iterations: C is a copy of S."""
+    import torch
+    n, _ = _gla_args(iterations, 0.0)
+    for name, t, dtype in (('A', A, torch.float32), ('S', S, torch.complex64), ('mixture', mixture, torch.float32)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+            raise ValueError('%s must be a %s torch tensor on the device' % (name, str(dtype).replace('torch.', '')))
+    if S.dim() not in (3, 4):
+        raise ValueError('expected (K, T, F) spectrograms of the sources or a (B, K, T, F) stack')
+    if A.shape != S.shape:
+        raise ValueError('magnitudes of shape %s for spectrograms of shape %s' % (tuple(A.shape), tuple(S.shape)))
+    if A.device != S.device or mixture.device != S.device:
+        raise ValueError('A, S and mixture must be on one device')
+    K, T, F = S.shape[-3:]
+    if K < 1:
+        raise ValueError('no sources')
+    if F != fsize // 2 + 1:
+        raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
+    length = _capi.istft_length(T, fsize, fshift, perfectrec)
+    if tuple(mixture.shape) != tuple(S.shape[:-3]) + (length,):
+        raise ValueError('mixture of shape %s for %s spectrograms of %d frames: expected %s' %
+                         (tuple(mixture.shape), tuple(S.shape[:-2]), T, tuple(S.shape[:-3]) + (length,)))
+    if n > 0 and _capi.stft_frames(length, fsize, fshift, perfectrec) != T:
+        raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' %
+                         (T, _capi.stft_frames(length, fsize, fshift, perfectrec)))
+    awin, swin = np.array(awin, dtype=np.float64), np.array(swin, dtype=np.float64)
+    return _misi_autograd_function().apply(A, S, mixture, int(fsize), int(fshift), awin, swin, n, bool(perfectrec))
+
+
+# --------------------------------------------------------------------------------------------
 # RTISI-LA (Zhu, Beauregard & Wyse 2007): Griffin-Lim under a look-ahead -- what online LWS approximates, as batch LWS does Griffin-Lim
 # --------------------------------------------------------------------------------------------
 def _look_ahead_arg(look_ahead):
@@ -1242,6 +1470,15 @@ class lws(object):
         """Device form: a new complex64 torch tensor, see the module's misi_dev."""
         return misi_dev(S, mixture, self.fsize, self.fshift, self.awin, self.swin, iterations, magnitudes=magnitudes,
                         perfectrec=self.perfectrec, return_trace=return_trace, return_signals=return_signals, device=self.device)
+
+    def misi_grad(self, S, mixture, iterations, magnitudes, grad_out=None, grad_signals=None):
+        """Host fp64 gradient through misi with this object's windows and perfectrec: (gA, gS, gy), see the module's misi_grad."""
+        return misi_grad(S, mixture, self.fsize, self.fshift, self.awin, self.swin, iterations, magnitudes, grad_out=grad_out,
+                         grad_signals=grad_signals, perfectrec=self.perfectrec)
+
+    def misi_layer(self, A, S, mixture, iterations):
+        """misi_dev as a differentiable torch operation on device tensors: (C, s), see the module's misi_layer."""
+        return misi_layer(A, S, mixture, self.fsize, self.fshift, self.awin, self.swin, iterations, perfectrec=self.perfectrec)
 
     def rtisi_la(self, S, iterations, look_ahead=None, magnitudes=None, return_signal=False, open_end=False, start='given'):
         """Host fp64 form with this object's windows, perfectrec and (look_ahead=None) look-ahead: see the module's rtisi_la."""
