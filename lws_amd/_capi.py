@@ -584,35 +584,43 @@ def misi_la_dev(C_ptr, A_ptr, y_ptr, x_ptr, B, K, frames, fsize, fshift, awin, s
                                         stream))
 
 
-def rtisi_stream_create(B, fsize, fshift, awin, swin, perfectrec, iterations, look_ahead, device=0, start="given"):
-    """A handle (c_void_p) for B RTISI-LA streams; free it with rtisi_stream_destroy.  start: 'given' or 'overlap'."""
-    code = start_code(start, ("given", "overlap"))
+def _stream_create(name, lead, fsize, fshift, awin, swin, perfectrec, iterations, look_ahead, device, start, other):
+    """lws_<name>_create, or under a start other than 'given' lws_<name>_create_ex; lead: the counts in front of fsize."""
+    code = start_code(start, ("given", other))
     a, w = _win(awin), _win(swin)
     if a.shape != (int(fsize),) or w.shape != (int(fsize),):
         raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
     h = C.c_void_p()
+    args = [int(device)] + [int(v) for v in lead] + [int(fsize), int(fshift), a.ctypes.data, w.ctypes.data, int(bool(perfectrec)),
+                                                     int(iterations), int(look_ahead)]
     if code == LWS_START_GIVEN:
-        check(load().lws_rtisi_stream_create(int(device), int(B), int(fsize), int(fshift), a.ctypes.data, w.ctypes.data,
-                                             int(bool(perfectrec)), int(iterations), int(look_ahead), C.byref(h)))
+        check(getattr(load(), "lws_%s_create" % name)(*args, C.byref(h)))
     else:
-        check(load().lws_rtisi_stream_create_ex(int(device), int(B), int(fsize), int(fshift), a.ctypes.data, w.ctypes.data,
-                                                int(bool(perfectrec)), int(iterations), int(look_ahead), code, C.byref(h)))
+        check(getattr(load(), "lws_%s_create_ex" % name)(*args, code, C.byref(h)))
     return h
+
+
+def _stream_call(fn, h, *args, stream=None):
+    """A push or finish: (rows, samples) committed per stream."""
+    nf, ns = C.c_int(0), C.c_int(0)
+    check(fn(h, *args, C.byref(nf), C.byref(ns), stream))
+    return nf.value, ns.value
+
+
+def rtisi_stream_create(B, fsize, fshift, awin, swin, perfectrec, iterations, look_ahead, device=0, start="given"):
+    """A handle (c_void_p) for B RTISI-LA streams; free it with rtisi_stream_destroy.  start: 'given' or 'overlap'."""
+    return _stream_create("rtisi_stream", (B,), fsize, fshift, awin, swin, perfectrec, iterations, look_ahead, device, start, "overlap")
 
 
 def rtisi_stream_push(h, S_ptr, A_ptr, frames, C_out_ptr, x_out_ptr, stream=None):
     """The next `frames` rows of every stream (device complex64 [B][frames][F]; A_ptr: device float32 or None).  Returns (rows,
     samples) committed per stream, written to C_out_ptr [B][frames][F] and x_out_ptr [B][frames*fshift] (or None).  Only enqueues."""
-    nf, ns = C.c_int(0), C.c_int(0)
-    check(load().lws_rtisi_stream_push(h, S_ptr, A_ptr, int(frames), C_out_ptr, x_out_ptr, C.byref(nf), C.byref(ns), stream))
-    return nf.value, ns.value
+    return _stream_call(load().lws_rtisi_stream_push, h, S_ptr, A_ptr, int(frames), C_out_ptr, x_out_ptr, stream=stream)
 
 
 def rtisi_stream_finish(h, C_out_ptr, x_out_ptr, stream=None):
     """Commits what is left: C_out_ptr [B][look_ahead][F], x_out_ptr [B][fsize + look_ahead*fshift] (or None).  Returns (rows, samples)."""
-    nf, ns = C.c_int(0), C.c_int(0)
-    check(load().lws_rtisi_stream_finish(h, C_out_ptr, x_out_ptr, C.byref(nf), C.byref(ns), stream))
-    return nf.value, ns.value
+    return _stream_call(load().lws_rtisi_stream_finish, h, C_out_ptr, x_out_ptr, stream=stream)
 
 
 def rtisi_stream_destroy(h):
@@ -622,36 +630,21 @@ def rtisi_stream_destroy(h):
 def misi_stream_create(B, K, fsize, fshift, awin, swin, perfectrec, iterations, look_ahead, device=0, start="given"):
     """A handle (c_void_p) for B online-MISI streams of K sources each; free it with misi_stream_destroy.  start: 'given' or
     'mixture'."""
-    code = start_code(start, ("given", "mixture"))
-    a, w = _win(awin), _win(swin)
-    if a.shape != (int(fsize),) or w.shape != (int(fsize),):
-        raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
-    h = C.c_void_p()
-    if code == LWS_START_GIVEN:
-        check(load().lws_misi_stream_create(int(device), int(B), int(K), int(fsize), int(fshift), a.ctypes.data, w.ctypes.data,
-                                            int(bool(perfectrec)), int(iterations), int(look_ahead), C.byref(h)))
-    else:
-        check(load().lws_misi_stream_create_ex(int(device), int(B), int(K), int(fsize), int(fshift), a.ctypes.data, w.ctypes.data,
-                                               int(bool(perfectrec)), int(iterations), int(look_ahead), code, C.byref(h)))
-    return h
+    return _stream_create("misi_stream", (B, K), fsize, fshift, awin, swin, perfectrec, iterations, look_ahead, device, start, "mixture")
 
 
 def misi_stream_push(h, S_ptr, A_ptr, y_ptr, frames, samples, C_out_ptr, x_out_ptr, stream=None):
     """The next `frames` rows of every source (device complex64 [B][K][frames][F]; A_ptr: device float32 or None) and the next
     `samples` mixture samples (device float32 [B][samples]).  Returns (rows, samples) committed per source, written to C_out_ptr
     [B][K][frames][F] and x_out_ptr [B][K][frames*fshift] (or None).  Only enqueues."""
-    nf, ns = C.c_int(0), C.c_int(0)
-    check(load().lws_misi_stream_push(h, S_ptr, A_ptr, y_ptr, int(frames), int(samples), C_out_ptr, x_out_ptr, C.byref(nf), C.byref(ns),
-                                      stream))
-    return nf.value, ns.value
+    return _stream_call(load().lws_misi_stream_push, h, S_ptr, A_ptr, y_ptr, int(frames), int(samples), C_out_ptr, x_out_ptr,
+                        stream=stream)
 
 
 def misi_stream_finish(h, C_out_ptr, x_out_ptr, stream=None):
     """Commits what is left: C_out_ptr [B][K][look_ahead][F], x_out_ptr [B][K][fsize + look_ahead*fshift] (or None).  Returns (rows,
     samples)."""
-    nf, ns = C.c_int(0), C.c_int(0)
-    check(load().lws_misi_stream_finish(h, C_out_ptr, x_out_ptr, C.byref(nf), C.byref(ns), stream))
-    return nf.value, ns.value
+    return _stream_call(load().lws_misi_stream_finish, h, C_out_ptr, x_out_ptr, stream=stream)
 
 
 def misi_stream_destroy(h):

@@ -6,6 +6,7 @@
 
 #include "../../include/lws_hip.h"
 #include "lws_common.h"
+#include "lws_la_stream.h"   // Factors, factor, prepad: plain C++, shared with the CPU tests
 
 namespace {
 
@@ -100,9 +101,6 @@ struct Scratch {
     }
 };
 
-// N = odd * 2^log2e
-struct Factors { int odd, log2e; };
-Factors factor(int n) { Factors f{n, 0}; while (!(f.odd & 1)) { f.odd >>= 1; ++f.log2e; } return f; }
 size_t fft_lds_bytes(int N) { return (size_t)(factor(N).odd > 1 ? 3 : 2) * N * sizeof(float2); }
 
 constexpr int MAX_DEVICES = 64;
@@ -113,7 +111,6 @@ int check_shape(int device, int B, int M, int N, int hop, int min_frames = 1) {
     if (hop < 1 || hop > N) return lws::set_error(LWS_ERR_INVALID, "frame shift %d", hop);
     return LWS_OK;
 }
-int prepad(int N, int hop) { const int r = N % hop; return r == 0 ? N - hop : N - r; }   // lws.pyx:55-60
 
 // stft(istft(.)) of M frames must give M frames again for the round trip to be a projection: with perfectrec the cuts of
 // lws.pyx:130-137 leave too little of fewer than about N / hop frames (and nothing at all of hop == N)

@@ -10,6 +10,11 @@
 //                   X_m[k] = (Z[k] + conj Z[N-k]) / 2, X_{m+1}[k] = (Z[k] - conj Z[N-k]) / 2j, and in its epilogue reads
 //                   c, A, t_prev and writes t, c and the per-frame fp64 sums (|c|^2, |X - c|^2) of the consistency pair.
 // An odd last frame pairs with zeros.  The iterate lives in the caller's buffer; the last iteration leaves t_n there.
+//
+// The file: the kernels first -- Griffin-Lim, MISI, RTISI-LA (k_rtisi), online MISI (k_misi_la), their streaming forms and the MISI
+// backward pass, each with its own comment -- then the host half.  The one-shot calls check their arguments and open the same way
+// (GlaCall); the two stream handles are one struct whose every decision is made by the step clock of lws_la_stream.h, plain C++
+// that the CPU tests drive without a device.
 #include "../../include/lws_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -405,7 +410,7 @@ struct MisiLaArgs {
 };
 
 // The bins k = threadIdx.x + i blockDim.x of one frame that a thread holds in registers: F <= blockDim.x up to N = 1024, and
-// blockDim.x = RTISI_MAX_THREADS above (rtisi_plan)
+// blockDim.x = RTISI_MAX_THREADS above (la_placement)
 constexpr int RTISI_BINS = (MAXN / 2 + 1 + RTISI_MAX_THREADS - 1) / RTISI_MAX_THREADS;
 
 // the unit phasor rtisi_project scales: (1, 0) where X == 0
@@ -634,17 +639,7 @@ struct RtisiHeld {
     const float *A;      // [B][rows][F]: magnitudes of the held frames
     float2 *S_next;      // where the rows of the frames still active after this launch go (null: not kept)
     float *A_next;
-};
-struct RtisiStreamArgs {
-    int N, odd, log2e, hop, LA, iters;
-    int nsteps, Mrel;            // steps of this launch; frames from its first step to the end of the stream (nsteps + LA while open)
-    int closing, origin;         // the launch that ends the stream; the first step is frame 0 of the stream
-    int zero_lo, emit_end;       // the lead-in cut and the end of the emitted samples, from the first sample of the first step
-    int base, slot_m, cur;       // ring offset and slot of the first step's frame; which frame buffer is fcur (scratch placement)
-    int nheld, held_rows;        // held frames in front of the chunk's; row stride of a stream in the held buffers
-    int chunk_rows, out_rows, out_samples;   // rows per stream of S / A, of Cout, samples per stream of xout
-    size_t state_floats;         // stride of a stream in `state`
-};
+};   // the launch's other arguments: RtisiStreamArgs of lws_la_stream.h
 
 template <class T> __device__ __forceinline__ const T *rtisi_row(const T *held, const T *chunk, int j, int nheld, int F) {
     return j < nheld ? held + (size_t)j * F : chunk + (size_t)(j - nheld) * F;
@@ -832,13 +827,7 @@ struct MisiStreamHeld {
     float2 *S_next;
     float *A_next;
     float *y_next;       // where the samples still under the active frames after this launch go (null: not kept)
-};
-struct MisiStreamArgs {
-    RtisiStreamArgs r;   // r.state_floats: stride of ONE source in `state`; the rows are [B][K][rows][F], the samples [B][K][samples]
-    int K, frame0;       // sources; the stream's first frame, counted from the first step's (clamped: no earlier frame covers sample 0)
-    int ny_held, ny_chunk, y_rows, y_keep;   // mixture samples held / in the chunk, per-stream stride of held.y, samples to keep
-    size_t stream_floats;                    // stride of a stream in `state`
-};
+};   // the launch's other arguments: MisiStreamArgs of lws_la_stream.h
 
 __device__ __forceinline__ float misi_stream_y(const float *held, const float *chunk, int t, int ny_held, int ny_chunk) {
     if (t < ny_held) return held[t];
@@ -1264,8 +1253,8 @@ __global__ void __launch_bounds__(FFT_THREADS) k_misi_bwd_frames(const float *gs
     }
 }
 
-// Windows and scratch of the iteration, one set per device, serialised on the device by the event scheme of lws_stft.hip.  The
-// windows stay on the device between calls: a call with the windows of the previous one uploads nothing.
+// ---- The host half.  Windows and scratch of the iteration, one set per device, serialised on the device by the event scheme of
+// lws_stft.hip.  The windows stay on the device between calls: a call with the windows of the previous one uploads nothing.
 struct GlaCtx {
     Scratch frames, t, a, rows, trace, win_a, win_s;
     Scratch delta, sig;                   // MISI: the shared mixture error, and the K overlap-added signals
@@ -1302,17 +1291,73 @@ int upload_window(Scratch &dst, std::vector<double> &held, const double *w, int 
     return LWS_OK;
 }
 
+// Every kernel of this file that takes dynamic LDS, and how much it may ask for: the transform buffers, or (a look-ahead kernel with
+// its state in LDS) all a workgroup can have.
+constexpr size_t RTISI_LDS_CAP = 160 * 1024;
+struct LdsOptIn {
+    hipError_t (*allow)(int);
+    int bytes;
+};
+#define LA_OPT_IN(kernel, start)                                                \
+    {&lws::allow_dynamic_lds<&kernel<true, start>>, (int)RTISI_LDS_CAP},        \
+    {&lws::allow_dynamic_lds<&kernel<false, start>>, 3 * MAXN * (int)sizeof(float2)}
+#define FFT_OPT_IN(...) {&lws::allow_dynamic_lds<&__VA_ARGS__>, 3 * MAXN * (int)sizeof(float2)}
+const LdsOptIn LDS_OPT_INS[] = {
+    FFT_OPT_IN(k_gla_inverse), FFT_OPT_IN(k_gla_forward<true>), FFT_OPT_IN(k_gla_forward<false>), FFT_OPT_IN(k_misi_forward<false>),
+    FFT_OPT_IN(k_misi_forward<true>), FFT_OPT_IN(k_misi_bwd_project), FFT_OPT_IN(k_misi_bwd_frames),
+    LA_OPT_IN(k_rtisi, LWS_START_GIVEN), LA_OPT_IN(k_rtisi, LWS_START_OVERLAP),
+    LA_OPT_IN(k_misi_la, LWS_START_GIVEN), LA_OPT_IN(k_misi_la, LWS_START_MIXTURE),
+    LA_OPT_IN(k_rtisi_stream, LWS_START_GIVEN), LA_OPT_IN(k_rtisi_stream, LWS_START_OVERLAP),
+    LA_OPT_IN(k_misi_la_stream, LWS_START_GIVEN), LA_OPT_IN(k_misi_la_stream, LWS_START_MIXTURE),
+};
+#undef LA_OPT_IN
+#undef FFT_OPT_IN
 int allow_lds_all() {
-    const int bytes = 3 * MAXN * (int)sizeof(float2);
-    STFT_TRY(lws::allow_dynamic_lds<&k_gla_inverse>(bytes));
-    STFT_TRY(lws::allow_dynamic_lds<&k_gla_forward<true>>(bytes));
-    STFT_TRY(lws::allow_dynamic_lds<&k_gla_forward<false>>(bytes));
-    STFT_TRY(lws::allow_dynamic_lds<&k_misi_forward<false>>(bytes));
-    STFT_TRY(lws::allow_dynamic_lds<&k_misi_forward<true>>(bytes));
-    STFT_TRY(lws::allow_dynamic_lds<&k_misi_bwd_project>(bytes));
-    STFT_TRY(lws::allow_dynamic_lds<&k_misi_bwd_frames>(bytes));
+    for (const LdsOptIn &k : LDS_OPT_INS) STFT_TRY(k.allow(k.bytes));
     return LWS_OK;
 }
+
+// The magnitudes of a call: those given, or those of the rows, by k_gla_abs into `scratch`.
+int magnitudes(const float *&A, const float2 *rows, size_t bins, Scratch &scratch, hipStream_t s) {
+    if (A) return LWS_OK;
+    int rc = scratch.ensure(bins * sizeof(float));
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_gla_abs, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, s, rows, static_cast<float *>(scratch.p), bins);
+    A = static_cast<const float *>(scratch.p);
+    return LWS_OK;
+}
+
+// What the one-shot calls share once their arguments are checked: the device's context under g_mu, the LDS opt-in, both windows on
+// the device, the factors of N and the cuts of perfectrec.  open() after the checks, close() after the last launch.
+struct GlaCall {
+    std::lock_guard<std::mutex> lk{g_mu};
+    GlaCtx &c;
+    hipStream_t s;
+    const float *wa = nullptr, *ws = nullptr;
+    Factors fc{};
+    size_t lds = 0;                 // of a launch that only transforms
+    int zero_lo = 0, zero_hi = 0;   // with perfectrec the reference cuts the first prepad and the last N - hop samples and the forward
+                                    // transform pads zeros back in their place (same frame count), as in lws_consistency_dev
+    GlaCall(int device, void *stream) : c(g_ctx[device]), s(static_cast<hipStream_t>(stream)) {}
+    int open(int device, int N, int hop, const double *awin, const double *swin, int perfectrec) {
+        STFT_TRY(hipSetDevice(device));
+        int rc = ctx_enter(c, s);
+        if (!rc) rc = allow_lds_all();
+        if (!rc) rc = upload_window(c.win_a, c.host_a, awin, N, s);
+        if (!rc) rc = upload_window(c.win_s, c.host_s, swin, N, s);
+        wa = static_cast<const float *>(c.win_a.p);
+        ws = static_cast<const float *>(c.win_s.p);
+        fc = factor(N);
+        lds = fft_lds_bytes(N);
+        zero_lo = perfectrec ? prepad(N, hop) : 0;
+        zero_hi = perfectrec ? N - hop : 0;
+        return rc;
+    }
+    int close() {
+        STFT_TRY(hipGetLastError());
+        return ctx_leave(c, s);
+    }
+};
 
 }  // namespace
 
@@ -1326,47 +1371,33 @@ extern "C" int lws_griffin_lim_dev(int device, void *C_dev, const float *A_dev, 
     if (!C_dev || !awin || !swin) return lws::set_error(LWS_ERR_INVALID, "null pointer");
     if (iters > 0 && (rc = check_round_trip(M, N, fshift, perfectrec))) return rc;
     if (B == 0 || iters == 0) return LWS_OK;
-    STFT_TRY(hipSetDevice(device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    std::lock_guard<std::mutex> lk(g_mu);
-    GlaCtx &c = g_ctx[device];
-    if ((rc = ctx_enter(c, s))) return rc;
-    if ((rc = allow_lds_all())) return rc;
-    if ((rc = upload_window(c.win_a, c.host_a, awin, N, s))) return rc;
-    if ((rc = upload_window(c.win_s, c.host_s, swin, N, s))) return rc;
+    GlaCall g(device, stream);
+    if ((rc = g.open(device, N, fshift, awin, swin, perfectrec))) return rc;
+    GlaCtx &c = g.c;
+    hipStream_t s = g.s;
     const int F = N / 2 + 1;
     const size_t bins = (size_t)B * M * F;
     const bool momentum = alpha > 0.0 && iters > 2;   // the first step has none and the last leaves t_n, not c_n
     if ((rc = c.frames.ensure((size_t)B * M * N * sizeof(float)))) return rc;
     if (momentum && (rc = c.t.ensure(bins * sizeof(float2)))) return rc;
-    if (!A_dev && (rc = c.a.ensure(bins * sizeof(float)))) return rc;
     if (trace && (rc = c.rows.ensure((size_t)B * M * 2 * sizeof(double)))) return rc;
     if (trace && (rc = c.trace.ensure((size_t)iters * B * 2 * sizeof(double)))) return rc;
     float2 *C = static_cast<float2 *>(C_dev), *T = static_cast<float2 *>(c.t.p);
     float *frames = static_cast<float *>(c.frames.p);
-    const float *wa = static_cast<const float *>(c.win_a.p), *ws = static_cast<const float *>(c.win_s.p);
-    if (!A_dev) {
-        hipLaunchKernelGGL(k_gla_abs, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, s, C, static_cast<float *>(c.a.p), bins);
-        A_dev = static_cast<const float *>(c.a.p);
-    }
-    const Factors fc = factor(N);
+    if ((rc = magnitudes(A_dev, C, bins, c.a, s))) return rc;
     const dim3 grid((M + 1) / 2, B);
-    const size_t lds = fft_lds_bytes(N);
-    // with perfectrec the reference cuts the first prepad and the last N - hop samples and the forward transform pads zeros
-    // back in their place (same frame count), as in lws_consistency_dev
-    const int zero_lo = perfectrec ? prepad(N, fshift) : 0, zero_hi = perfectrec ? N - fshift : 0;
     for (int i = 1; i <= iters; ++i) {
         const GlaStep st{(momentum && i >= 2 && i < iters) ? (float)alpha : 0.f, (momentum && i + 1 < iters) ? 1 : 0};
-        hipLaunchKernelGGL(k_gla_inverse, grid, dim3(FFT_THREADS), lds, s, C, frames, ws, M, N, fc.odd, fc.log2e);
+        hipLaunchKernelGGL(k_gla_inverse, grid, dim3(FFT_THREADS), g.lds, s, C, frames, g.ws, M, N, g.fc.odd, g.fc.log2e);
         if (trace) {
             double *rows = static_cast<double *>(c.rows.p);
-            hipLaunchKernelGGL(k_gla_forward<true>, grid, dim3(FFT_THREADS), lds, s, frames, wa, C, A_dev, T, rows, M, N, fc.odd,
-                               fc.log2e, fshift, zero_lo, zero_hi, st);
+            hipLaunchKernelGGL(k_gla_forward<true>, grid, dim3(FFT_THREADS), g.lds, s, frames, g.wa, C, A_dev, T, rows, M, N, g.fc.odd,
+                               g.fc.log2e, fshift, g.zero_lo, g.zero_hi, st);
             hipLaunchKernelGGL(k_gla_sum_rows, dim3((B + 63) / 64), dim3(64), 0, s, rows,
                                static_cast<double *>(c.trace.p) + (size_t)(i - 1) * B * 2, M, B);
         } else {
-            hipLaunchKernelGGL(k_gla_forward<false>, grid, dim3(FFT_THREADS), lds, s, frames, wa, C, A_dev, T,
-                               static_cast<double *>(nullptr), M, N, fc.odd, fc.log2e, fshift, zero_lo, zero_hi, st);
+            hipLaunchKernelGGL(k_gla_forward<false>, grid, dim3(FFT_THREADS), g.lds, s, frames, g.wa, C, A_dev, T,
+                               static_cast<double *>(nullptr), M, N, g.fc.odd, g.fc.log2e, fshift, g.zero_lo, g.zero_hi, st);
         }
     }
     STFT_TRY(hipGetLastError());
@@ -1374,7 +1405,7 @@ extern "C" int lws_griffin_lim_dev(int device, void *C_dev, const float *A_dev, 
         STFT_TRY(hipMemcpyAsync(trace, c.trace.p, (size_t)iters * B * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
         STFT_TRY(hipStreamSynchronize(s));
     }
-    return ctx_leave(c, s);
+    return g.close();
 }
 
 namespace {
@@ -1394,38 +1425,27 @@ int misi_run(int device, void *C_dev, const float *A_dev, const float *y_dev, in
     if (len < 1) return lws::set_error(LWS_ERR_INVALID, "%d frames leave no samples", M);
     if (iters > 0 && (rc = check_round_trip(M, N, fshift, perfectrec))) return rc;
     if (B == 0 || (iters == 0 && !x_dev)) return LWS_OK;
-    STFT_TRY(hipSetDevice(device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    std::lock_guard<std::mutex> lk(g_mu);
-    GlaCtx &c = g_ctx[device];
-    if ((rc = ctx_enter(c, s))) return rc;
-    if ((rc = allow_lds_all())) return rc;
-    if ((rc = upload_window(c.win_a, c.host_a, awin, N, s))) return rc;
-    if ((rc = upload_window(c.win_s, c.host_s, swin, N, s))) return rc;
+    GlaCall g(device, stream);
+    if ((rc = g.open(device, N, fshift, awin, swin, perfectrec))) return rc;
+    GlaCtx &c = g.c;
+    hipStream_t s = g.s;
     const int F = N / 2 + 1, BK = B * K, Tfull = fshift * (M - 1) + N, nblk = (Tfull + 255) / 256;
     const size_t bins = (size_t)BK * M * F;
     const bool want_trace = trace && iters > 0;
     if ((rc = c.frames.ensure((size_t)BK * M * N * sizeof(float)))) return rc;
     if ((rc = c.delta.ensure((size_t)B * Tfull * sizeof(float)))) return rc;
     if ((rc = c.sig.ensure((size_t)BK * Tfull * sizeof(float)))) return rc;
-    if (!A_dev && iters > 0 && (rc = c.a.ensure(bins * sizeof(float)))) return rc;
     if (want_trace && (rc = c.rows.ensure((size_t)B * nblk * 2 * sizeof(double)))) return rc;
     if (want_trace && (rc = c.trace.ensure((size_t)iters * B * 2 * sizeof(double)))) return rc;
     float2 *C = static_cast<float2 *>(C_dev);
     float *frames = static_cast<float *>(c.frames.p), *delta = static_cast<float *>(c.delta.p);
     float *sig = static_cast<float *>(c.sig.p);
     double *rows = static_cast<double *>(c.rows.p);
-    const float *wa = static_cast<const float *>(c.win_a.p), *ws = static_cast<const float *>(c.win_s.p);
-    if (!A_dev && iters > 0) {
-        hipLaunchKernelGGL(k_gla_abs, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, s, C, static_cast<float *>(c.a.p), bins);
-        A_dev = static_cast<const float *>(c.a.p);
-    }
-    const Factors fc = factor(N);
+    if (iters > 0 && (rc = magnitudes(A_dev, C, bins, c.a, s))) return rc;
     const dim3 grid((M + 1) / 2, BK), rgrid(nblk, B);
-    const size_t lds = fft_lds_bytes(N);
-    const int zero_lo = perfectrec ? prepad(N, fshift) : 0, zero_hi = perfectrec ? N - fshift : 0;   // as in lws_griffin_lim_dev
+    const int zero_lo = g.zero_lo, zero_hi = g.zero_hi;
     for (int i = 1; i <= iters; ++i) {
-        hipLaunchKernelGGL(k_gla_inverse, grid, dim3(FFT_THREADS), lds, s, C, frames, ws, M, N, fc.odd, fc.log2e);
+        hipLaunchKernelGGL(k_gla_inverse, grid, dim3(FFT_THREADS), g.lds, s, C, frames, g.ws, M, N, g.fc.odd, g.fc.log2e);
         if (want_trace) {
             hipLaunchKernelGGL(k_misi_residual<true>, rgrid, dim3(256), 0, s, frames, y_dev, delta, sig, rows, K, M, N, fshift, zero_lo, zero_hi);
             hipLaunchKernelGGL(k_gla_sum_rows, dim3((B + 63) / 64), dim3(64), 0, s, rows,
@@ -1435,14 +1455,14 @@ int misi_run(int device, void *C_dev, const float *A_dev, const float *y_dev, in
                                M, N, fshift, zero_lo, zero_hi);
         }
         if (taped)
-            hipLaunchKernelGGL(k_misi_forward<true>, grid, dim3(FFT_THREADS), lds, s, sig, delta, wa, C, A_dev, K, M, N, fc.odd, fc.log2e,
-                               fshift, tape + (size_t)(i - 1) * bins);
+            hipLaunchKernelGGL(k_misi_forward<true>, grid, dim3(FFT_THREADS), g.lds, s, sig, delta, g.wa, C, A_dev, K, M, N, g.fc.odd,
+                               g.fc.log2e, fshift, tape + (size_t)(i - 1) * bins);
         else
-            hipLaunchKernelGGL(k_misi_forward<false>, grid, dim3(FFT_THREADS), lds, s, sig, delta, wa, C, A_dev, K, M, N, fc.odd, fc.log2e,
-                               fshift, static_cast<float2 *>(nullptr));
+            hipLaunchKernelGGL(k_misi_forward<false>, grid, dim3(FFT_THREADS), g.lds, s, sig, delta, g.wa, C, A_dev, K, M, N, g.fc.odd,
+                               g.fc.log2e, fshift, static_cast<float2 *>(nullptr));
     }
     if (x_dev) {   // the signals of the final iterate, with their own residual shared out
-        hipLaunchKernelGGL(k_gla_inverse, grid, dim3(FFT_THREADS), lds, s, C, frames, ws, M, N, fc.odd, fc.log2e);
+        hipLaunchKernelGGL(k_gla_inverse, grid, dim3(FFT_THREADS), g.lds, s, C, frames, g.ws, M, N, g.fc.odd, g.fc.log2e);
         hipLaunchKernelGGL(k_misi_residual<false>, rgrid, dim3(256), 0, s, frames, y_dev, delta, sig, static_cast<double *>(nullptr), K,
                            M, N, fshift, zero_lo, zero_hi);
         hipLaunchKernelGGL(k_misi_signals, dim3((len + 255) / 256, BK), dim3(256), 0, s, sig, delta, x_dev, K, Tfull, zero_lo, len);
@@ -1452,7 +1472,7 @@ int misi_run(int device, void *C_dev, const float *A_dev, const float *y_dev, in
         STFT_TRY(hipMemcpyAsync(trace, c.trace.p, (size_t)iters * B * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
         STFT_TRY(hipStreamSynchronize(s));
     }
-    return ctx_leave(c, s);
+    return g.close();
 }
 
 }  // namespace
@@ -1483,14 +1503,10 @@ extern "C" int lws_misi_backward_dev(int device, const void *gC_dev, const float
     if (len < 1) return lws::set_error(LWS_ERR_INVALID, "%d frames leave no samples", M);
     if (iters > 0 && (rc = check_round_trip(M, N, fshift, perfectrec))) return rc;
     if (B == 0) return LWS_OK;
-    STFT_TRY(hipSetDevice(device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    std::lock_guard<std::mutex> lk(g_mu);
-    GlaCtx &c = g_ctx[device];
-    if ((rc = ctx_enter(c, s))) return rc;
-    if ((rc = allow_lds_all())) return rc;
-    if ((rc = upload_window(c.win_a, c.host_a, awin, N, s))) return rc;
-    if ((rc = upload_window(c.win_s, c.host_s, swin, N, s))) return rc;
+    GlaCall g(device, stream);
+    if ((rc = g.open(device, N, fshift, awin, swin, perfectrec))) return rc;
+    GlaCtx &c = g.c;
+    hipStream_t s = g.s;
     const int F = N / 2 + 1, BK = B * K, Tfull = fshift * (M - 1) + N, nblk = (Tfull + 255) / 256;
     const size_t bins = (size_t)BK * M * F;
     if (iters > 0 && (rc = c.frames.ensure((size_t)BK * M * N * sizeof(float)))) return rc;
@@ -1499,45 +1515,41 @@ extern "C" int lws_misi_backward_dev(int device, const void *gC_dev, const float
     float *frames = static_cast<float *>(c.frames.p), *gsig = static_cast<float *>(c.sig.p);
     float2 *gc = static_cast<float2 *>(c.gc.p), *gS = static_cast<float2 *>(gS_out);
     const float2 *gC = static_cast<const float2 *>(gC_dev), *tape = static_cast<const float2 *>(tape_dev);
-    const float *wa = static_cast<const float *>(c.win_a.p), *ws = static_cast<const float *>(c.win_s.p);
-    const Factors fc = factor(N);
     const dim3 grid((M + 1) / 2, BK), rgrid(nblk, B);
-    const size_t lds = fft_lds_bytes(N);
-    const int zero_lo = perfectrec ? prepad(N, fshift) : 0, zero_hi = perfectrec ? N - fshift : 0;   // as in lws_griffin_lim_dev
     if (iters == 0) STFT_TRY(hipMemsetAsync(gA_out, 0, bins * sizeof(float), s));
     // the gradient on c_i, i = iters .. 0: from the cotangents on entry, through one iteration each after that; the one on c_0 is
     // the result for the start and goes to the caller (or nowhere)
     for (int i = iters; i >= 0; --i) {
         const bool entry = i == iters;
         if (!entry)
-            hipLaunchKernelGGL(k_misi_bwd_project, grid, dim3(FFT_THREADS), lds, s, gc, tape + (size_t)i * bins, A_dev, gA_out, frames,
-                               wa, M, N, fc.odd, fc.log2e, i + 1 == iters ? 1 : 0);
+            hipLaunchKernelGGL(k_misi_bwd_project, grid, dim3(FFT_THREADS), g.lds, s, gc, tape + (size_t)i * bins, A_dev, gA_out, frames,
+                               g.wa, M, N, g.fc.odd, g.fc.log2e, i + 1 == iters ? 1 : 0);
         if (i == 0 && !gS && !gy_out) break;
         if (entry)
-            hipLaunchKernelGGL(k_misi_bwd_share<true>, rgrid, dim3(256), 0, s, gx_dev, gsig, gy_out, K, M, N, fshift, zero_lo, zero_hi, 1);
+            hipLaunchKernelGGL(k_misi_bwd_share<true>, rgrid, dim3(256), 0, s, gx_dev, gsig, gy_out, K, M, N, fshift, g.zero_lo, g.zero_hi, 1);
         else
-            hipLaunchKernelGGL(k_misi_bwd_share<false>, rgrid, dim3(256), 0, s, frames, gsig, gy_out, K, M, N, fshift, zero_lo, zero_hi, 0);
+            hipLaunchKernelGGL(k_misi_bwd_share<false>, rgrid, dim3(256), 0, s, frames, gsig, gy_out, K, M, N, fshift, g.zero_lo, g.zero_hi, 0);
         if (i == 0 && !gS) break;
-        hipLaunchKernelGGL(k_misi_bwd_frames, grid, dim3(FFT_THREADS), lds, s, gsig, ws, entry ? gC : static_cast<const float2 *>(nullptr),
-                           i == 0 ? gS : gc, M, N, fc.odd, fc.log2e, fshift);
+        hipLaunchKernelGGL(k_misi_bwd_frames, grid, dim3(FFT_THREADS), g.lds, s, gsig, g.ws, entry ? gC : static_cast<const float2 *>(nullptr),
+                           i == 0 ? gS : gc, M, N, g.fc.odd, g.fc.log2e, fshift);
     }
-    STFT_TRY(hipGetLastError());
-    return ctx_leave(c, s);
+    return g.close();
 }
 
 namespace {
 
-// Where the state of k_rtisi lives: behind the transform buffers in LDS if all of it fits there, in device scratch otherwise.
-struct RtisiPlan {
-    size_t state_floats, lds_bytes;
+// Where the state of a look-ahead kernel lives: behind the transform buffers in LDS if all of it fits there, in device scratch
+// otherwise.  K == 0: the one spectrogram of k_rtisi.  K sources (k_misi_la): K such states and the (K + 1) R floats of the coupling.
+struct LaPlacement {
+    size_t source_floats, all_floats, lds_bytes;   // state of one spectrogram (R + 2 (LA + 1) N), of a workgroup; the launch's LDS
     bool in_lds;
     int threads;   // one workgroup per CU and every step behind a barrier: a thread per sample, up to 16 waves, hides the LDS latency
 };
-constexpr size_t RTISI_LDS_CAP = 160 * 1024;
-RtisiPlan rtisi_plan(int N, int hop, int LA) {
-    RtisiPlan p;
-    p.state_floats = (size_t)N + (size_t)LA * hop + 2 * (size_t)(LA + 1) * N;
-    const size_t all = fft_lds_bytes(N) + p.state_floats * sizeof(float);
+LaPlacement la_placement(int N, int hop, int LA, int K) {
+    LaPlacement p;
+    p.source_floats = la_state_floats(N, hop, LA);
+    p.all_floats = K == 0 ? p.source_floats : (size_t)K * p.source_floats + ((size_t)K + 1) * ((size_t)N + (size_t)LA * hop);
+    const size_t all = fft_lds_bytes(N) + p.all_floats * sizeof(float);
     p.in_lds = all <= RTISI_LDS_CAP;
     p.lds_bytes = p.in_lds ? all : fft_lds_bytes(N);
     p.threads = N <= FFT_THREADS ? FFT_THREADS : N >= RTISI_MAX_THREADS ? RTISI_MAX_THREADS : (N + FFT_THREADS - 1) / FFT_THREADS * FFT_THREADS;
@@ -1545,6 +1557,16 @@ RtisiPlan rtisi_plan(int N, int hop, int LA) {
 }
 
 }  // namespace
+
+extern "C" int lws_rtisi_la_placement(int N, int fshift, int look_ahead, int K, int *in_lds, int *threads, size_t *lds_bytes) {
+    if (N < 1 || fshift < 1 || look_ahead < 0 || K < 0)
+        return lws::set_error(LWS_ERR_INVALID, "placement of N = %d, hop %d, look-ahead %d, %d sources", N, fshift, look_ahead, K);
+    const LaPlacement p = la_placement(N, fshift, look_ahead, K);
+    if (in_lds) *in_lds = p.in_lds ? 1 : 0;
+    if (threads) *threads = p.threads;
+    if (lds_bytes) *lds_bytes = p.lds_bytes;
+    return LWS_OK;
+}
 
 extern "C" int lws_rtisi_la_dev(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift,
                                 const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *stream) {
@@ -1565,79 +1587,19 @@ extern "C" int lws_rtisi_la_dev_ex(int device, void *C_dev, const float *A_dev, 
     if (iters > 0 && (rc = check_round_trip(M, N, fshift, perfectrec))) return rc;
     const int len = lws_istft_length(M, N, fshift, perfectrec);
     if (B == 0 || (given && iters == 0 && (!x_dev || len < 1))) return LWS_OK;   // an entry estimate is a result without iterations too
-    STFT_TRY(hipSetDevice(device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    std::lock_guard<std::mutex> lk(g_mu);
-    GlaCtx &c = g_ctx[device];
-    if ((rc = ctx_enter(c, s))) return rc;
-    STFT_TRY((lws::allow_dynamic_lds<&k_rtisi<true, LWS_START_GIVEN>>((int)RTISI_LDS_CAP)));
-    STFT_TRY((lws::allow_dynamic_lds<&k_rtisi<false, LWS_START_GIVEN>>(3 * MAXN * (int)sizeof(float2))));
-    STFT_TRY((lws::allow_dynamic_lds<&k_rtisi<true, LWS_START_OVERLAP>>((int)RTISI_LDS_CAP)));
-    STFT_TRY((lws::allow_dynamic_lds<&k_rtisi<false, LWS_START_OVERLAP>>(3 * MAXN * (int)sizeof(float2))));
-    if ((rc = upload_window(c.win_a, c.host_a, awin, N, s))) return rc;
-    if ((rc = upload_window(c.win_s, c.host_s, swin, N, s))) return rc;
+    GlaCall g(device, stream);
+    if ((rc = g.open(device, N, fshift, awin, swin, perfectrec))) return rc;
     const int F = N / 2 + 1, LA = look_ahead < M - 1 ? look_ahead : M - 1;   // no frame beyond M - 1 to look at
-    const size_t bins = (size_t)B * M * F;
-    const RtisiPlan p = rtisi_plan(N, fshift, LA);
-    if (!p.in_lds && (rc = c.state.ensure((size_t)B * p.state_floats * sizeof(float)))) return rc;
-    if (!A_dev && (iters > 0 || !given)) {   // the entry projection reads A
-        if ((rc = c.a.ensure(bins * sizeof(float)))) return rc;
-        hipLaunchKernelGGL(k_gla_abs, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, s, static_cast<const float2 *>(C_dev),
-                           static_cast<float *>(c.a.p), bins);
-        A_dev = static_cast<const float *>(c.a.p);
-    }
-    const Factors fc = factor(N);
-    const RtisiArgs a{M, N, fc.odd, fc.log2e, fshift, LA, iters, perfectrec ? prepad(N, fshift) : 0, perfectrec ? N - fshift : 0,
-                      len, p.state_floats};
+    const LaPlacement p = la_placement(N, fshift, LA, 0);
+    if (!p.in_lds && (rc = g.c.state.ensure((size_t)B * p.all_floats * sizeof(float)))) return rc;
     float2 *C = static_cast<float2 *>(C_dev);
-    const float *wa = static_cast<const float *>(c.win_a.p), *ws = static_cast<const float *>(c.win_s.p);
-    float *x = len < 1 ? nullptr : x_dev, *scratch = p.in_lds ? nullptr : static_cast<float *>(c.state.p);
+    if ((iters > 0 || !given) && (rc = magnitudes(A_dev, C, (size_t)B * M * F, g.c.a, g.s))) return rc;   // the entry projection reads A
+    const RtisiArgs a{M, N, g.fc.odd, g.fc.log2e, fshift, LA, iters, g.zero_lo, g.zero_hi, len, p.source_floats};
+    float *x = len < 1 ? nullptr : x_dev, *scratch = p.in_lds ? nullptr : static_cast<float *>(g.c.state.p);
     auto *kernel = p.in_lds ? (given ? k_rtisi<true, LWS_START_GIVEN> : k_rtisi<true, LWS_START_OVERLAP>)
                             : (given ? k_rtisi<false, LWS_START_GIVEN> : k_rtisi<false, LWS_START_OVERLAP>);
-    hipLaunchKernelGGL(kernel, dim3(B), dim3(p.threads), p.lds_bytes, s, C, A_dev, x, wa, ws, scratch, a);
-    STFT_TRY(hipGetLastError());
-    return ctx_leave(c, s);
-}
-
-namespace {
-
-// Where the state of k_misi_la lives: as rtisi_plan decides for one source, for K of them and the (K + 1) R floats of the coupling.
-struct MisiLaPlan {
-    size_t source_floats, all_floats, lds_bytes;
-    bool in_lds;
-    int threads;
-};
-MisiLaPlan misi_la_plan(int N, int hop, int LA, int K) {
-    const RtisiPlan one = rtisi_plan(N, hop, LA);
-    MisiLaPlan p;
-    p.source_floats = one.state_floats;
-    p.all_floats = (size_t)K * one.state_floats + ((size_t)K + 1) * ((size_t)N + (size_t)LA * hop);
-    const size_t all = fft_lds_bytes(N) + p.all_floats * sizeof(float);
-    p.in_lds = all <= RTISI_LDS_CAP;
-    p.lds_bytes = p.in_lds ? all : fft_lds_bytes(N);
-    p.threads = one.threads;
-    return p;
-}
-
-}  // namespace
-
-extern "C" int lws_rtisi_la_placement(int N, int fshift, int look_ahead, int K, int *in_lds, int *threads, size_t *lds_bytes) {
-    if (N < 1 || fshift < 1 || look_ahead < 0 || K < 0)
-        return lws::set_error(LWS_ERR_INVALID, "placement of N = %d, hop %d, look-ahead %d, %d sources", N, fshift, look_ahead, K);
-    bool lds;
-    int th;
-    size_t bytes;
-    if (K == 0) {
-        const RtisiPlan p = rtisi_plan(N, fshift, look_ahead);
-        lds = p.in_lds; th = p.threads; bytes = p.lds_bytes;
-    } else {
-        const MisiLaPlan p = misi_la_plan(N, fshift, look_ahead, K);
-        lds = p.in_lds; th = p.threads; bytes = p.lds_bytes;
-    }
-    if (in_lds) *in_lds = lds ? 1 : 0;
-    if (threads) *threads = th;
-    if (lds_bytes) *lds_bytes = bytes;
-    return LWS_OK;
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(p.threads), p.lds_bytes, g.s, C, A_dev, x, g.wa, g.ws, scratch, a);
+    return g.close();
 }
 
 extern "C" int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, float *x_dev, int B, int K, int M, int N,
@@ -1662,124 +1624,217 @@ extern "C" int lws_misi_la_dev_ex(int device, void *C_dev, const float *A_dev, c
     if (len < 1) return lws::set_error(LWS_ERR_INVALID, "%d frames leave no samples", M);
     if (iters > 0 && (rc = check_round_trip(M, N, fshift, perfectrec))) return rc;
     if (B == 0 || (given && iters == 0 && !x_dev)) return LWS_OK;   // an entry estimate is a result without iterations too
-    STFT_TRY(hipSetDevice(device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    std::lock_guard<std::mutex> lk(g_mu);
-    GlaCtx &c = g_ctx[device];
-    if ((rc = ctx_enter(c, s))) return rc;
-    STFT_TRY((lws::allow_dynamic_lds<&k_misi_la<true, LWS_START_GIVEN>>((int)RTISI_LDS_CAP)));
-    STFT_TRY((lws::allow_dynamic_lds<&k_misi_la<false, LWS_START_GIVEN>>(3 * MAXN * (int)sizeof(float2))));
-    STFT_TRY((lws::allow_dynamic_lds<&k_misi_la<true, LWS_START_MIXTURE>>((int)RTISI_LDS_CAP)));
-    STFT_TRY((lws::allow_dynamic_lds<&k_misi_la<false, LWS_START_MIXTURE>>(3 * MAXN * (int)sizeof(float2))));
-    if ((rc = upload_window(c.win_a, c.host_a, awin, N, s))) return rc;
-    if ((rc = upload_window(c.win_s, c.host_s, swin, N, s))) return rc;
+    GlaCall g(device, stream);
+    if ((rc = g.open(device, N, fshift, awin, swin, perfectrec))) return rc;
     const int F = N / 2 + 1, LA = look_ahead < M - 1 ? look_ahead : M - 1;   // no frame beyond M - 1 to look at
-    const size_t bins = (size_t)B * K * M * F;
-    const MisiLaPlan p = misi_la_plan(N, fshift, LA, K);
-    if (!p.in_lds && (rc = c.state.ensure((size_t)B * p.all_floats * sizeof(float)))) return rc;
-    if (!A_dev && (iters > 0 || !given)) {   // the entry projection reads A
-        if ((rc = c.a.ensure(bins * sizeof(float)))) return rc;
-        hipLaunchKernelGGL(k_gla_abs, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, s, static_cast<const float2 *>(C_dev),
-                           static_cast<float *>(c.a.p), bins);
-        A_dev = static_cast<const float *>(c.a.p);
-    }
-    const Factors fc = factor(N);
-    const MisiLaArgs q{{M, N, fc.odd, fc.log2e, fshift, LA, iters, perfectrec ? prepad(N, fshift) : 0, perfectrec ? N - fshift : 0, len,
-                        p.source_floats},
-                       K, p.all_floats};
+    const LaPlacement p = la_placement(N, fshift, LA, K);
+    if (!p.in_lds && (rc = g.c.state.ensure((size_t)B * p.all_floats * sizeof(float)))) return rc;
     float2 *C = static_cast<float2 *>(C_dev);
-    const float *wa = static_cast<const float *>(c.win_a.p), *ws = static_cast<const float *>(c.win_s.p);
-    float *scratch = p.in_lds ? nullptr : static_cast<float *>(c.state.p);
+    if ((iters > 0 || !given) && (rc = magnitudes(A_dev, C, (size_t)B * K * M * F, g.c.a, g.s))) return rc;   // the entry projection reads A
+    const MisiLaArgs q{{M, N, g.fc.odd, g.fc.log2e, fshift, LA, iters, g.zero_lo, g.zero_hi, len, p.source_floats}, K, p.all_floats};
+    float *scratch = p.in_lds ? nullptr : static_cast<float *>(g.c.state.p);
     auto *kernel = p.in_lds ? (given ? k_misi_la<true, LWS_START_GIVEN> : k_misi_la<true, LWS_START_MIXTURE>)
                             : (given ? k_misi_la<false, LWS_START_GIVEN> : k_misi_la<false, LWS_START_MIXTURE>);
-    hipLaunchKernelGGL(kernel, dim3(B), dim3(p.threads), p.lds_bytes, s, C, A_dev, y_dev, x_dev, wa, ws, scratch, q);
-    STFT_TRY(hipGetLastError());
-    return ctx_leave(c, s);
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(p.threads), p.lds_bytes, g.s, C, A_dev, y_dev, x_dev, g.wa, g.ws, scratch, q);
+    return g.close();
 }
 
-// ---- Streaming RTISI-LA: the handle.  Everything a stream carries between calls is its own -- state, held rows, windows, the
-// magnitudes of a chunk given without them -- so streams share nothing with each other or with the calls on GlaCtx.
-struct lws_rtisi_stream {
-    int device = 0, B = 0, N = 0, hop = 0, LA = 0, iters = 0, perfectrec = 0, start = LWS_START_GIVEN;
-    RtisiPlan plan{};
-    size_t state_floats = 0;              // per stream: ring, fcur and, with the scratch placement, the other frame buffer
-    Scratch state, held_s[2], held_a[2], abuf, win_a, win_s;
-    long long entered = 0, committed = 0; // frames pushed, frames committed
-    int base = 0, slot = 0, cur = 0;      // of the next step: ring offset, slot of its frame, which frame buffer is fcur
-    int held = 0;                         // which held buffer is current
-    bool ran = false, finished = false;
+// ---- The look-ahead streams: one handle for lws_rtisi_stream (K == 0) and lws_misi_stream (K sources of each of B mixtures).  What a
+// stream carries between calls is its own -- state, held rows, (K > 0) held mixture samples and, with the scratch placement, the room
+// for target and xs, windows, the magnitudes of a chunk given without them -- so streams share nothing with each other or with the
+// calls on GlaCtx.  What a call does is decided by the clock (lws_la_stream.h); only la_launch knows which kernel runs.
+struct lws_la_stream {
+    int device = 0, B = 0;
+    LaClock clock;
+    Scratch state, held_s[2], held_a[2], held_y[2], abuf, win_a, win_s;
     hipEvent_t last = nullptr;            // the event scheme of GlaCtx, for a caller that changes streams between calls
     hipStream_t last_stream = nullptr;
     bool busy = false;
     std::mutex mu;
 };
+struct lws_rtisi_stream : lws_la_stream {};
+struct lws_misi_stream : lws_la_stream {};
 
 namespace {
 
-int stream_enter(lws_rtisi_stream &h, hipStream_t s) {
+int la_enter(lws_la_stream &h, hipStream_t s) {
     if (h.busy && s != h.last_stream) STFT_TRY(hipStreamWaitEvent(s, h.last, 0));
     return LWS_OK;
 }
-int stream_leave(lws_rtisi_stream &h, hipStream_t s) {
+int la_leave(lws_la_stream &h, hipStream_t s) {
     STFT_TRY(hipEventRecord(h.last, s));
     h.busy = true;
     h.last_stream = s;
     return LWS_OK;
 }
 
-// rows [at, at + frames) of the held buffers from a chunk: the frames that arrive before the first commit can run
-int stream_stash(lws_rtisi_stream &h, const float2 *S, const float *A, int frames, hipStream_t s) {
-    const size_t F = (size_t)h.N / 2 + 1, at = (size_t)h.entered;
-    if (h.start == LWS_START_GIVEN)   // no other start reads the rows
-        STFT_TRY(hipMemcpy2DAsync(static_cast<float2 *>(h.held_s[h.held].p) + at * F, (size_t)h.LA * F * sizeof(float2), S,
-                                  (size_t)frames * F * sizeof(float2), (size_t)frames * F * sizeof(float2), h.B, hipMemcpyDeviceToDevice,
-                                  s));
+// a chunk's rows, and the samples under them, into the held buffers the next launch reads: what arrives before the first commit can run
+int la_stash(lws_la_stream &h, const LaPlan &p, const float2 *S, const float *A, const float *y, int frames, int samples, hipStream_t s) {
+    const LaClock &c = h.clock;
+    const size_t F = (size_t)c.N / 2 + 1, at = (size_t)p.stash_row, specs = (size_t)h.B * (c.K ? c.K : 1);
+    if (c.given)   // no other start reads the rows
+        STFT_TRY(hipMemcpy2DAsync(static_cast<float2 *>(h.held_s[p.write].p) + at * F, (size_t)c.LA * F * sizeof(float2), S,
+                                  (size_t)frames * F * sizeof(float2), (size_t)frames * F * sizeof(float2), specs,
+                                  hipMemcpyDeviceToDevice, s));
     if (A)
-        STFT_TRY(hipMemcpy2DAsync(static_cast<float *>(h.held_a[h.held].p) + at * F, (size_t)h.LA * F * sizeof(float), A,
-                                  (size_t)frames * F * sizeof(float), (size_t)frames * F * sizeof(float), h.B, hipMemcpyDeviceToDevice, s));
+        STFT_TRY(hipMemcpy2DAsync(static_cast<float *>(h.held_a[p.write].p) + at * F, (size_t)c.LA * F * sizeof(float), A,
+                                  (size_t)frames * F * sizeof(float), (size_t)frames * F * sizeof(float), specs, hipMemcpyDeviceToDevice,
+                                  s));
+    if (c.K)
+        STFT_TRY(hipMemcpy2DAsync(static_cast<float *>(h.held_y[p.write].p) + p.stash_y, (size_t)c.y_rows * sizeof(float), y,
+                                  (size_t)samples * sizeof(float), (size_t)samples * sizeof(float), h.B, hipMemcpyDeviceToDevice, s));
     return LWS_OK;
 }
 
-// the commit steps committed .. committed + nsteps - 1; M < 0 while the stream is open, the frame count at its end
-int stream_launch(lws_rtisi_stream &h, const float2 *S, const float *A, int frames, float2 *C_out, float *x_out, int out_rows,
-                  int out_samples, int nsteps, long long M, hipStream_t s) {
-    const bool closing = M >= 0;
-    const int LA = (closing && !h.ran) ? (int)M - 1 : h.LA;   // an end before the first commit: no frame beyond M - 1 to look at
-    const RtisiPlan p = rtisi_plan(h.N, h.hop, LA);
-    const Factors fc = factor(h.N);
-    const long long t0 = (long long)h.hop * h.committed, lo = h.perfectrec ? prepad(h.N, h.hop) : 0;
-    RtisiStreamArgs q{};
-    q.N = h.N; q.odd = fc.odd; q.log2e = fc.log2e; q.hop = h.hop; q.LA = LA; q.iters = h.iters;
-    q.nsteps = nsteps;
-    q.Mrel = closing ? (int)(M - h.committed) : nsteps + LA;
-    q.closing = closing;
-    q.origin = h.committed == 0;
-    q.zero_lo = lo > t0 ? (int)(lo - t0) : 0;
-    q.emit_end = closing && h.perfectrec ? (int)((long long)h.hop * M - t0) : 0x7fffffff;
-    q.base = h.base; q.slot_m = h.slot; q.cur = h.cur;
-    q.nheld = h.ran ? h.LA : (int)h.entered;   // before the first launch: the stashed frames (the chunk's are not counted yet)
-    q.held_rows = h.LA;
-    q.chunk_rows = frames; q.out_rows = out_rows; q.out_samples = out_samples;
-    q.state_floats = h.state_floats;
-    const int nxt = h.held ^ 1;
-    const bool given = h.start == LWS_START_GIVEN;   // any other start projects at entry: it keeps the magnitudes without iterations too
-    const RtisiHeld held{static_cast<const float2 *>(h.held_s[h.held].p), static_cast<const float *>(h.held_a[h.held].p),
-                         closing || h.iters > 0 ? nullptr : static_cast<float2 *>(h.held_s[nxt].p),
-                         closing || (given && h.iters == 0) ? nullptr : static_cast<float *>(h.held_a[nxt].p)};
+int la_launch(lws_la_stream &h, const LaPlan &p, const float2 *S, const float *A, const float *y, float2 *C_out, float *x_out,
+              hipStream_t s) {
+    const LaClock &c = h.clock;
+    const LaPlacement pl = la_placement(c.N, c.hop, p.a.r.LA, c.K);
+    const float2 *hs = static_cast<const float2 *>(h.held_s[p.read].p);
+    const float *ha = static_cast<const float *>(h.held_a[p.read].p), *hy = static_cast<const float *>(h.held_y[p.read].p);
+    float2 *s_next = p.keep_s ? static_cast<float2 *>(h.held_s[p.write].p) : nullptr;
+    float *a_next = p.keep_a ? static_cast<float *>(h.held_a[p.write].p) : nullptr;
+    float *y_next = p.keep_y ? static_cast<float *>(h.held_y[p.write].p) : nullptr;
     const float *wa = static_cast<const float *>(h.win_a.p), *ws = static_cast<const float *>(h.win_s.p);
     float *st = static_cast<float *>(h.state.p);
-    auto *kernel = p.in_lds ? (given ? k_rtisi_stream<true, LWS_START_GIVEN> : k_rtisi_stream<true, LWS_START_OVERLAP>)
-                            : (given ? k_rtisi_stream<false, LWS_START_GIVEN> : k_rtisi_stream<false, LWS_START_OVERLAP>);
-    hipLaunchKernelGGL(kernel, dim3(h.B), dim3(p.threads), p.lds_bytes, s, S, A, C_out, x_out, wa, ws, st, held, q);
+    const dim3 grid(h.B), block(pl.threads);
+    if (c.K == 0) {
+        auto *kernel = pl.in_lds ? (c.given ? k_rtisi_stream<true, LWS_START_GIVEN> : k_rtisi_stream<true, LWS_START_OVERLAP>)
+                                 : (c.given ? k_rtisi_stream<false, LWS_START_GIVEN> : k_rtisi_stream<false, LWS_START_OVERLAP>);
+        hipLaunchKernelGGL(kernel, grid, block, pl.lds_bytes, s, S, A, C_out, x_out, wa, ws, st, RtisiHeld{hs, ha, s_next, a_next}, p.a.r);
+    } else {
+        auto *kernel = pl.in_lds ? (c.given ? k_misi_la_stream<true, LWS_START_GIVEN> : k_misi_la_stream<true, LWS_START_MIXTURE>)
+                                 : (c.given ? k_misi_la_stream<false, LWS_START_GIVEN> : k_misi_la_stream<false, LWS_START_MIXTURE>);
+        hipLaunchKernelGGL(kernel, grid, block, pl.lds_bytes, s, S, A, y, C_out, x_out, wa, ws, st,
+                           MisiStreamHeld{hs, ha, hy, s_next, a_next, y_next}, p.a);
+    }
     STFT_TRY(hipGetLastError());
-    const int R = h.N + LA * h.hop;
-    h.base = (int)(((long long)h.base + (long long)h.hop * nsteps) % R);
-    h.slot = (int)(((long long)h.slot + nsteps) % (LA + 1));
-    h.cur ^= (int)(((long long)h.iters * nsteps) & 1);
-    h.held = nxt;
-    h.committed += nsteps;
-    h.ran = true;
     return LWS_OK;
+}
+
+void la_destroy(lws_la_stream *h) {
+    (void)hipSetDevice(h->device);
+    for (Scratch *b : {&h->state, &h->held_s[0], &h->held_s[1], &h->held_a[0], &h->held_a[1], &h->held_y[0], &h->held_y[1], &h->abuf,
+                       &h->win_a, &h->win_s})
+        if (b->p) (void)hipFree(b->p);
+    if (h->last) (void)hipEventDestroy(h->last);
+}
+
+// mixture: a lws_misi_stream of K >= 1 sources (other start: LWS_START_MIXTURE); else a lws_rtisi_stream, K == 0 (LWS_START_OVERLAP)
+template <class Handle>
+int la_create(int device, int B, int K, int N, int fshift, const double *awin, const double *swin, int perfectrec, int iters,
+              int look_ahead, int start, bool mixture, Handle **out) {
+    if (!out) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    *out = nullptr;
+    int rc = check_shape(device, B, 1, N, fshift);
+    if (rc) return rc;
+    if (start != LWS_START_GIVEN && start != (mixture ? LWS_START_MIXTURE : LWS_START_OVERLAP))
+        return lws::set_error(LWS_ERR_INVALID, "start %d for %s", start, mixture ? "online MISI" : "RTISI-LA");
+    const bool given = start == LWS_START_GIVEN;
+    if (B < 1) return lws::set_error(LWS_ERR_INVALID, "%d streams", B);
+    if (mixture && K < 1) return lws::set_error(LWS_ERR_INVALID, "%d sources", K);
+    if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
+    if (look_ahead < 0) return lws::set_error(LWS_ERR_INVALID, "look-ahead of %d frames", look_ahead);
+    if (!awin || !swin) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    if (!la_look_ahead_fits(N, fshift, look_ahead, K)) return lws::set_error(LWS_ERR_UNSUPPORTED, "look-ahead of %d frames", look_ahead);
+    STFT_TRY(hipSetDevice(device));
+    if ((rc = allow_lds_all())) return rc;
+    Handle *h = new Handle;
+    h->device = device; h->B = B;
+    LaClock &c = h->clock;
+    la_clock_init(c, N, fshift, look_ahead, iters, K, perfectrec != 0, given, la_placement(N, fshift, look_ahead, K).in_lds);
+    const size_t F = (size_t)N / 2 + 1, rows = (size_t)B * (K ? K : 1) * look_ahead * F;
+    const size_t state_bytes = (size_t)B * (K ? c.stream_floats : c.state_floats) * sizeof(float);
+    const size_t y_bytes = (size_t)B * c.y_rows * sizeof(float);
+    std::vector<float> wa(N), ws(N);
+    for (int i = 0; i < N; ++i) { wa[i] = (float)awin[i]; ws[i] = (float)swin[i]; }
+    rc = h->state.ensure(state_bytes);
+    if (!rc) rc = h->win_a.ensure((size_t)N * sizeof(float));
+    if (!rc) rc = h->win_s.ensure((size_t)N * sizeof(float));
+    if (!rc && K) rc = h->held_y[0].ensure(y_bytes);
+    if (!rc && K) rc = h->held_y[1].ensure(y_bytes);
+    if (!rc && (given || iters == 0)) rc = h->held_s[0].ensure(rows * sizeof(float2));   // start rows, or entry rows to return
+    if (!rc && iters == 0) rc = h->held_s[1].ensure(rows * sizeof(float2));
+    if (!rc && (iters > 0 || !given)) rc = h->held_a[0].ensure(rows * sizeof(float));
+    if (!rc && (iters > 0 || !given)) rc = h->held_a[1].ensure(rows * sizeof(float));
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipEventCreateWithFlags(&h->last, hipEventDisableTiming);
+    if (!rc && e == hipSuccess) e = hipMemset(h->state.p, 0, state_bytes);
+    if (!rc && e == hipSuccess && K) e = hipMemset(h->held_y[0].p, 0, y_bytes);
+    if (!rc && e == hipSuccess && K) e = hipMemset(h->held_y[1].p, 0, y_bytes);
+    if (!rc && e == hipSuccess) e = hipMemcpy(h->win_a.p, wa.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice);
+    if (!rc && e == hipSuccess) e = hipMemcpy(h->win_s.p, ws.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice);
+    if (!rc && e == hipSuccess) e = hipDeviceSynchronize();   // the state is zero before any stream of the caller's touches it
+    if (!rc && e != hipSuccess) rc = lws::set_error(LWS_ERR_HIP, "creating a stream's state failed: %s", hipGetErrorString(e));
+    if (rc) {
+        la_destroy(h);
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return LWS_OK;
+}
+
+int la_push(lws_la_stream *h, const void *S_dev, const float *A_dev, const float *y_dev, int frames, int samples, void *C_out_dev,
+            float *x_out_dev, int *frames_out, int *samples_out, void *stream) {
+    if (frames_out) *frames_out = 0;
+    if (samples_out) *samples_out = 0;
+    if (!h) return lws::set_error(LWS_ERR_INVALID, "null stream handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    LaClock &c = h->clock;
+    long long want = 0;
+    switch (la_check_push(c, frames, samples, &want)) {
+    case LA_NEGATIVE: return lws::set_error(LWS_ERR_INVALID, "%d frames", frames);
+    case LA_FINISHED: return lws::set_error(LWS_ERR_INVALID, "push after finish");
+    case LA_TOO_LONG: return lws::set_error(LWS_ERR_UNSUPPORTED, "%d frames in one push", frames);
+    case LA_SAMPLES:
+        return lws::set_error(LWS_ERR_INVALID, "%d mixture samples for %d frames after %lld: expected %lld", samples, frames, c.entered,
+                              want);
+    case LA_GO: break;
+    }
+    if (frames == 0) return LWS_OK;
+    const bool given = c.given;
+    if ((!S_dev && (given || !A_dev)) || (c.K && !y_dev))   // magnitudes alone serve any other start
+        return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    const LaPlan p = la_plan_push(c, frames, samples);
+    if (p.launch && !C_out_dev) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    STFT_TRY(hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = la_enter(*h, s);
+    if (rc) return rc;
+    const float2 *S = static_cast<const float2 *>(S_dev);
+    const size_t bins = (size_t)h->B * (c.K ? c.K : 1) * frames * (c.N / 2 + 1);
+    if ((c.iters > 0 || !given) && (rc = magnitudes(A_dev, S, bins, h->abuf, s))) return rc;   // |S| by the kernel the one-shot calls use
+    if (given && c.iters == 0) A_dev = nullptr;
+    rc = p.launch ? la_launch(*h, p, S, A_dev, y_dev, static_cast<float2 *>(C_out_dev), x_out_dev, s)
+                  : la_stash(*h, p, S, A_dev, y_dev, frames, samples, s);
+    if (rc) return rc;
+    c = p.after;
+    if (frames_out) *frames_out = p.frames_out;
+    if (samples_out) *samples_out = p.samples_out;
+    return la_leave(*h, s);
+}
+
+int la_finish(lws_la_stream *h, void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out, void *stream) {
+    if (frames_out) *frames_out = 0;
+    if (samples_out) *samples_out = 0;
+    if (!h) return lws::set_error(LWS_ERR_INVALID, "null stream handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    LaClock &c = h->clock;
+    if (la_check_finish(c) != LA_GO) return lws::set_error(LWS_ERR_INVALID, "finish after finish");
+    const LaPlan p = la_plan_finish(c, x_out_dev != nullptr);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.launch) {
+        if (p.a.r.nsteps > 0 && !C_out_dev) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+        STFT_TRY(hipSetDevice(h->device));
+        int rc = la_enter(*h, s);
+        if (!rc) rc = la_launch(*h, p, nullptr, nullptr, nullptr, static_cast<float2 *>(C_out_dev), x_out_dev, s);
+        if (rc) return rc;
+    }
+    c = p.after;
+    if (frames_out) *frames_out = p.frames_out;
+    if (samples_out) *samples_out = p.samples_out;
+    return p.launch ? la_leave(*h, s) : LWS_OK;
 }
 
 }  // namespace
@@ -1788,402 +1843,42 @@ extern "C" int lws_rtisi_stream_create(int device, int B, int N, int fshift, con
                                        int iters, int look_ahead, lws_rtisi_stream **out) {
     return lws_rtisi_stream_create_ex(device, B, N, fshift, awin, swin, perfectrec, iters, look_ahead, LWS_START_GIVEN, out);
 }
-
 extern "C" int lws_rtisi_stream_create_ex(int device, int B, int N, int fshift, const double *awin, const double *swin, int perfectrec,
                                           int iters, int look_ahead, int start, lws_rtisi_stream **out) {
-    if (!out) return lws::set_error(LWS_ERR_INVALID, "null pointer");
-    *out = nullptr;
-    int rc = check_shape(device, B, 1, N, fshift);
-    if (rc) return rc;
-    if (start != LWS_START_GIVEN && start != LWS_START_OVERLAP) return lws::set_error(LWS_ERR_INVALID, "start %d for RTISI-LA", start);
-    const bool given = start == LWS_START_GIVEN;
-    if (B < 1) return lws::set_error(LWS_ERR_INVALID, "%d streams", B);
-    if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
-    if (look_ahead < 0) return lws::set_error(LWS_ERR_INVALID, "look-ahead of %d frames", look_ahead);
-    if (!awin || !swin) return lws::set_error(LWS_ERR_INVALID, "null pointer");
-    if ((long long)(look_ahead + 2) * fshift + N > 0x7fffffffLL / 2)
-        return lws::set_error(LWS_ERR_UNSUPPORTED, "look-ahead of %d frames", look_ahead);
-    STFT_TRY(hipSetDevice(device));
-    STFT_TRY((lws::allow_dynamic_lds<&k_rtisi_stream<true, LWS_START_GIVEN>>((int)RTISI_LDS_CAP)));
-    STFT_TRY((lws::allow_dynamic_lds<&k_rtisi_stream<false, LWS_START_GIVEN>>(3 * MAXN * (int)sizeof(float2))));
-    STFT_TRY((lws::allow_dynamic_lds<&k_rtisi_stream<true, LWS_START_OVERLAP>>((int)RTISI_LDS_CAP)));
-    STFT_TRY((lws::allow_dynamic_lds<&k_rtisi_stream<false, LWS_START_OVERLAP>>(3 * MAXN * (int)sizeof(float2))));
-    lws_rtisi_stream *h = new lws_rtisi_stream;
-    h->start = start;
-    h->device = device; h->B = B; h->N = N; h->hop = fshift; h->LA = look_ahead; h->iters = iters; h->perfectrec = perfectrec ? 1 : 0;
-    h->plan = rtisi_plan(N, fshift, look_ahead);
-    const size_t F = (size_t)N / 2 + 1, frame_floats = (size_t)(look_ahead + 1) * N;
-    h->state_floats = h->plan.in_lds ? h->plan.state_floats - frame_floats : h->plan.state_floats;
-    const size_t state_bytes = (size_t)B * h->state_floats * sizeof(float), rows = (size_t)B * look_ahead * F;
-    std::vector<float> wa(N), ws(N);
-    for (int i = 0; i < N; ++i) { wa[i] = (float)awin[i]; ws[i] = (float)swin[i]; }
-    rc = h->state.ensure(state_bytes);
-    if (!rc) rc = h->win_a.ensure((size_t)N * sizeof(float));
-    if (!rc) rc = h->win_s.ensure((size_t)N * sizeof(float));
-    if (!rc && (given || iters == 0)) rc = h->held_s[0].ensure(rows * sizeof(float2));   // start rows, or entry rows to return
-    if (!rc && iters == 0) rc = h->held_s[1].ensure(rows * sizeof(float2));
-    if (!rc && (iters > 0 || !given)) rc = h->held_a[0].ensure(rows * sizeof(float));
-    if (!rc && (iters > 0 || !given)) rc = h->held_a[1].ensure(rows * sizeof(float));
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipEventCreateWithFlags(&h->last, hipEventDisableTiming);
-    if (!rc && e == hipSuccess) e = hipMemset(h->state.p, 0, state_bytes);
-    if (!rc && e == hipSuccess) e = hipMemcpy(h->win_a.p, wa.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice);
-    if (!rc && e == hipSuccess) e = hipMemcpy(h->win_s.p, ws.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice);
-    if (!rc && e == hipSuccess) e = hipDeviceSynchronize();   // the state is zero before any stream of the caller's touches it
-    if (!rc && e != hipSuccess) rc = lws::set_error(LWS_ERR_HIP, "creating a stream's state failed: %s", hipGetErrorString(e));
-    if (rc) {
-        lws_rtisi_stream_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return LWS_OK;
+    return la_create(device, B, 0, N, fshift, awin, swin, perfectrec, iters, look_ahead, start, false, out);
 }
-
 extern "C" int lws_rtisi_stream_push(lws_rtisi_stream *h, const void *S_dev, const float *A_dev, int frames, void *C_out_dev,
                                      float *x_out_dev, int *frames_out, int *samples_out, void *stream) {
-    if (frames_out) *frames_out = 0;
-    if (samples_out) *samples_out = 0;
-    if (!h) return lws::set_error(LWS_ERR_INVALID, "null stream handle");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (frames < 0) return lws::set_error(LWS_ERR_INVALID, "%d frames", frames);
-    if (h->finished) return lws::set_error(LWS_ERR_INVALID, "push after finish");
-    if (frames == 0) return LWS_OK;
-    const bool given = h->start == LWS_START_GIVEN;
-    if (!S_dev && (given || !A_dev)) return lws::set_error(LWS_ERR_INVALID, "null pointer");   // magnitudes alone serve any other start
-    if (((long long)frames + h->LA + 2) * h->hop + h->N > 0x7fffffffLL)
-        return lws::set_error(LWS_ERR_UNSUPPORTED, "%d frames in one push", frames);
-    const long long entered = h->entered + frames;
-    const long long nsteps = entered > h->LA ? entered - h->LA - h->committed : 0;
-    if (nsteps > 0 && !C_out_dev) return lws::set_error(LWS_ERR_INVALID, "null pointer");
-    STFT_TRY(hipSetDevice(h->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = stream_enter(*h, s);
-    if (rc) return rc;
-    const float2 *S = static_cast<const float2 *>(S_dev);
-    const size_t bins = (size_t)h->B * frames * (h->N / 2 + 1);
-    if (!A_dev && (h->iters > 0 || !given)) {   // |S| by the kernel lws_rtisi_la_dev takes it from
-        if ((rc = h->abuf.ensure(bins * sizeof(float)))) return rc;
-        hipLaunchKernelGGL(k_gla_abs, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, s, S, static_cast<float *>(h->abuf.p), bins);
-        A_dev = static_cast<const float *>(h->abuf.p);
-    }
-    if (given && h->iters == 0) A_dev = nullptr;
-    if (nsteps == 0) {
-        if ((rc = stream_stash(*h, S, A_dev, frames, s))) return rc;
-    } else {
-        const long long t0 = (long long)h->hop * h->committed, lo = h->perfectrec ? prepad(h->N, h->hop) : 0;
-        const long long from = lo > t0 ? lo : t0, to = (long long)h->hop * (h->committed + nsteps);
-        if ((rc = stream_launch(*h, S, A_dev, frames, static_cast<float2 *>(C_out_dev), x_out_dev, frames, frames * h->hop, (int)nsteps,
-                                -1, s)))
-            return rc;
-        if (frames_out) *frames_out = (int)nsteps;
-        if (samples_out) *samples_out = to > from ? (int)(to - from) : 0;
-    }
-    h->entered = entered;
-    return stream_leave(*h, s);
+    return la_push(h, S_dev, A_dev, nullptr, frames, 0, C_out_dev, x_out_dev, frames_out, samples_out, stream);
 }
-
 extern "C" int lws_rtisi_stream_finish(lws_rtisi_stream *h, void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out,
                                        void *stream) {
-    if (frames_out) *frames_out = 0;
-    if (samples_out) *samples_out = 0;
-    if (!h) return lws::set_error(LWS_ERR_INVALID, "null stream handle");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->finished) return lws::set_error(LWS_ERR_INVALID, "finish after finish");
-    const long long M = h->entered, nsteps = M - h->committed;
-    // no step left (nothing pushed, or look_ahead == 0): only the samples behind the last commit, which perfectrec cuts
-    if (nsteps == 0 && (M == 0 || h->perfectrec || !x_out_dev)) {
-        h->finished = true;
-        if (samples_out && M > 0 && !h->perfectrec) *samples_out = h->N - h->hop;
-        return LWS_OK;
-    }
-    if (nsteps > 0 && !C_out_dev) return lws::set_error(LWS_ERR_INVALID, "null pointer");
-    STFT_TRY(hipSetDevice(h->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = stream_enter(*h, s);
-    if (rc) return rc;
-    const long long t0 = (long long)h->hop * h->committed, lo = h->perfectrec ? prepad(h->N, h->hop) : 0;
-    const long long from = lo > t0 ? lo : t0, to = h->perfectrec ? (long long)h->hop * M : (long long)h->hop * (M - 1) + h->N;
-    if ((rc = stream_launch(*h, nullptr, nullptr, 0, static_cast<float2 *>(C_out_dev), x_out_dev, h->LA, h->N + h->LA * h->hop,
-                            (int)nsteps, M, s)))
-        return rc;
-    h->finished = true;
-    if (frames_out) *frames_out = (int)nsteps;
-    if (samples_out) *samples_out = to > from ? (int)(to - from) : 0;
-    return stream_leave(*h, s);
+    return la_finish(h, C_out_dev, x_out_dev, frames_out, samples_out, stream);
 }
-
 extern "C" void lws_rtisi_stream_destroy(lws_rtisi_stream *h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    for (Scratch *b : {&h->state, &h->held_s[0], &h->held_s[1], &h->held_a[0], &h->held_a[1], &h->abuf, &h->win_a, &h->win_s})
-        if (b->p) (void)hipFree(b->p);
-    if (h->last) (void)hipEventDestroy(h->last);
+    la_destroy(h);
     delete h;
 }
-
-// ---- Streaming online MISI: the handle.  As lws_rtisi_stream, for the K sources of each of B mixtures: besides state, held rows and
-// windows it owns the held mixture samples and, with the scratch placement, the room for target and xs -- nothing is shared with
-// other streams or with the calls on GlaCtx.
-struct lws_misi_stream {
-    int device = 0, B = 0, K = 0, N = 0, hop = 0, LA = 0, iters = 0, perfectrec = 0, start = LWS_START_GIVEN;
-    MisiLaPlan plan{};
-    size_t source_floats = 0;             // per source: ring, fcur and, with the scratch placement, the other frame buffer
-    size_t stream_floats = 0;             // per stream: K of those and, with the scratch placement, the (K + 1) R floats of target and xs
-    int y_rows = 0;                       // floats of a stream in held_y
-    Scratch state, held_s[2], held_a[2], held_y[2], abuf, win_a, win_s;
-    long long entered = 0, committed = 0; // frames pushed, frames committed
-    int base = 0, slot = 0, cur = 0;      // of the next step: ring offset, slot of its frame, which frame buffer is fcur
-    int held = 0;                         // which held buffers are current
-    bool ran = false, finished = false;
-    hipEvent_t last = nullptr;            // as lws_rtisi_stream
-    hipStream_t last_stream = nullptr;
-    bool busy = false;
-    std::mutex mu;
-};
-
-namespace {
-
-// mixture samples under the first M frames of a stream
-long long misi_need(const lws_misi_stream &h, long long M) {
-    return M <= 0 ? 0 : (long long)h.hop * (M - 1) + h.N - (h.perfectrec ? prepad(h.N, h.hop) : 0);
-}
-
-int misi_enter(lws_misi_stream &h, hipStream_t s) {
-    if (h.busy && s != h.last_stream) STFT_TRY(hipStreamWaitEvent(s, h.last, 0));
-    return LWS_OK;
-}
-int misi_leave(lws_misi_stream &h, hipStream_t s) {
-    STFT_TRY(hipEventRecord(h.last, s));
-    h.busy = true;
-    h.last_stream = s;
-    return LWS_OK;
-}
-
-// rows [at, at + frames) of the held buffers and the samples under them from a chunk: what arrives before the first commit can run.
-// Held sample t is sample t of the stream's timeline (the lead-in included, never read)
-int misi_stash(lws_misi_stream &h, const float2 *S, const float *A, const float *y, int frames, int samples, hipStream_t s) {
-    const size_t F = (size_t)h.N / 2 + 1, at = (size_t)h.entered, BK = (size_t)h.B * h.K;
-    const size_t y_at = (size_t)(h.perfectrec ? prepad(h.N, h.hop) : 0) + (size_t)misi_need(h, h.entered);
-    if (h.start == LWS_START_GIVEN)   // no other start reads the rows
-        STFT_TRY(hipMemcpy2DAsync(static_cast<float2 *>(h.held_s[h.held].p) + at * F, (size_t)h.LA * F * sizeof(float2), S,
-                                  (size_t)frames * F * sizeof(float2), (size_t)frames * F * sizeof(float2), BK, hipMemcpyDeviceToDevice,
-                                  s));
-    if (A)
-        STFT_TRY(hipMemcpy2DAsync(static_cast<float *>(h.held_a[h.held].p) + at * F, (size_t)h.LA * F * sizeof(float), A,
-                                  (size_t)frames * F * sizeof(float), (size_t)frames * F * sizeof(float), BK, hipMemcpyDeviceToDevice, s));
-    STFT_TRY(hipMemcpy2DAsync(static_cast<float *>(h.held_y[h.held].p) + y_at, (size_t)h.y_rows * sizeof(float), y,
-                              (size_t)samples * sizeof(float), (size_t)samples * sizeof(float), h.B, hipMemcpyDeviceToDevice, s));
-    return LWS_OK;
-}
-
-// the commit steps committed .. committed + nsteps - 1; M < 0 while the stream is open, the frame count at its end
-int misi_launch(lws_misi_stream &h, const float2 *S, const float *A, const float *y, int frames, int samples, float2 *C_out,
-                float *x_out, int out_rows, int out_samples, int nsteps, long long M, hipStream_t s) {
-    const bool closing = M >= 0;
-    const int LA = (closing && !h.ran) ? (int)M - 1 : h.LA;   // an end before the first commit: no frame beyond M - 1 to look at
-    const MisiLaPlan p = misi_la_plan(h.N, h.hop, LA, h.K);
-    const Factors fc = factor(h.N);
-    const long long t0 = (long long)h.hop * h.committed, lo = h.perfectrec ? prepad(h.N, h.hop) : 0;
-    const int R = h.N + LA * h.hop, back = h.N / h.hop + 1;
-    MisiStreamArgs a{};
-    RtisiStreamArgs &q = a.r;
-    q.N = h.N; q.odd = fc.odd; q.log2e = fc.log2e; q.hop = h.hop; q.LA = LA; q.iters = h.iters;
-    q.nsteps = nsteps;
-    q.Mrel = closing ? (int)(M - h.committed) : nsteps + LA;
-    q.closing = closing;
-    q.origin = h.committed == 0;
-    q.zero_lo = lo > t0 ? (int)(lo - t0) : 0;
-    q.emit_end = closing && h.perfectrec ? (int)((long long)h.hop * M - t0) : 0x7fffffff;
-    q.base = h.base; q.slot_m = h.slot; q.cur = h.cur;
-    q.nheld = h.ran ? h.LA : (int)h.entered;   // before the first launch: the stashed frames (the chunk's are not counted yet)
-    q.held_rows = h.LA;
-    q.chunk_rows = frames; q.out_rows = out_rows; q.out_samples = out_samples;
-    q.state_floats = h.source_floats;
-    a.K = h.K;
-    a.frame0 = h.committed < back ? -(int)h.committed : -back;
-    a.ny_held = h.ran ? R - h.hop : (int)(lo + misi_need(h, h.entered));
-    a.ny_chunk = samples;
-    a.y_rows = h.y_rows;
-    a.y_keep = R - h.hop;
-    a.stream_floats = h.stream_floats;
-    const int nxt = h.held ^ 1;
-    const bool given = h.start == LWS_START_GIVEN;   // any other start projects at entry: it keeps the magnitudes without iterations too
-    const MisiStreamHeld held{static_cast<const float2 *>(h.held_s[h.held].p), static_cast<const float *>(h.held_a[h.held].p),
-                              static_cast<const float *>(h.held_y[h.held].p),
-                              closing || h.iters > 0 ? nullptr : static_cast<float2 *>(h.held_s[nxt].p),
-                              closing || (given && h.iters == 0) ? nullptr : static_cast<float *>(h.held_a[nxt].p),
-                              closing ? nullptr : static_cast<float *>(h.held_y[nxt].p)};
-    const float *wa = static_cast<const float *>(h.win_a.p), *ws = static_cast<const float *>(h.win_s.p);
-    float *st = static_cast<float *>(h.state.p);
-    auto *kernel = p.in_lds ? (given ? k_misi_la_stream<true, LWS_START_GIVEN> : k_misi_la_stream<true, LWS_START_MIXTURE>)
-                            : (given ? k_misi_la_stream<false, LWS_START_GIVEN> : k_misi_la_stream<false, LWS_START_MIXTURE>);
-    hipLaunchKernelGGL(kernel, dim3(h.B), dim3(p.threads), p.lds_bytes, s, S, A, y, C_out, x_out, wa, ws, st, held, a);
-    STFT_TRY(hipGetLastError());
-    h.base = (int)(((long long)h.base + (long long)h.hop * nsteps) % R);
-    h.slot = (int)(((long long)h.slot + nsteps) % (LA + 1));
-    h.cur ^= (int)(((long long)h.iters * nsteps) & 1);
-    h.held = nxt;
-    h.committed += nsteps;
-    h.ran = true;
-    return LWS_OK;
-}
-
-}  // namespace
 
 extern "C" int lws_misi_stream_create(int device, int B, int K, int N, int fshift, const double *awin, const double *swin,
                                       int perfectrec, int iters, int look_ahead, lws_misi_stream **out) {
     return lws_misi_stream_create_ex(device, B, K, N, fshift, awin, swin, perfectrec, iters, look_ahead, LWS_START_GIVEN, out);
 }
-
 extern "C" int lws_misi_stream_create_ex(int device, int B, int K, int N, int fshift, const double *awin, const double *swin,
                                          int perfectrec, int iters, int look_ahead, int start, lws_misi_stream **out) {
-    if (!out) return lws::set_error(LWS_ERR_INVALID, "null pointer");
-    *out = nullptr;
-    int rc = check_shape(device, B, 1, N, fshift);
-    if (rc) return rc;
-    if (start != LWS_START_GIVEN && start != LWS_START_MIXTURE) return lws::set_error(LWS_ERR_INVALID, "start %d for online MISI", start);
-    const bool given = start == LWS_START_GIVEN;
-    if (B < 1) return lws::set_error(LWS_ERR_INVALID, "%d streams", B);
-    if (K < 1) return lws::set_error(LWS_ERR_INVALID, "%d sources", K);
-    if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
-    if (look_ahead < 0) return lws::set_error(LWS_ERR_INVALID, "look-ahead of %d frames", look_ahead);
-    if (!awin || !swin) return lws::set_error(LWS_ERR_INVALID, "null pointer");
-    if ((long long)(look_ahead + 2) * fshift + N > 0x7fffffffLL / 2)
-        return lws::set_error(LWS_ERR_UNSUPPORTED, "look-ahead of %d frames", look_ahead);
-    const MisiLaPlan plan = misi_la_plan(N, fshift, look_ahead, K);
-    const size_t frame_floats = (size_t)(look_ahead + 1) * N;
-    const size_t source_floats = plan.in_lds ? plan.source_floats - frame_floats : plan.source_floats;
-    if (2 * ((size_t)K + 1) * plan.source_floats > 0x7fffffffULL)   // the kernel indexes a stream's state, target and xs with ints
-        return lws::set_error(LWS_ERR_UNSUPPORTED, "look-ahead of %d frames", look_ahead);
-    STFT_TRY(hipSetDevice(device));
-    STFT_TRY((lws::allow_dynamic_lds<&k_misi_la_stream<true, LWS_START_GIVEN>>((int)RTISI_LDS_CAP)));
-    STFT_TRY((lws::allow_dynamic_lds<&k_misi_la_stream<false, LWS_START_GIVEN>>(3 * MAXN * (int)sizeof(float2))));
-    STFT_TRY((lws::allow_dynamic_lds<&k_misi_la_stream<true, LWS_START_MIXTURE>>((int)RTISI_LDS_CAP)));
-    STFT_TRY((lws::allow_dynamic_lds<&k_misi_la_stream<false, LWS_START_MIXTURE>>(3 * MAXN * (int)sizeof(float2))));
-    lws_misi_stream *h = new lws_misi_stream;
-    h->start = start;
-    h->device = device; h->B = B; h->K = K; h->N = N; h->hop = fshift; h->LA = look_ahead; h->iters = iters;
-    h->perfectrec = perfectrec ? 1 : 0;
-    h->plan = plan;
-    h->source_floats = source_floats;
-    h->stream_floats = (size_t)K * source_floats + (plan.in_lds ? 0 : ((size_t)K + 1) * ((size_t)N + (size_t)look_ahead * fshift));
-    const size_t F = (size_t)N / 2 + 1, R = (size_t)N + (size_t)look_ahead * fshift;
-    // held samples: the R - hop the next launch still needs; before the first launch, the lead-in (never read) and what was stashed
-    const size_t lo = perfectrec ? (size_t)prepad(N, fshift) : 0, keep = R - fshift;
-    h->y_rows = (int)(keep > lo ? keep : lo) + 1;
-    const size_t state_bytes = (size_t)B * h->stream_floats * sizeof(float), rows = (size_t)B * K * look_ahead * F;
-    const size_t y_bytes = (size_t)B * h->y_rows * sizeof(float);
-    std::vector<float> wa(N), ws(N);
-    for (int i = 0; i < N; ++i) { wa[i] = (float)awin[i]; ws[i] = (float)swin[i]; }
-    rc = h->state.ensure(state_bytes);
-    if (!rc) rc = h->win_a.ensure((size_t)N * sizeof(float));
-    if (!rc) rc = h->win_s.ensure((size_t)N * sizeof(float));
-    if (!rc) rc = h->held_y[0].ensure(y_bytes);
-    if (!rc) rc = h->held_y[1].ensure(y_bytes);
-    if (!rc && (given || iters == 0)) rc = h->held_s[0].ensure(rows * sizeof(float2));   // start rows, or entry rows to return
-    if (!rc && iters == 0) rc = h->held_s[1].ensure(rows * sizeof(float2));
-    if (!rc && (iters > 0 || !given)) rc = h->held_a[0].ensure(rows * sizeof(float));
-    if (!rc && (iters > 0 || !given)) rc = h->held_a[1].ensure(rows * sizeof(float));
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipEventCreateWithFlags(&h->last, hipEventDisableTiming);
-    if (!rc && e == hipSuccess) e = hipMemset(h->state.p, 0, state_bytes);
-    if (!rc && e == hipSuccess) e = hipMemset(h->held_y[0].p, 0, y_bytes);
-    if (!rc && e == hipSuccess) e = hipMemset(h->held_y[1].p, 0, y_bytes);
-    if (!rc && e == hipSuccess) e = hipMemcpy(h->win_a.p, wa.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice);
-    if (!rc && e == hipSuccess) e = hipMemcpy(h->win_s.p, ws.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice);
-    if (!rc && e == hipSuccess) e = hipDeviceSynchronize();   // the state is zero before any stream of the caller's touches it
-    if (!rc && e != hipSuccess) rc = lws::set_error(LWS_ERR_HIP, "creating a stream's state failed: %s", hipGetErrorString(e));
-    if (rc) {
-        lws_misi_stream_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return LWS_OK;
+    return la_create(device, B, K, N, fshift, awin, swin, perfectrec, iters, look_ahead, start, true, out);
 }
-
 extern "C" int lws_misi_stream_push(lws_misi_stream *h, const void *S_dev, const float *A_dev, const float *y_dev, int frames,
                                     int samples, void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out, void *stream) {
-    if (frames_out) *frames_out = 0;
-    if (samples_out) *samples_out = 0;
-    if (!h) return lws::set_error(LWS_ERR_INVALID, "null stream handle");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (frames < 0) return lws::set_error(LWS_ERR_INVALID, "%d frames", frames);
-    if (h->finished) return lws::set_error(LWS_ERR_INVALID, "push after finish");
-    if (((long long)frames + h->LA + 2) * h->hop + h->N > 0x7fffffffLL)
-        return lws::set_error(LWS_ERR_UNSUPPORTED, "%d frames in one push", frames);
-    const long long entered = h->entered + frames, want = misi_need(*h, entered) - misi_need(*h, h->entered);
-    if (samples != want)
-        return lws::set_error(LWS_ERR_INVALID, "%d mixture samples for %d frames after %lld: expected %lld", samples, frames, h->entered,
-                              want);
-    if (frames == 0) return LWS_OK;
-    const bool given = h->start == LWS_START_GIVEN;
-    if ((!S_dev && (given || !A_dev)) || !y_dev)   // magnitudes alone serve any other start
-        return lws::set_error(LWS_ERR_INVALID, "null pointer");
-    const long long nsteps = entered > h->LA ? entered - h->LA - h->committed : 0;
-    if (nsteps > 0 && !C_out_dev) return lws::set_error(LWS_ERR_INVALID, "null pointer");
-    STFT_TRY(hipSetDevice(h->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = misi_enter(*h, s);
-    if (rc) return rc;
-    const float2 *S = static_cast<const float2 *>(S_dev);
-    const size_t bins = (size_t)h->B * h->K * frames * (h->N / 2 + 1);
-    if (!A_dev && (h->iters > 0 || !given)) {   // |S| by the kernel lws_misi_la_dev takes it from
-        if ((rc = h->abuf.ensure(bins * sizeof(float)))) return rc;
-        hipLaunchKernelGGL(k_gla_abs, dim3((unsigned)((bins + 255) / 256)), dim3(256), 0, s, S, static_cast<float *>(h->abuf.p), bins);
-        A_dev = static_cast<const float *>(h->abuf.p);
-    }
-    if (given && h->iters == 0) A_dev = nullptr;
-    if (nsteps == 0) {
-        if ((rc = misi_stash(*h, S, A_dev, y_dev, frames, samples, s))) return rc;
-    } else {
-        const long long t0 = (long long)h->hop * h->committed, lo = h->perfectrec ? prepad(h->N, h->hop) : 0;
-        const long long from = lo > t0 ? lo : t0, to = (long long)h->hop * (h->committed + nsteps);
-        if ((rc = misi_launch(*h, S, A_dev, y_dev, frames, samples, static_cast<float2 *>(C_out_dev), x_out_dev, frames,
-                              frames * h->hop, (int)nsteps, -1, s)))
-            return rc;
-        if (frames_out) *frames_out = (int)nsteps;
-        if (samples_out) *samples_out = to > from ? (int)(to - from) : 0;
-    }
-    h->entered = entered;
-    return misi_leave(*h, s);
+    return la_push(h, S_dev, A_dev, y_dev, frames, samples, C_out_dev, x_out_dev, frames_out, samples_out, stream);
 }
-
 extern "C" int lws_misi_stream_finish(lws_misi_stream *h, void *C_out_dev, float *x_out_dev, int *frames_out, int *samples_out,
                                       void *stream) {
-    if (frames_out) *frames_out = 0;
-    if (samples_out) *samples_out = 0;
-    if (!h) return lws::set_error(LWS_ERR_INVALID, "null stream handle");
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->finished) return lws::set_error(LWS_ERR_INVALID, "finish after finish");
-    const long long M = h->entered, nsteps = M - h->committed;
-    // no step left (nothing pushed, or look_ahead == 0): only the samples behind the last commit, which perfectrec cuts
-    if (nsteps == 0 && (M == 0 || h->perfectrec || !x_out_dev)) {
-        h->finished = true;
-        if (samples_out && M > 0 && !h->perfectrec) *samples_out = h->N - h->hop;
-        return LWS_OK;
-    }
-    if (nsteps > 0 && !C_out_dev) return lws::set_error(LWS_ERR_INVALID, "null pointer");
-    STFT_TRY(hipSetDevice(h->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = misi_enter(*h, s);
-    if (rc) return rc;
-    const long long t0 = (long long)h->hop * h->committed, lo = h->perfectrec ? prepad(h->N, h->hop) : 0;
-    const long long from = lo > t0 ? lo : t0, to = h->perfectrec ? (long long)h->hop * M : (long long)h->hop * (M - 1) + h->N;
-    if ((rc = misi_launch(*h, nullptr, nullptr, nullptr, 0, 0, static_cast<float2 *>(C_out_dev), x_out_dev, h->LA,
-                          h->N + h->LA * h->hop, (int)nsteps, M, s)))
-        return rc;
-    h->finished = true;
-    if (frames_out) *frames_out = (int)nsteps;
-    if (samples_out) *samples_out = to > from ? (int)(to - from) : 0;
-    return misi_leave(*h, s);
+    return la_finish(h, C_out_dev, x_out_dev, frames_out, samples_out, stream);
 }
-
 extern "C" void lws_misi_stream_destroy(lws_misi_stream *h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    for (Scratch *b : {&h->state, &h->held_s[0], &h->held_s[1], &h->held_a[0], &h->held_a[1], &h->held_y[0], &h->held_y[1],
-                       &h->abuf, &h->win_a, &h->win_s})
-        if (b->p) (void)hipFree(b->p);
-    if (h->last) (void)hipEventDestroy(h->last);
+    la_destroy(h);
     delete h;
 }

@@ -726,7 +726,68 @@ def _start_rows(S, magnitudes, start, device):
     return t, A
 
 
-class RtisiLaStream(object):
+class _LaStream(object):
+    """What RtisiLaStream and MisiLaStream share: the checks of their constructors, what push() and finish() hand back, finish(),
+    close().  Tensors are (B,) + _lead + (rows, F) and (B,) + _lead + (samples,), with _lead = (K,) for the sources of a mixture."""
+    _other_start = _create = _finish = _destroy = None   # of the subclass: its start besides 'given', its calls in _capi
+
+    def __init__(self, K, fsize, fshift, awin, swin, iterations, look_ahead, perfectrec, batch, return_signals, device, start):
+        self._h = None
+        n, _ = _gla_args(iterations, 0.0)
+        self.look_ahead = _look_ahead_arg(look_ahead)
+        self.start = _start_arg(start, ('given', self._other_start))
+        if K is not None and (int(K) != K or K < 1):
+            raise ValueError('K must be a positive integer, got %r' % (K,))
+        if batch is not None and (int(batch) != batch or batch < 1):
+            raise ValueError('batch must be None or a positive integer, got %r' % (batch,))
+        if fsize % 2:
+            raise ValueError('Odd ffts not supported.')
+        self.fsize, self.fshift, self.iterations, self.perfectrec = int(fsize), int(fshift), n, perfectrec is True
+        self.batch, self.device = None if batch is None else int(batch), int(device)
+        self._B, self._F = 1 if batch is None else int(batch), int(fsize) // 2 + 1
+        self._lead, self._signals = () if K is None else (int(K),), bool(return_signals)
+        self.finished = False
+        swin = np.squeeze(np.asarray(swin, dtype=np.float64))
+        self._h = type(self)._create(self._B, *self._lead, fsize, fshift, awin, swin, self.perfectrec, n, self.look_ahead,
+                                     device=self.device, start=self.start)
+
+    def _returns(self, out, sig, nf, ns):
+        out = out[..., :nf, :]
+        if self.batch is None:
+            out = out[0]
+        if not self._signals:
+            return out
+        sig = sig[..., :ns]
+        return out, (sig[0] if self.batch is None else sig)
+
+    def finish(self):
+        import torch
+        if self._h is None or self.finished:
+            raise ValueError('finish on a stream that has finished or been closed')
+        dev = torch.device("cuda", self.device)
+        lead = (self._B,) + self._lead
+        out = torch.empty(lead + (self.look_ahead, self._F), dtype=torch.complex64, device=dev)
+        sig = None
+        if self._signals:
+            sig = torch.empty(lead + (self.fsize + self.look_ahead * self.fshift,), dtype=torch.float32, device=dev)
+        nf, ns = type(self)._finish(self._h, out.data_ptr() if out.numel() else None, None if sig is None else sig.data_ptr(),
+                                    stream=torch.cuda.current_stream(dev).cuda_stream)
+        self.finished = True
+        return self._returns(out, sig, nf, ns)
+
+    def close(self):
+        h, self._h = self._h, None
+        if h is not None:
+            type(self)._destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown
+            pass
+
+
+class RtisiLaStream(_LaStream):
     """rtisi_la_dev() for frames that arrive over time (k_rtisi_stream of lws_gla.hip): push() takes the next rows, (Tc, F) -- or
     (B, Tc, F) for `batch`=B streams side by side -- numpy or torch, and returns the rows that could be committed, a new complex64
     torch tensor (n, F) / (B, n, F): frame m is committed once frame m + look_ahead has been pushed, so n may be 0.  finish() returns
@@ -737,33 +798,12 @@ class RtisiLaStream(object):
     themselves, with the same latency.  start='overlap' drives the stream from magnitudes alone, as rtisi_la(..., start='overlap')
     does: push(A) then takes real or complex rows, reads only their magnitudes (or `magnitudes`), and iterations=0 returns the entry
     estimates.  close() frees the device state (also on deletion)."""
+    _other_start, _create, _finish, _destroy = 'overlap', _capi.rtisi_stream_create, _capi.rtisi_stream_finish, _capi.rtisi_stream_destroy
 
     def __init__(self, fsize, fshift, awin, swin, iterations, look_ahead=3, perfectrec=False, batch=None, return_signal=False, device=0,
                  start='given'):
-        self._h = None
-        n, _ = _gla_args(iterations, 0.0)
-        self.look_ahead = _look_ahead_arg(look_ahead)
-        self.start = _start_arg(start, ('given', 'overlap'))
-        if batch is not None and (int(batch) != batch or batch < 1):
-            raise ValueError('batch must be None or a positive integer, got %r' % (batch,))
-        if fsize % 2:
-            raise ValueError('Odd ffts not supported.')
-        self.fsize, self.fshift, self.iterations, self.perfectrec = int(fsize), int(fshift), n, perfectrec is True
-        self.batch, self.return_signal, self.device = None if batch is None else int(batch), bool(return_signal), int(device)
-        self._B, self._F = 1 if batch is None else int(batch), int(fsize) // 2 + 1
-        self.finished = False
-        swin = np.squeeze(np.asarray(swin, dtype=np.float64))
-        self._h = _capi.rtisi_stream_create(self._B, fsize, fshift, awin, swin, self.perfectrec, n, self.look_ahead, device=self.device,
-                                            start=self.start)
-
-    def _returns(self, out, sig, nf, ns):
-        out = out[:, :nf]
-        if self.batch is None:
-            out = out[0]
-        if not self.return_signal:
-            return out
-        sig = sig[:, :ns]
-        return out, (sig[0] if self.batch is None else sig)
+        _LaStream.__init__(self, None, fsize, fshift, awin, swin, iterations, look_ahead, perfectrec, batch, return_signal, device, start)
+        self.return_signal = self._signals
 
     def push(self, S, magnitudes=None):
         import torch
@@ -786,31 +826,6 @@ class RtisiLaStream(object):
                                              None if sig is None else sig.data_ptr(),
                                              stream=torch.cuda.current_stream(t.device).cuda_stream)
         return self._returns(out, sig, nf, ns)
-
-    def finish(self):
-        import torch
-        if self._h is None or self.finished:
-            raise ValueError('finish on a stream that has finished or been closed')
-        dev = torch.device("cuda", self.device)
-        out = torch.empty((self._B, self.look_ahead, self._F), dtype=torch.complex64, device=dev)
-        sig = None
-        if self.return_signal:
-            sig = torch.empty((self._B, self.fsize + self.look_ahead * self.fshift), dtype=torch.float32, device=dev)
-        nf, ns = _capi.rtisi_stream_finish(self._h, out.data_ptr() if out.numel() else None, None if sig is None else sig.data_ptr(),
-                                           stream=torch.cuda.current_stream(dev).cuda_stream)
-        self.finished = True
-        return self._returns(out, sig, nf, ns)
-
-    def close(self):
-        h, self._h = self._h, None
-        if h is not None:
-            _capi.rtisi_stream_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # interpreter shutdown
-            pass
 
 
 def rtisi_la_dev(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=None, perfectrec=False, return_signal=False,
@@ -1015,7 +1030,7 @@ def misi_la_dev(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3,
     return (out, sig[0] if single else sig) if return_signals else out
 
 
-class MisiLaStream(object):
+class MisiLaStream(_LaStream):
     """misi_la_dev() for frames and mixture that arrive over time (k_misi_la_stream of lws_gla.hip).  push() takes the next rows of the
     K sources, (K, Tc, F) -- or (B, K, Tc, F) for `batch`=B mixtures side by side -- and the next samples_needed(Tc) samples of the
     mixture, (n,) / (B, n), numpy or torch: after M frames the stream has every mixture sample under them, fshift (M - 1) + fsize
@@ -1031,28 +1046,14 @@ class MisiLaStream(object):
     push(A, mixture) then takes real or complex rows, reads only their magnitudes (or `magnitudes`), and iterations=0 returns the
     entry estimates.  A push with another sample count raises ValueError and leaves the stream as it was.  close() frees the device
     state (also on deletion)."""
+    _other_start, _create, _finish, _destroy = 'mixture', _capi.misi_stream_create, _capi.misi_stream_finish, _capi.misi_stream_destroy
 
     def __init__(self, K, fsize, fshift, awin, swin, iterations, look_ahead=3, perfectrec=False, batch=None, return_signals=False,
                  device=0, start='given'):
-        self._h = None
-        n, _ = _gla_args(iterations, 0.0)
-        self.look_ahead = _look_ahead_arg(look_ahead)
-        self.start = _start_arg(start, ('given', 'mixture'))
-        if int(K) != K or K < 1:
-            raise ValueError('K must be a positive integer, got %r' % (K,))
-        if batch is not None and (int(batch) != batch or batch < 1):
-            raise ValueError('batch must be None or a positive integer, got %r' % (batch,))
-        if fsize % 2:
-            raise ValueError('Odd ffts not supported.')
-        self.K, self.fsize, self.fshift, self.iterations, self.perfectrec = int(K), int(fsize), int(fshift), n, perfectrec is True
-        self.batch, self.return_signals, self.device = None if batch is None else int(batch), bool(return_signals), int(device)
-        self._B, self._F = 1 if batch is None else int(batch), int(fsize) // 2 + 1
+        _LaStream.__init__(self, K, fsize, fshift, awin, swin, iterations, look_ahead, perfectrec, batch, return_signals, device, start)
+        self.K, self.return_signals = int(K), self._signals
         self._lo = _perfectrec_prepad(self.fsize, self.fshift) if self.perfectrec else 0
         self._entered = 0
-        self.finished = False
-        swin = np.squeeze(np.asarray(swin, dtype=np.float64))
-        self._h = _capi.misi_stream_create(self._B, self.K, fsize, fshift, awin, swin, self.perfectrec, n, self.look_ahead,
-                                           device=self.device, start=self.start)
 
     def _need(self, M):
         return 0 if M <= 0 else self.fshift * (M - 1) + self.fsize - self._lo
@@ -1060,15 +1061,6 @@ class MisiLaStream(object):
     def samples_needed(self, Tc):
         """The mixture samples the next push of Tc frames must carry."""
         return self._need(self._entered + int(Tc)) - self._need(self._entered)
-
-    def _returns(self, out, sig, nf, ns):
-        out = out[:, :, :nf]
-        if self.batch is None:
-            out = out[0]
-        if not self.return_signals:
-            return out
-        sig = sig[:, :, :ns]
-        return out, (sig[0] if self.batch is None else sig)
 
     def push(self, S, mixture, magnitudes=None):
         import torch
@@ -1097,31 +1089,6 @@ class MisiLaStream(object):
                                             stream=torch.cuda.current_stream(t.device).cuda_stream)
             self._entered += Tc
         return self._returns(out, sig, nf, ns)
-
-    def finish(self):
-        import torch
-        if self._h is None or self.finished:
-            raise ValueError('finish on a stream that has finished or been closed')
-        dev = torch.device("cuda", self.device)
-        out = torch.empty((self._B, self.K, self.look_ahead, self._F), dtype=torch.complex64, device=dev)
-        sig = None
-        if self.return_signals:
-            sig = torch.empty((self._B, self.K, self.fsize + self.look_ahead * self.fshift), dtype=torch.float32, device=dev)
-        nf, ns = _capi.misi_stream_finish(self._h, out.data_ptr() if out.numel() else None, None if sig is None else sig.data_ptr(),
-                                          stream=torch.cuda.current_stream(dev).cuda_stream)
-        self.finished = True
-        return self._returns(out, sig, nf, ns)
-
-    def close(self):
-        h, self._h = self._h, None
-        if h is not None:
-            _capi.misi_stream_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:   # interpreter shutdown
-            pass
 
 
 def extspec(S, L, Q):
