@@ -218,6 +218,29 @@ int lws_consistency_dev(int device, const void *S_dev, int B, int M, int N, int 
 int lws_griffin_lim_dev(int device, void *C_dev, const float *A_dev, int B, int M, int N, int fshift, const double *awin,
                         const double *swin, int perfectrec, int iters, double alpha, double *trace, void *stream);
 
+/* Training through Griffin-Lim (a few unrolled Fast Griffin-Lim steps under a waveform or spectral loss, "deep Griffin-Lim"):
+ * lws_griffin_lim_dev with a tape, and its backward pass.  lws_griffin_lim_tape_dev takes the arguments of lws_griffin_lim_dev
+ * without the trace and with A_dev required, runs the same launches -- C_dev comes back with the bits of lws_griffin_lim_dev -- and
+ * also writes the X of every step, before its projection, to tape_dev[iters][B][M][N/2+1] (complex64; required if iters > 0).
+ * lws_griffin_lim_backward_dev: from the cotangent gC_dev[B][M][N/2+1] (complex64; NULL: zeros) of the returned C = t_iters, the
+ * gradients of the loss with respect to the magnitudes, gA_out[B][M][N/2+1] (float32, required), and the start, gS_out[B][M][N/2+1]
+ * (complex64; NULL: not stored, and the last launch is left out).  Complex gradients are g = dL/dRe + j dL/dIm (dL = Re sum
+ * conj(g) dz).  A_dev, tape_dev and alpha are those of the forward call; alpha is a number, not a variable: it gets no gradient.
+ * The update c_i = t_i + alpha_i (t_i - t_{i-1}) (alpha_1 = 0, alpha_i = alpha after that) is linear in the t's, so the momentum needs
+ * no tape of its own: with gc_i the gradient on c_i and gc_iters = 0 (c_iters is never used), backward from i = iters to 1,
+ * gt = gC for i = iters and (1 + alpha_i) gc_i - alpha_{i+1} gc_{i+1} otherwise; with u = X_i / |X_i| of the tape: gA += Re(conj(u) gt),
+ * gX = j u (A / |X_i|) Im(conj(u) gt) (u = 1 and gX = 0 where |X_i| == 0); gv = N istft(gX / 2, Re gX at the bins 0 and N/2; window
+ * awin); gc_{i-1} = (2/N) stft(gv; window swin) (1/N and no imaginary part at the bins 0 and N/2; the perfectrec cuts carry no
+ * gradient); gS = gc_0.  iters == 0: gA = 0, gS = gC.  Two launches per iteration, as the forward; no atomics, every sum in a fixed
+ * order: results repeat bit for bit.  The calls only enqueue work on `stream`.  Argument errors and status codes as
+ * lws_griffin_lim_dev (alpha outside [0, 1) included); a null A_dev, gA_out or (iters > 0) tape_dev: LWS_ERR_INVALID, before anything
+ * is enqueued. */
+int lws_griffin_lim_tape_dev(int device, void *C_dev, const float *A_dev, int B, int M, int N, int fshift, const double *awin,
+                             const double *swin, int perfectrec, int iters, double alpha, void *tape_dev, void *stream);
+int lws_griffin_lim_backward_dev(int device, const void *gC_dev, const float *A_dev, const void *tape_dev, int B, int M, int N,
+                                 int fshift, const double *awin, const double *swin, int perfectrec, int iters, double alpha,
+                                 float *gA_out, void *gS_out, void *stream);
+
 /* MISI (Multiple Input Spectrogram Inversion, Gunawan & Sen 2010), device resident (lws_gla.hip; the reference has no counterpart):
  * Griffin-Lim on the K sources of each of B mixtures, coupled through the known mixture y.  Iteration i = 1..iters computes
  * x_k = istft(c_k), e = y - sum_k x_k (k ascending), X_k = stft(x_k + e / K), c_k = A X_k / |X_k| (A + 0j where |X_k| == 0); no

@@ -33,7 +33,7 @@ EXPORTS = (
     "lws_nofuture_lws_dev", "lws_online_lws_dev", "lws_residual_dev", "lws_last_kernel_time",
     "lws_last_kernel_name", "lws_generic_stage", "lws_stft_frames", "lws_istft_length", "lws_stft_dev", "lws_istft_dev", "lws_stft_zp_dev",
     "lws_consistency_dev", "lws_griffin_lim_dev", "lws_misi_dev", "lws_rtisi_la_dev", "lws_misi_la_dev",
-    "lws_misi_tape_dev", "lws_misi_backward_dev",
+    "lws_misi_tape_dev", "lws_misi_backward_dev", "lws_griffin_lim_tape_dev", "lws_griffin_lim_backward_dev",
     "lws_rtisi_la_dev_ex", "lws_misi_la_dev_ex", "lws_rtisi_stream_create_ex", "lws_misi_stream_create_ex",
     "lws_rtisi_stream_create", "lws_rtisi_stream_push", "lws_rtisi_stream_finish", "lws_rtisi_stream_destroy", "lws_rtisi_la_placement",
     "lws_misi_stream_create", "lws_misi_stream_push", "lws_misi_stream_finish", "lws_misi_stream_destroy", "lws_hann", "lws_synthwin", "lws_weights_shape", "lws_create_weights",
@@ -109,6 +109,8 @@ def load():
     lib.lws_consistency_dev.argtypes = [ip, vp, ip, ip, ip, ip, vp, vp, ip, vp, vp]
     dp = C.c_double
     lib.lws_griffin_lim_dev.argtypes = [ip, vp, vp, ip, ip, ip, ip, vp, vp, ip, ip, dp, vp, vp]
+    lib.lws_griffin_lim_tape_dev.argtypes = [ip, vp, vp, ip, ip, ip, ip, vp, vp, ip, ip, dp, vp, vp]
+    lib.lws_griffin_lim_backward_dev.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, vp, vp, ip, ip, dp, vp, vp, vp]
     lib.lws_misi_dev.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, vp, vp, vp]
     lib.lws_misi_tape_dev.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, vp, vp, vp]
     lib.lws_misi_backward_dev.argtypes = [ip, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, vp, vp, vp, vp]
@@ -499,6 +501,30 @@ def griffin_lim_dev(C_ptr, A_ptr, B, frames, fsize, fshift, awin, swin, perfectr
                                      w.ctypes.data, int(bool(perfectrec)), int(iterations), float(alpha),
                                      trace.ctypes.data if (want_trace and trace.size) else None, stream))
     return trace
+
+
+def griffin_lim_tape_dev(C_ptr, A_ptr, B, frames, fsize, fshift, awin, swin, perfectrec, iterations, alpha, tape_ptr, device=0,
+                         stream=None):
+    """griffin_lim_dev with a tape: A_ptr is required, tape_ptr is device complex64 [iterations][B][frames][fsize//2+1] for the X of
+    every step before its projection (None only with zero iterations).  C gets the bits griffin_lim_dev gives it.  Only enqueues."""
+    a, w = _win(awin), _win(swin)
+    if a.shape != (int(fsize),) or w.shape != (int(fsize),):
+        raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
+    check(load().lws_griffin_lim_tape_dev(int(device), C_ptr, A_ptr, int(B), int(frames), int(fsize), int(fshift), a.ctypes.data,
+                                          w.ctypes.data, int(bool(perfectrec)), int(iterations), float(alpha), tape_ptr, stream))
+
+
+def griffin_lim_backward_dev(gC_ptr, A_ptr, tape_ptr, B, frames, fsize, fshift, awin, swin, perfectrec, iterations, alpha, gA_ptr,
+                             gS_ptr=None, device=0, stream=None):
+    """The backward pass of griffin_lim_tape_dev: the cotangent gC_ptr (device complex64, as C; None for zeros); A_ptr, tape_ptr and
+    alpha those of the forward call; results to gA_ptr (float32, as A) and gS_ptr (complex64, as the start; None to leave it out).
+    Only enqueues."""
+    a, w = _win(awin), _win(swin)
+    if a.shape != (int(fsize),) or w.shape != (int(fsize),):
+        raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
+    check(load().lws_griffin_lim_backward_dev(int(device), gC_ptr, A_ptr, tape_ptr, int(B), int(frames), int(fsize), int(fshift),
+                                              a.ctypes.data, w.ctypes.data, int(bool(perfectrec)), int(iterations), float(alpha),
+                                              gA_ptr, gS_ptr, stream))
 
 
 def misi_dev(C_ptr, A_ptr, y_ptr, B, K, frames, fsize, fshift, awin, swin, perfectrec, iterations, x_ptr=None, want_trace=False,

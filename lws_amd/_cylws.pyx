@@ -273,6 +273,30 @@ def lws_griffin_lim_dev(int device, C_dev, A_dev, int B, int M, int N, int fshif
     return rc
 
 
+def lws_griffin_lim_tape_dev(int device, C_dev, A_dev, int B, int M, int N, int fshift, awin, swin, int perfectrec, int iters, alpha_,
+                             tape_dev, stream):
+    cdef uintptr_t cd = _addr(C_dev), ad = _addr(A_dev), a = _addr(awin), w = _addr(swin), t = _addr(tape_dev), st = _addr(stream)
+    cdef double alpha = _dbl(alpha_)
+    cdef int rc
+    with nogil:
+        rc = c.lws_griffin_lim_tape_dev(device, <void *>cd, <const float *>ad, B, M, N, fshift, <const double *>a, <const double *>w,
+                                        perfectrec, iters, alpha, <void *>t, <void *>st)
+    return rc
+
+
+def lws_griffin_lim_backward_dev(int device, gC_dev, A_dev, tape_dev, int B, int M, int N, int fshift, awin, swin, int perfectrec,
+                                 int iters, alpha_, gA_out, gS_out, stream):
+    cdef uintptr_t gcd = _addr(gC_dev), ad = _addr(A_dev), t = _addr(tape_dev), a = _addr(awin), w = _addr(swin)
+    cdef uintptr_t ga = _addr(gA_out), gs = _addr(gS_out), st = _addr(stream)
+    cdef double alpha = _dbl(alpha_)
+    cdef int rc
+    with nogil:
+        rc = c.lws_griffin_lim_backward_dev(device, <const void *>gcd, <const float *>ad, <const void *>t, B, M, N, fshift,
+                                            <const double *>a, <const double *>w, perfectrec, iters, alpha, <float *>ga, <void *>gs,
+                                            <void *>st)
+    return rc
+
+
 def lws_misi_dev(int device, C_dev, A_dev, y_dev, int B, int K, int M, int N, int fshift, awin, swin, int perfectrec, int iters,
                  x_dev, trace, stream):
     cdef uintptr_t cd = _addr(C_dev), ad = _addr(A_dev), yd = _addr(y_dev), a = _addr(awin), w = _addr(swin), xd = _addr(x_dev)

@@ -11,10 +11,10 @@
 //                   c, A, t_prev and writes t, c and the per-frame fp64 sums (|c|^2, |X - c|^2) of the consistency pair.
 // An odd last frame pairs with zeros.  The iterate lives in the caller's buffer; the last iteration leaves t_n there.
 //
-// The file: the kernels first -- Griffin-Lim, MISI, RTISI-LA (k_rtisi), online MISI (k_misi_la), their streaming forms and the MISI
-// backward pass, each with its own comment -- then the host half.  The one-shot calls check their arguments and open the same way
-// (GlaCall); the two stream handles are one struct whose every decision is made by the step clock of lws_la_stream.h, plain C++
-// that the CPU tests drive without a device.
+// The file: the kernels first -- Griffin-Lim, MISI, RTISI-LA (k_rtisi), online MISI (k_misi_la), their streaming forms and the backward
+// passes of MISI and of Griffin-Lim, each with its own comment -- then the host half.  The one-shot calls check their arguments and open
+// the same way (GlaCall); the two stream handles are one struct whose every decision is made by the step clock of lws_la_stream.h,
+// plain C++ that the CPU tests drive without a device.
 #include "../../include/lws_hip.h"
 
 #include <hip/hip_runtime.h>
@@ -100,10 +100,12 @@ __device__ __forceinline__ void gla_bin(float2 X, float2 *c, const float *A, flo
 
 // lws.pyx:82-88 for the frames m0, m0 + 1 of the overlap-added signal (length Tfull = hop (M - 1) + N, never stored), then the
 // magnitude projection.  rows (SUMS): [B][M][2] doubles, (sum |c|^2, sum |X - c|^2) of each frame, as k_stft_frames writes them.
-template <bool SUMS>
+// TAPE: X as it stands before the projection also goes to tape[B][M][F], for the backward pass (its transform is an instance of its
+// own, see lws_fft.h, so that the untaped kernels stay what they were).
+template <bool SUMS, bool TAPE>
 __global__ void __launch_bounds__(FFT_THREADS) k_gla_forward(const float *frames, const float *awin, float2 *C, const float *A,
                                                               float2 *T, double *rows, int M, int N, int odd, int log2e, int hop,
-                                                              int zero_lo, int zero_hi, GlaStep st) {
+                                                              int zero_lo, int zero_hi, GlaStep st, float2 *tape) {
     extern __shared__ float2 lds[];
     __shared__ double red[SUMS ? 4 : 1][FFT_THREADS];
     const int m0 = 2 * blockIdx.x, b = blockIdx.y, F = N / 2 + 1;
@@ -118,11 +120,15 @@ __global__ void __launch_bounds__(FFT_THREADS) k_gla_forward(const float *frames
         xa[n] = make_float2(re, im);
     }
     __syncthreads();
-    const float2 *r = fft_lds(xa, ya, N, odd, log2e, -1.0f);
+    const float2 *r = fft_lds<TAPE ? 10 : 0>(xa, ya, N, odd, log2e, -1.0f);
     const size_t base = ((size_t)b * M + m0) * F;
     double p0 = 0, e0 = 0, p1 = 0, e1 = 0;
     for (int k = threadIdx.x; k < F; k += blockDim.x) {
         const float2 zk = r[k], zn = r[k == 0 ? 0 : N - k];
+        if constexpr (TAPE) {
+            tape[base + k] = make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y));
+            if (two) tape[base + F + k] = make_float2(0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x));
+        }
         gla_bin<SUMS>(make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)), C, A, T, base + k, st, p0, e0);
         if (two) gla_bin<SUMS>(make_float2(0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)), C, A, T, base + F + k, st, p1, e1);
     }
@@ -1253,12 +1259,104 @@ __global__ void __launch_bounds__(FFT_THREADS) k_misi_bwd_frames(const float *gs
     }
 }
 
+// ---- Griffin-Lim, backward: the gradient of a loss on t_n with respect to A and the start, from the tape of
+// k_gla_forward<false, true>.  c_i = (1 + alpha_i) t_i - alpha_i t_{i-1} is linear in the t's, so no t is kept: the gradient on t_i
+// is gt_i = (1 + alpha_i) gc_i - alpha_{i+1} gc_{i+1} (gOut for i = n), a two-term recurrence over two gradient buffers.  An
+// iteration runs the forward's two launches the other way: k_gla_bwd_project (gt, the projection's derivative per bin, a raw inverse
+// transform times awin), k_gla_bwd_frames (the overlap-add gathered in its load, a forward transform times swin, weighted).  No
+// atomics: every sum has one owner and a fixed order.
+
+// gt for one bin and misi_bwd_bin's step 3 on it: ga (null: zeros) the gradient on c_i or gOut, gb that on c_{i+1}, read only where
+// its coefficient cb is not zero.  Step 3 is written out again, not shared with misi_bwd_bin: with one function taking gt by value
+// the compiler swaps the operands of two multiplies in k_misi_bwd_project, whose instruction stream is to stay the parent's.
+__device__ __forceinline__ float2 gla_bwd_bin(const float2 *ga, const float2 *gb, float ca, float cb, const float2 *tape,
+                                              const float *A, float *gA, size_t i, bool edge, int first) {
+    float2 g = make_float2(0.f, 0.f);
+    if (ga) {
+        const float2 a = ga[i];
+        g = make_float2(ca * a.x, ca * a.y);
+    }
+    if (cb != 0.f) {
+        const float2 b = gb[i];
+        g = make_float2(g.x - cb * b.x, g.y - cb * b.y);
+    }
+    const float2 X = tape[i];
+    const float mag = sqrtf(X.x * X.x + X.y * X.y);
+    float da = g.x;
+    float2 gX = make_float2(0.f, 0.f);
+    if (mag > 0.f) {
+        const float ux = X.x / mag, uy = X.y / mag;
+        da = ux * g.x + uy * g.y;
+        const float s = (A[i] / mag) * (ux * g.y - uy * g.x);
+        gX = make_float2(-uy * s, ux * s);
+    }
+    gA[i] = first ? da : gA[i] + da;
+    return edge ? make_float2(gX.x, 0.f) : make_float2(0.5f * gX.x, 0.5f * gX.y);
+}
+
+// Steps 0, 3 and 4 for the frames m0 = 2 blockIdx.x and m0 + 1 of spectrogram blockIdx.y: k_misi_bwd_project with gt formed in its
+// load.  The frame buffer it fills is the one k_gla_bwd_frames gathers from.
+__global__ void __launch_bounds__(FFT_THREADS) k_gla_bwd_project(const float2 *ga, const float2 *gb, float ca, float cb,
+                                                                  const float2 *tape, const float *A, float *gA, float *frames,
+                                                                  const float *awin, int M, int N, int odd, int log2e, int first) {
+    extern __shared__ float2 lds[];
+    const int m0 = 2 * blockIdx.x, b = blockIdx.y, F = N / 2 + 1;
+    const bool two = m0 + 1 < M;
+    const size_t base = ((size_t)b * M + m0) * F;
+    float2 *x = lds, *y = lds + N;
+    for (int k = threadIdx.x; k < F; k += blockDim.x) {
+        const bool edge = k == 0 || k == N / 2;
+        const float2 u = gla_bwd_bin(ga, gb, ca, cb, tape, A, gA, base + k, edge, first);
+        const float2 v = two ? gla_bwd_bin(ga, gb, ca, cb, tape, A, gA, base + F + k, edge, first) : make_float2(0.f, 0.f);
+        rtisi_put_pair(x, k, N, u, v);
+    }
+    __syncthreads();
+    const float2 *r = fft_lds<11>(x, y, N, odd, log2e, 1.0f);
+    float *o0 = frames + ((size_t)b * M + m0) * N, *o1 = o0 + N;
+    for (int n = threadIdx.x; n < N; n += blockDim.x) {
+        const float w = awin[n];
+        o0[n] = r[n].x * w;
+        if (two) o1[n] = r[n].y * w;
+    }
+}
+
+// Step 2 for the frames m0, m0 + 1 of spectrogram blockIdx.y: each sample of gv gathered from the frames that cover it as
+// k_gla_forward gathers its signal (gla_sample: ascending frames, zero in the perfectrec cuts, no signal buffer), times swin, one
+// forward transform, then the separation and weights of k_misi_bwd_frames.  gc: where the gradient on c_{i-1} goes.
+__global__ void __launch_bounds__(FFT_THREADS) k_gla_bwd_frames(const float *frames, const float *swin, float2 *gc, int M, int N,
+                                                                 int odd, int log2e, int hop, int zero_lo, int zero_hi) {
+    extern __shared__ float2 lds[];
+    const int m0 = 2 * blockIdx.x, b = blockIdx.y, F = N / 2 + 1;
+    const bool two = m0 + 1 < M;
+    const int t_end = hop * (M - 1) + N - zero_hi;
+    const float *f = frames + (size_t)b * M * N;
+    float2 *xa = lds, *ya = lds + N;
+    for (int n = threadIdx.x; n < N; n += blockDim.x) {
+        const float w = swin[n];
+        const float re = gla_sample(f, m0 * hop + n, M, N, hop, zero_lo, t_end) * w;
+        const float im = two ? gla_sample(f, (m0 + 1) * hop + n, M, N, hop, zero_lo, t_end) * w : 0.f;
+        xa[n] = make_float2(re, im);
+    }
+    __syncthreads();
+    const float2 *r = fft_lds<11>(xa, ya, N, odd, log2e, -1.0f);
+    const size_t base = ((size_t)b * M + m0) * F;
+    const float inv = 1.0f / (float)N;
+    for (int k = threadIdx.x; k < F; k += blockDim.x) {
+        const float2 zk = r[k], zn = r[k == 0 ? 0 : N - k];
+        const bool edge = k == 0 || k == N / 2;
+        const float w = edge ? 0.5f * inv : inv;             // (1/2 of the separation) (2/N, or 1/N)
+        gc[base + k] = make_float2(w * (zk.x + zn.x), edge ? 0.f : w * (zk.y - zn.y));
+        if (two) gc[base + F + k] = make_float2(w * (zk.y + zn.y), edge ? 0.f : w * (zn.x - zk.x));
+    }
+}
+
 // ---- The host half.  Windows and scratch of the iteration, one set per device, serialised on the device by the event scheme of
 // lws_stft.hip.  The windows stay on the device between calls: a call with the windows of the previous one uploads nothing.
 struct GlaCtx {
     Scratch frames, t, a, rows, trace, win_a, win_s;
     Scratch delta, sig;                   // MISI: the shared mixture error, and the K overlap-added signals
     Scratch gc;                           // MISI backward: the gradient on the iterate, between the iterations
+    Scratch gc2;                          // Griffin-Lim backward: with gc, the gradients on c_i and c_{i+1}
     Scratch state;                        // RTISI-LA: ring and frames of the workgroups whose state does not fit in LDS
     std::vector<double> host_a, host_s;   // what win_a / win_s hold
     hipEvent_t last = nullptr;
@@ -1303,8 +1401,9 @@ struct LdsOptIn {
     {&lws::allow_dynamic_lds<&kernel<false, start>>, 3 * MAXN * (int)sizeof(float2)}
 #define FFT_OPT_IN(...) {&lws::allow_dynamic_lds<&__VA_ARGS__>, 3 * MAXN * (int)sizeof(float2)}
 const LdsOptIn LDS_OPT_INS[] = {
-    FFT_OPT_IN(k_gla_inverse), FFT_OPT_IN(k_gla_forward<true>), FFT_OPT_IN(k_gla_forward<false>), FFT_OPT_IN(k_misi_forward<false>),
-    FFT_OPT_IN(k_misi_forward<true>), FFT_OPT_IN(k_misi_bwd_project), FFT_OPT_IN(k_misi_bwd_frames),
+    FFT_OPT_IN(k_gla_inverse), FFT_OPT_IN(k_gla_forward<true, false>), FFT_OPT_IN(k_gla_forward<false, false>),
+    FFT_OPT_IN(k_gla_forward<false, true>), FFT_OPT_IN(k_gla_bwd_project), FFT_OPT_IN(k_gla_bwd_frames),
+    FFT_OPT_IN(k_misi_forward<false>), FFT_OPT_IN(k_misi_forward<true>), FFT_OPT_IN(k_misi_bwd_project), FFT_OPT_IN(k_misi_bwd_frames),
     LA_OPT_IN(k_rtisi, LWS_START_GIVEN), LA_OPT_IN(k_rtisi, LWS_START_OVERLAP),
     LA_OPT_IN(k_misi_la, LWS_START_GIVEN), LA_OPT_IN(k_misi_la, LWS_START_MIXTURE),
     LA_OPT_IN(k_rtisi_stream, LWS_START_GIVEN), LA_OPT_IN(k_rtisi_stream, LWS_START_OVERLAP),
@@ -1361,14 +1460,17 @@ struct GlaCall {
 
 }  // namespace
 
-extern "C" int lws_griffin_lim_dev(int device, void *C_dev, const float *A_dev, int B, int M, int N, int fshift,
-                                   const double *awin, const double *swin, int perfectrec, int iters, double alpha,
-                                   double *trace, void *stream) {
+namespace {
+
+// lws_griffin_lim_dev, and with a tape (taped) lws_griffin_lim_tape_dev: the same launches, the forward one writing X as well
+int gla_run(int device, void *C_dev, const float *A_dev, int B, int M, int N, int fshift, const double *awin, const double *swin,
+            int perfectrec, int iters, double alpha, double *trace, float2 *tape, bool taped, void *stream) {
     int rc = check_shape(device, B, M, N, fshift);
     if (rc) return rc;
     if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
     if (!(alpha >= 0.0 && alpha < 1.0)) return lws::set_error(LWS_ERR_INVALID, "momentum %g outside [0, 1)", alpha);
     if (!C_dev || !awin || !swin) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    if (taped && (!A_dev || (iters > 0 && !tape))) return lws::set_error(LWS_ERR_INVALID, "null magnitudes or tape");
     if (iters > 0 && (rc = check_round_trip(M, N, fshift, perfectrec))) return rc;
     if (B == 0 || iters == 0) return LWS_OK;
     GlaCall g(device, stream);
@@ -1389,21 +1491,89 @@ extern "C" int lws_griffin_lim_dev(int device, void *C_dev, const float *A_dev, 
     for (int i = 1; i <= iters; ++i) {
         const GlaStep st{(momentum && i >= 2 && i < iters) ? (float)alpha : 0.f, (momentum && i + 1 < iters) ? 1 : 0};
         hipLaunchKernelGGL(k_gla_inverse, grid, dim3(FFT_THREADS), g.lds, s, C, frames, g.ws, M, N, g.fc.odd, g.fc.log2e);
-        if (trace) {
+        if (taped) {
+            hipLaunchKernelGGL((k_gla_forward<false, true>), grid, dim3(FFT_THREADS), g.lds, s, frames, g.wa, C, A_dev, T,
+                               static_cast<double *>(nullptr), M, N, g.fc.odd, g.fc.log2e, fshift, g.zero_lo, g.zero_hi, st,
+                               tape + (size_t)(i - 1) * bins);
+        } else if (trace) {
             double *rows = static_cast<double *>(c.rows.p);
-            hipLaunchKernelGGL(k_gla_forward<true>, grid, dim3(FFT_THREADS), g.lds, s, frames, g.wa, C, A_dev, T, rows, M, N, g.fc.odd,
-                               g.fc.log2e, fshift, g.zero_lo, g.zero_hi, st);
+            hipLaunchKernelGGL((k_gla_forward<true, false>), grid, dim3(FFT_THREADS), g.lds, s, frames, g.wa, C, A_dev, T, rows, M, N,
+                               g.fc.odd, g.fc.log2e, fshift, g.zero_lo, g.zero_hi, st, static_cast<float2 *>(nullptr));
             hipLaunchKernelGGL(k_gla_sum_rows, dim3((B + 63) / 64), dim3(64), 0, s, rows,
                                static_cast<double *>(c.trace.p) + (size_t)(i - 1) * B * 2, M, B);
         } else {
-            hipLaunchKernelGGL(k_gla_forward<false>, grid, dim3(FFT_THREADS), g.lds, s, frames, g.wa, C, A_dev, T,
-                               static_cast<double *>(nullptr), M, N, g.fc.odd, g.fc.log2e, fshift, g.zero_lo, g.zero_hi, st);
+            hipLaunchKernelGGL((k_gla_forward<false, false>), grid, dim3(FFT_THREADS), g.lds, s, frames, g.wa, C, A_dev, T,
+                               static_cast<double *>(nullptr), M, N, g.fc.odd, g.fc.log2e, fshift, g.zero_lo, g.zero_hi, st,
+                               static_cast<float2 *>(nullptr));
         }
     }
     STFT_TRY(hipGetLastError());
     if (trace) {
         STFT_TRY(hipMemcpyAsync(trace, c.trace.p, (size_t)iters * B * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
         STFT_TRY(hipStreamSynchronize(s));
+    }
+    return g.close();
+}
+
+}  // namespace
+
+extern "C" int lws_griffin_lim_dev(int device, void *C_dev, const float *A_dev, int B, int M, int N, int fshift,
+                                   const double *awin, const double *swin, int perfectrec, int iters, double alpha,
+                                   double *trace, void *stream) {
+    return gla_run(device, C_dev, A_dev, B, M, N, fshift, awin, swin, perfectrec, iters, alpha, trace, nullptr, false, stream);
+}
+
+extern "C" int lws_griffin_lim_tape_dev(int device, void *C_dev, const float *A_dev, int B, int M, int N, int fshift,
+                                        const double *awin, const double *swin, int perfectrec, int iters, double alpha,
+                                        void *tape_dev, void *stream) {
+    return gla_run(device, C_dev, A_dev, B, M, N, fshift, awin, swin, perfectrec, iters, alpha, nullptr,
+                   static_cast<float2 *>(tape_dev), true, stream);
+}
+
+extern "C" int lws_griffin_lim_backward_dev(int device, const void *gC_dev, const float *A_dev, const void *tape_dev, int B, int M,
+                                            int N, int fshift, const double *awin, const double *swin, int perfectrec, int iters,
+                                            double alpha, float *gA_out, void *gS_out, void *stream) {
+    int rc = check_shape(device, B, M, N, fshift);
+    if (rc) return rc;
+    if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
+    if (!(alpha >= 0.0 && alpha < 1.0)) return lws::set_error(LWS_ERR_INVALID, "momentum %g outside [0, 1)", alpha);
+    if (!A_dev || !gA_out || !awin || !swin || (iters > 0 && !tape_dev)) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    if (iters > 0 && (rc = check_round_trip(M, N, fshift, perfectrec))) return rc;
+    if (B == 0) return LWS_OK;
+    GlaCall g(device, stream);
+    if ((rc = g.open(device, N, fshift, awin, swin, perfectrec))) return rc;
+    GlaCtx &c = g.c;
+    hipStream_t s = g.s;
+    const int F = N / 2 + 1;
+    const size_t bins = (size_t)B * M * F;
+    const float2 *gC = static_cast<const float2 *>(gC_dev), *tape = static_cast<const float2 *>(tape_dev);
+    float2 *gS = static_cast<float2 *>(gS_out);
+    if (iters == 0) {   // t_0 is the start itself
+        STFT_TRY(hipMemsetAsync(gA_out, 0, bins * sizeof(float), s));
+        if (gS && gC) STFT_TRY(hipMemcpyAsync(gS, gC, bins * sizeof(float2), hipMemcpyDeviceToDevice, s));
+        if (gS && !gC) STFT_TRY(hipMemsetAsync(gS, 0, bins * sizeof(float2), s));
+        return g.close();
+    }
+    if ((rc = c.frames.ensure((size_t)B * M * N * sizeof(float)))) return rc;
+    if (iters > 1 && (rc = c.gc.ensure(bins * sizeof(float2)))) return rc;
+    if (iters > 2 && (rc = c.gc2.ensure(bins * sizeof(float2)))) return rc;
+    float *frames = static_cast<float *>(c.frames.p);
+    // ga holds the gradient on c_i and gb that on c_{i+1} when step i starts; step i leaves the gradient on c_{i-1} in gb, whose
+    // last reader was this step's first launch, and the two change places.  The first step run (i = iters) reads the caller's
+    // cotangent instead, and the gradient on c_n, which nothing reads, is zero: no second term at i = iters - 1.
+    float2 *ga = static_cast<float2 *>(c.gc2.p), *gb = static_cast<float2 *>(c.gc.p);
+    const dim3 grid((M + 1) / 2, B);
+    for (int i = iters; i >= 1; --i) {
+        const bool entry = i == iters;
+        const float ca = entry ? 1.f : 1.f + (i >= 2 ? (float)alpha : 0.f);
+        const float cb = (entry || i + 1 == iters) ? 0.f : (float)alpha;
+        hipLaunchKernelGGL(k_gla_bwd_project, grid, dim3(FFT_THREADS), g.lds, s, entry ? gC : static_cast<const float2 *>(ga),
+                           static_cast<const float2 *>(gb), ca, cb, tape + (size_t)(i - 1) * bins, A_dev, gA_out, frames, g.wa, M, N,
+                           g.fc.odd, g.fc.log2e, entry ? 1 : 0);
+        if (i == 1 && !gS) break;
+        hipLaunchKernelGGL(k_gla_bwd_frames, grid, dim3(FFT_THREADS), g.lds, s, frames, g.ws, i == 1 ? gS : gb, M, N, g.fc.odd,
+                           g.fc.log2e, fshift, g.zero_lo, g.zero_hi);
+        float2 *sw = ga; ga = gb; gb = sw;
     }
     return g.close();
 }

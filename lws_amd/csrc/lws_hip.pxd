@@ -53,6 +53,11 @@ cdef extern from "lws_hip.h" nogil:
                             const double *swin, int perfectrec, double *out, void *stream)
     int lws_griffin_lim_dev(int device, void *C_dev, const float *A_dev, int B, int M, int N, int fshift, const double *awin,
                             const double *swin, int perfectrec, int iters, double alpha, double *trace, void *stream)
+    int lws_griffin_lim_tape_dev(int device, void *C_dev, const float *A_dev, int B, int M, int N, int fshift, const double *awin,
+                                 const double *swin, int perfectrec, int iters, double alpha, void *tape_dev, void *stream)
+    int lws_griffin_lim_backward_dev(int device, const void *gC_dev, const float *A_dev, const void *tape_dev, int B, int M, int N,
+                                     int fshift, const double *awin, const double *swin, int perfectrec, int iters, double alpha,
+                                     float *gA_out, void *gS_out, void *stream)
     int lws_misi_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, int B, int K, int M, int N, int fshift,
                      const double *awin, const double *swin, int perfectrec, int iters, float *x_dev, double *trace, void *stream)
     int lws_misi_tape_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, int B, int K, int M, int N, int fshift,

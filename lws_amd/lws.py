@@ -609,6 +609,177 @@ def misi_layer(A, S, mixture, fsize, fshift, awin, swin, iterations, perfectrec=
 
 
 # --------------------------------------------------------------------------------------------
+# Training through (Fast) Griffin-Lim (a few unrolled steps under a waveform or spectral loss, "deep Griffin-Lim"): the gradient of a
+# loss on griffin_lim()'s result, host fp64 definition and device form.  Same convention for complex gradients as above.
+# --------------------------------------------------------------------------------------------
+def _gla_backward(tape, A, grad_out, alpha, fsize, fshift, awin, swin, perfectrec=False, _perturb=None):
+    """The backward pass of griffin_lim() from a tape of its projections' arguments: tape (n, B, T, F) the X of the steps 1..n,
+    A (B, T, F), grad_out (B, T, F) complex, the cotangent of t_n, or None for zeros.  Returns (gA, gS); see griffin_lim_grad, which
+    records the tape and calls this."""
+    tape, A = np.asarray(tape, dtype=np.complex128), np.asarray(A, dtype=np.float64)
+    B, T, F = A.shape
+    n = tape.shape[0]
+    gA, gS = np.zeros(A.shape), np.zeros(A.shape, dtype=np.complex128)
+    for b in range(B):
+        gout = np.zeros((T, F), dtype=np.complex128) if grad_out is None else np.asarray(grad_out[b], dtype=np.complex128)
+        gc, gc_next = gout, None            # the gradients on c_i and c_{i+1}; with n == 0 the start is the result
+        for i in range(n, 0, -1):
+            if i == n:                      # step 0: c_n is never used, t_n is the result
+                gt = gout
+            else:
+                gt = (1.0 + (alpha if i >= 2 else 0.0)) * gc
+                if i + 1 < n:               # gc_n = 0
+                    gt = gt - alpha * gc_next
+            X = tape[i - 1, b]
+            mag = np.abs(X)
+            u = np.where(mag > 0, X / np.where(mag > 0, mag, 1.0), 1.0 + 0j)                  # step 3
+            q = np.conj(u) * gt
+            gA[b] += q.real
+            gX = np.where(mag > 0, 1j * u * (A[b] / np.where(mag > 0, mag, 1.0)) * q.imag, 0j)
+            gv = _misi_stft_adjoint(gX, fsize, fshift, awin, perfectrec)                       # step 4
+            if _perturb is not None:
+                gv = np.real(_perturb('gv', i, b, gv))
+            new = _misi_istft_adjoint(gv, T, fsize, fshift, swin, perfectrec)                  # step 2
+            if _perturb is not None:
+                new = _perturb('gc', i - 1, b, new)
+            gc_next, gc = gc, new
+        gS[b] = gc
+    return gA, gS
+
+
+def griffin_lim_grad(S, fsize, fshift, awin, swin, iterations, magnitudes, alpha=0.99, grad_out=None, perfectrec=False,
+                     _perturb=None, _tape=None):
+    """The gradient of a loss L on the result of griffin_lim(S, ..., alpha=alpha, magnitudes=A), in fp64 on the host: the definition
+    the device backward pass (griffin_lim_layer) is held to.  grad_out: the cotangent dL/dRe + j dL/dIm of the returned
+    spectrogram, shaped as S, (T, F) or (B, T, F); None for zeros.  Returns (gA, gS), the gradients on the magnitudes (real) and on
+    the start S (complex, same convention), shaped as S.  A is a variable of its own here: `magnitudes` is required.  alpha is a
+    number, not a variable: it gets no gradient.
+
+    The update c_i = t_i + alpha_i (t_i - t_{i-1}) (alpha_1 = 0, alpha_i = alpha after that) is linear in the t's, so no t is kept:
+    the momentum is a two-term recurrence in the gradients.  With gc_i the gradient on c_i and gc_n = 0 (c_n is never used),
+    backward through step i = n..1 of griffin_lim(), X_i the argument of that step's projection:
+      0. gt = grad_out for i = n, (1 + alpha_i) gc_i - alpha_{i+1} gc_{i+1} otherwise
+      3. u = X_i / |X_i|, q = conj(u) gt;  gA += Re q;  gX = j u (A / |X_i|) Im q   (where |X_i| == 0 the forward gives A + 0j: u = 1, gX = 0)
+      4. gv = N istft(G; window awin), G = gX / 2 on the interior bins and Re gX at the bins 0 and N/2
+      2. gc_{i-1} = (w / N) stft(gv; window swin), w = 2 on the interior bins, 1 and no imaginary part at the bins 0 and N/2 (the
+         perfectrec cuts carry no gradient)
+    and gS = gc_0.  Zero iterations: gA = 0, gS = grad_out.
+    (_perturb(kind, i, b, Z) -> Z: replaces each projection argument, kind 'X', step i; each result of 4, kind 'gv', step i, of
+    which the real part is taken; each result of 2, kind 'gc', the gradient on c_i.  The error model of the tests.
+    _tape: (n, T, F) / (n, B, T, F), the X of every step from elsewhere -- a device run's -- instead of this function's own forward
+    pass: the backward pass alone, teacher-forced.)"""
+    n, alpha = _gla_args(iterations, alpha)
+    S = np.asarray(S)
+    if S.ndim not in (2, 3):
+        raise ValueError('expected a (T, F) spectrogram or a (B, T, F) stack')
+    if magnitudes is None:
+        raise ValueError('griffin_lim_grad differentiates with respect to the magnitudes: give them')
+    A = np.asarray(magnitudes, dtype=np.float64)
+    if A.shape != S.shape:
+        raise ValueError('magnitudes of shape %s for a spectrogram of shape %s' % (A.shape, S.shape))
+    single = S.ndim == 2
+    S3, A3 = (S[None], A[None]) if single else (S, A)
+    tape = np.empty((n,) + S3.shape, dtype=np.complex128)
+
+    def record(i, b, X):
+        if _perturb is not None:
+            X = _perturb('X', i, b, X)
+        tape[i - 1, b] = X
+        return X
+
+    if _tape is None:
+        griffin_lim(S3, fsize, fshift, awin, swin, n, alpha=alpha, magnitudes=A3, perfectrec=perfectrec, _perturb=record)
+    else:
+        tape[...] = np.asarray(_tape).reshape(tape.shape)
+    gC = None
+    if grad_out is not None:
+        gC = np.asarray(grad_out, dtype=np.complex128)
+        if gC.shape != S.shape:
+            raise ValueError('grad_out of shape %s for a spectrogram of shape %s' % (gC.shape, S.shape))
+        gC = gC[None] if single else gC
+    gA, gS = _gla_backward(tape, A3, gC, alpha, fsize, fshift, awin, swin, perfectrec=perfectrec, _perturb=_perturb)
+    return (gA[0], gS[0]) if single else (gA, gS)
+
+
+_gla_function = None
+
+
+def _gla_autograd_function():
+    """The torch.autograd.Function behind griffin_lim_layer, made on first use: importing this module needs no torch."""
+    global _gla_function
+    if _gla_function is not None:
+        return _gla_function
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class GriffinLimLayer(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, A, S, fsize, fshift, awin, swin, n, alpha, perfectrec):
+            dev = S.device
+            B, T, F = (1,) + tuple(S.shape) if S.dim() == 2 else tuple(S.shape)
+            A = A.detach().contiguous()
+            C = S.detach().clone(memory_format=torch.contiguous_format)          # the iteration is in place: never on the caller's storage
+            tape = torch.empty((n, B, T, F), dtype=torch.complex64, device=dev)
+            _capi.griffin_lim_tape_dev(C.data_ptr(), A.data_ptr(), B, T, fsize, fshift, awin, swin, perfectrec, n, alpha,
+                                       tape.data_ptr() if n else None, device=dev.index,
+                                       stream=torch.cuda.current_stream(dev).cuda_stream)
+            ctx.save_for_backward(A, tape)
+            ctx.set_materialize_grads(False)
+            ctx.gla = (B, T, fsize, fshift, awin, swin, perfectrec, n, alpha)
+            return C
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gC):
+            A, tape = ctx.saved_tensors
+            B, T, fsize, fshift, awin, swin, perfectrec, n, alpha = ctx.gla
+            dev = A.device
+            if gC is not None:
+                gC = gC.to(torch.complex64).contiguous()
+            gA = torch.empty_like(A)
+            gS = torch.empty(A.shape, dtype=torch.complex64, device=dev) if ctx.needs_input_grad[1] else None
+            ptr = lambda t: None if t is None else t.data_ptr()
+            _capi.griffin_lim_backward_dev(ptr(gC), A.data_ptr(), tape.data_ptr() if n else None, B, T, fsize, fshift, awin, swin,
+                                           perfectrec, n, alpha, gA.data_ptr(), ptr(gS), device=dev.index,
+                                           stream=torch.cuda.current_stream(dev).cuda_stream)
+            return (gA if ctx.needs_input_grad[0] else None, gS) + (None,) * 7
+
+    _gla_function = GriffinLimLayer
+    return GriffinLimLayer
+
+
+def griffin_lim_layer(A, S, fsize, fshift, awin, swin, iterations, alpha=0.99, perfectrec=False):
+    """griffin_lim_dev(S, ..., alpha=alpha, magnitudes=A) as a differentiable torch operation, for training through a few unrolled
+    (Fast) Griffin-Lim steps: returns C, the spectrogram after `iterations` steps, with the bits griffin_lim_dev gives it, and
+    loss.backward() reaches whichever of A and S require grad (the other gets None).  alpha is a number, not a variable: it gets no
+    gradient.  Takes device tensors, A float32 and S complex64 of shape (T, F) or (B, T, F); does not modify them; runs on the
+    current torch stream and only enqueues work, forward and backward.  Once differentiable.  The forward pass keeps the argument
+    of every projection for the backward pass: a complex64 tape of `iterations` times the size of S, held by the autograd graph
+    until backward() has run (or the result is dropped); the momentum needs no tape of its own.  The backward pass is two launches
+    per iteration, as the forward pass (lws_gla.hip), and repeats bit for bit; its definition is griffin_lim_grad.  Zero
+    iterations: C is a copy of S.  Raises ValueError, as griffin_lim_dev does, for a frame count the round trip does not keep."""
+    import torch
+    n, alpha = _gla_args(iterations, alpha)
+    for name, t, dtype in (('A', A, torch.float32), ('S', S, torch.complex64)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+            raise ValueError('%s must be a %s torch tensor on the device' % (name, str(dtype).replace('torch.', '')))
+    if S.dim() not in (2, 3):
+        raise ValueError('expected a (T, F) spectrogram or a (B, T, F) stack')
+    if A.shape != S.shape:
+        raise ValueError('magnitudes of shape %s for a spectrogram of shape %s' % (tuple(A.shape), tuple(S.shape)))
+    if A.device != S.device:
+        raise ValueError('A and S must be on one device')
+    T, F = S.shape[-2:]
+    if F != fsize // 2 + 1:
+        raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
+    back = _capi.stft_frames(_capi.istft_length(T, fsize, fshift, perfectrec), fsize, fshift, perfectrec)
+    if n > 0 and back != T:
+        raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
+    awin, swin = np.array(awin, dtype=np.float64), np.array(swin, dtype=np.float64)
+    return _gla_autograd_function().apply(A, S, int(fsize), int(fshift), awin, swin, n, alpha, bool(perfectrec))
+
+
+# --------------------------------------------------------------------------------------------
 # RTISI-LA (Zhu, Beauregard & Wyse 2007): Griffin-Lim under a look-ahead -- what online LWS approximates, as batch LWS does Griffin-Lim
 # --------------------------------------------------------------------------------------------
 def _look_ahead_arg(look_ahead):
@@ -1442,6 +1613,17 @@ class lws(object):
         """Host fp64 gradient through misi with this object's windows and perfectrec: (gA, gS, gy), see the module's misi_grad."""
         return misi_grad(S, mixture, self.fsize, self.fshift, self.awin, self.swin, iterations, magnitudes, grad_out=grad_out,
                          grad_signals=grad_signals, perfectrec=self.perfectrec)
+
+    def griffin_lim_grad(self, S, iterations, magnitudes, alpha=0.99, grad_out=None):
+        """Host fp64 gradient through griffin_lim with this object's windows and perfectrec: (gA, gS), see the module's
+        griffin_lim_grad."""
+        return griffin_lim_grad(S, self.fsize, self.fshift, self.awin, self.swin, iterations, magnitudes, alpha=alpha,
+                                grad_out=grad_out, perfectrec=self.perfectrec)
+
+    def griffin_lim_layer(self, A, S, iterations, alpha=0.99):
+        """griffin_lim_dev as a differentiable torch operation on device tensors: C, see the module's griffin_lim_layer."""
+        return griffin_lim_layer(A, S, self.fsize, self.fshift, self.awin, self.swin, iterations, alpha=alpha,
+                                 perfectrec=self.perfectrec)
 
     def misi_layer(self, A, S, mixture, iterations):
         """misi_dev as a differentiable torch operation on device tensors: (C, s), see the module's misi_layer."""
