@@ -313,6 +313,34 @@ enum {
 int lws_rtisi_la_dev_ex(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift,
                         const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, int start, void *stream);
 
+/* Training through RTISI-LA (a model that will run under the causal iteration at inference is trained through it): lws_rtisi_la_dev
+ * with a tape, and its backward pass; LWS_START_GIVEN only.  lws_rtisi_la_tape_dev takes the arguments of lws_rtisi_la_dev with A_dev
+ * required, runs the same iteration -- C_dev and x_dev come back with the bits of lws_rtisi_la_dev -- and also writes the argument X of
+ * every projection to tape_dev[B][M][iters][LA + 1][N/2+1] (complex64; required if iters > 0), LA = min(look_ahead, M - 1): row
+ * [b][m][it - 1][j - m] is frame j in inner iteration `it` of commit step m; rows of frames beyond last = min(m + LA, M - 1) are
+ * neither written nor read.
+ * lws_rtisi_la_backward_dev: from the cotangents gC_dev[B][M][N/2+1] (complex64) of the returned C and gx_dev[B][len] (float32, len =
+ * lws_istft_length(M, ...)) of the signal -- either may be NULL: zeros -- the gradients of the loss with respect to the magnitudes,
+ * gA_out[B][M][N/2+1] (float32, required), and the start, gS_out[B][M][N/2+1] (complex64; NULL: not stored).  Complex gradients are
+ * g = dL/dRe + j dL/dIm.  A_dev, tape_dev, iters and look_ahead are those of the forward call.  With inv_adj(g) = (2/N) rfft(swin g)
+ * (1/N and no imaginary part at the bins 0 and N/2), fwd_adj(gX) = N awin irfft(gX / 2, Re gX at the bins 0 and N/2), v[j] the samples
+ * hop j .. hop j + N of a timeline vector v: gdone = keep gx placed on the uncut timeline, G = 0; for m = M-1 .. 0, for it = iters .. 1:
+ * Gn = 0; for j = m .. last: gf = gdone[m] if (it == iters and j == m) else G[j], gc = inv_adj(gf) (+ gC_m for that same pair), u = X /
+ * |X| of the tape, gA_j += Re(conj(u) gc), gX = j u (A_j / |X|) Im(conj(u) gc) (u = 1, gX = 0 where |X| == 0), Gn[j] += fwd_adj(gX);
+ * then Gn *= keep, gdone += Gn, G = Gn; after the iterations gS_j = inv_adj(G[j]) for the frames that entered in step m.  iters == 0:
+ * gA = 0, gS_m = gC_m + inv_adj(gdone[m]).  One launch, one workgroup per spectrogram; no atomics, every sum in a fixed order: results
+ * repeat bit for bit.  The calls only enqueue work on `stream`.  Argument errors and status codes as lws_rtisi_la_dev; a null A_dev,
+ * gA_out or (iters > 0) tape_dev: LWS_ERR_INVALID, before anything is enqueued.
+ * lws_rtisi_la_bwd_placement: where the backward kernel keeps its state (3 (N + look_ahead fshift) floats) for a look-ahead already
+ * clamped to M - 1, as lws_rtisi_la_placement reports it for the forward kernels. */
+int lws_rtisi_la_tape_dev(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift,
+                          const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *tape_dev,
+                          void *stream);
+int lws_rtisi_la_backward_dev(int device, const void *gC_dev, const float *gx_dev, const float *A_dev, const void *tape_dev, int B, int M,
+                              int N, int fshift, const double *awin, const double *swin, int perfectrec, int iters, int look_ahead,
+                              float *gA_out, void *gS_out, void *stream);
+int lws_rtisi_la_bwd_placement(int N, int fshift, int look_ahead, int *in_lds, int *threads, size_t *lds_bytes);
+
 /* Streaming RTISI-LA (lws_gla.hip): lws_rtisi_la_dev for frames that arrive over time, B streams side by side, the state of the
  * iteration (the overlap-add ring, the windowed inverse frames and the magnitudes of the look_ahead frames still active; per stream)
  * in device memory owned by the handle.  The rows all calls return, one after another, are what one call with every pushed row

@@ -34,6 +34,7 @@ EXPORTS = (
     "lws_last_kernel_name", "lws_generic_stage", "lws_stft_frames", "lws_istft_length", "lws_stft_dev", "lws_istft_dev", "lws_stft_zp_dev",
     "lws_consistency_dev", "lws_griffin_lim_dev", "lws_misi_dev", "lws_rtisi_la_dev", "lws_misi_la_dev",
     "lws_misi_tape_dev", "lws_misi_backward_dev", "lws_griffin_lim_tape_dev", "lws_griffin_lim_backward_dev",
+    "lws_rtisi_la_tape_dev", "lws_rtisi_la_backward_dev", "lws_rtisi_la_bwd_placement",
     "lws_rtisi_la_dev_ex", "lws_misi_la_dev_ex", "lws_rtisi_stream_create_ex", "lws_misi_stream_create_ex",
     "lws_rtisi_stream_create", "lws_rtisi_stream_push", "lws_rtisi_stream_finish", "lws_rtisi_stream_destroy", "lws_rtisi_la_placement",
     "lws_misi_stream_create", "lws_misi_stream_push", "lws_misi_stream_finish", "lws_misi_stream_destroy", "lws_hann", "lws_synthwin", "lws_weights_shape", "lws_create_weights",
@@ -116,6 +117,9 @@ def load():
     lib.lws_misi_backward_dev.argtypes = [ip, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, vp, vp, vp, vp]
     lib.lws_rtisi_la_dev.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, vp, vp, ip, ip, ip, vp]
     lib.lws_misi_la_dev.argtypes = [ip, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, ip, vp]
+    lib.lws_rtisi_la_tape_dev.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, vp, vp, ip, ip, ip, vp, vp]
+    lib.lws_rtisi_la_backward_dev.argtypes = [ip, vp, vp, vp, vp, ip, ip, ip, ip, vp, vp, ip, ip, ip, vp, vp, vp]
+    lib.lws_rtisi_la_bwd_placement.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(C.c_size_t)]
     lib.lws_rtisi_la_dev_ex.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, vp, vp, ip, ip, ip, ip, vp]
     lib.lws_misi_la_dev_ex.argtypes = [ip, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, ip, ip, ip, vp]
     lib.lws_rtisi_stream_create_ex.argtypes = [ip, ip, ip, ip, vp, vp, ip, ip, ip, ip, C.POINTER(vp)]
@@ -683,3 +687,36 @@ def rtisi_la_placement(fsize, fshift, look_ahead, K=0):
     lds, th, nb = C.c_int(-1), C.c_int(-1), C.c_size_t(0)
     check(load().lws_rtisi_la_placement(int(fsize), int(fshift), int(look_ahead), int(K), C.byref(lds), C.byref(th), C.byref(nb)))
     return bool(lds.value), th.value, nb.value
+
+
+def rtisi_la_bwd_placement(fsize, fshift, look_ahead):
+    """(in_lds, threads, lds_bytes) of the launch lws_rtisi_la_backward_dev makes for this frame size, hop and (clamped) look-ahead:
+    whether the three gradient vectors sit in LDS, the workgroup, the dynamic LDS asked for.  Host only."""
+    lds, th, nb = C.c_int(-1), C.c_int(-1), C.c_size_t(0)
+    check(load().lws_rtisi_la_bwd_placement(int(fsize), int(fshift), int(look_ahead), C.byref(lds), C.byref(th), C.byref(nb)))
+    return bool(lds.value), th.value, nb.value
+
+
+def rtisi_la_tape_dev(C_ptr, A_ptr, x_ptr, B, frames, fsize, fshift, awin, swin, perfectrec, iterations, look_ahead, tape_ptr, device=0,
+                      stream=None):
+    """rtisi_la_dev (start 'given') with a tape: A_ptr is required, tape_ptr is device complex64
+    [B][frames][iterations][min(look_ahead, frames - 1) + 1][fsize//2+1] for the argument of every projection (None only with zero
+    iterations).  C and the signal get the bits rtisi_la_dev gives them.  Only enqueues."""
+    a, w = _win(awin), _win(swin)
+    if a.shape != (int(fsize),) or w.shape != (int(fsize),):
+        raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
+    check(load().lws_rtisi_la_tape_dev(int(device), C_ptr, A_ptr, x_ptr, int(B), int(frames), int(fsize), int(fshift), a.ctypes.data,
+                                       w.ctypes.data, int(bool(perfectrec)), int(iterations), int(look_ahead), tape_ptr, stream))
+
+
+def rtisi_la_backward_dev(gC_ptr, gx_ptr, A_ptr, tape_ptr, B, frames, fsize, fshift, awin, swin, perfectrec, iterations, look_ahead,
+                          gA_ptr, gS_ptr=None, device=0, stream=None):
+    """The backward pass of rtisi_la_tape_dev: cotangents gC_ptr (device complex64, as C) and gx_ptr (device float32, as the signal),
+    either None for zeros; A_ptr, tape_ptr, iterations and look_ahead those of the forward call; results to gA_ptr (float32, as A)
+    and gS_ptr (complex64, as the start; None to leave it out).  Only enqueues."""
+    a, w = _win(awin), _win(swin)
+    if a.shape != (int(fsize),) or w.shape != (int(fsize),):
+        raise ValueError("windows of %d and %d samples for frames of %d" % (a.size, w.size, int(fsize)))
+    check(load().lws_rtisi_la_backward_dev(int(device), gC_ptr, gx_ptr, A_ptr, tape_ptr, int(B), int(frames), int(fsize), int(fshift),
+                                           a.ctypes.data, w.ctypes.data, int(bool(perfectrec)), int(iterations), int(look_ahead),
+                                           gA_ptr, gS_ptr, stream))

@@ -472,6 +472,34 @@ def lws_rtisi_la_placement(int N, int fshift, int look_ahead, int K, in_lds_ref,
     return c.lws_rtisi_la_placement(N, fshift, look_ahead, K, <int *>i, <int *>t, <size_t *>b)
 
 
+def lws_rtisi_la_bwd_placement(int N, int fshift, int look_ahead, in_lds_ref, threads_ref, lds_bytes_ref):
+    cdef uintptr_t i = _addr(in_lds_ref), t = _addr(threads_ref), b = _addr(lds_bytes_ref)
+    return c.lws_rtisi_la_bwd_placement(N, fshift, look_ahead, <int *>i, <int *>t, <size_t *>b)
+
+
+def lws_rtisi_la_tape_dev(int device, C_dev, A_dev, x_dev, int B, int M, int N, int fshift, awin, swin, int perfectrec, int iters,
+                          int look_ahead, tape_dev, stream):
+    cdef uintptr_t cd = _addr(C_dev), ad = _addr(A_dev), xd = _addr(x_dev), a = _addr(awin), w = _addr(swin), t = _addr(tape_dev)
+    cdef uintptr_t st = _addr(stream)
+    cdef int rc
+    with nogil:
+        rc = c.lws_rtisi_la_tape_dev(device, <void *>cd, <const float *>ad, <float *>xd, B, M, N, fshift, <const double *>a,
+                                     <const double *>w, perfectrec, iters, look_ahead, <void *>t, <void *>st)
+    return rc
+
+
+def lws_rtisi_la_backward_dev(int device, gC_dev, gx_dev, A_dev, tape_dev, int B, int M, int N, int fshift, awin, swin, int perfectrec,
+                              int iters, int look_ahead, gA_out, gS_out, stream):
+    cdef uintptr_t gcd = _addr(gC_dev), gxd = _addr(gx_dev), ad = _addr(A_dev), t = _addr(tape_dev), a = _addr(awin), w = _addr(swin)
+    cdef uintptr_t ga = _addr(gA_out), gs = _addr(gS_out), st = _addr(stream)
+    cdef int rc
+    with nogil:
+        rc = c.lws_rtisi_la_backward_dev(device, <const void *>gcd, <const float *>gxd, <const float *>ad, <const void *>t, B, M, N,
+                                         fshift, <const double *>a, <const double *>w, perfectrec, iters, look_ahead, <float *>ga,
+                                         <void *>gs, <void *>st)
+    return rc
+
+
 def lws_hann(int n, int symmetric, int use_offset, out):
     cdef uintptr_t o = _addr(out)
     return c.lws_hann(n, symmetric, use_offset, <double *>o)

@@ -11,8 +11,8 @@
 //                   c, A, t_prev and writes t, c and the per-frame fp64 sums (|c|^2, |X - c|^2) of the consistency pair.
 // An odd last frame pairs with zeros.  The iterate lives in the caller's buffer; the last iteration leaves t_n there.
 //
-// The file: the kernels first -- Griffin-Lim, MISI, RTISI-LA (k_rtisi), online MISI (k_misi_la), their streaming forms and the backward
-// passes of MISI and of Griffin-Lim, each with its own comment -- then the host half.  The one-shot calls check their arguments and open
+// The file: the kernels first -- Griffin-Lim, MISI, RTISI-LA (k_rtisi) and its backward pass (k_rtisi_bwd), online MISI (k_misi_la), their
+// streaming forms and the backward passes of MISI and of Griffin-Lim, each with its own comment -- then the host half.  The one-shot calls check their arguments and open
 // the same way (GlaCall); the two stream handles are one struct whose every decision is made by the step clock of lws_la_stream.h,
 // plain C++ that the CPU tests drive without a device.
 #include "../../include/lws_hip.h"
@@ -292,109 +292,192 @@ __device__ __forceinline__ float2 rtisi_project(float2 X, float a) {
 // f_j = inv(c_j) -- the forward load, projection and inverse of a later pass with last = j - 1, one frame per transform (imaginary
 // half zero), since the load of frame j + 1 reads f_j.  S is not read; without iterations c_j goes where S_j was.  A template
 // parameter, so that the GIVEN instances are the code they were: both kernels sit at the SGPR limit (see the transform call).
-template <bool IN_LDS, int START>
-__global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi(float2 *C, const float *A, float *xout, const float *awin, const float *swin,
-                                                        float *scratch, RtisiArgs a) {
+// The kernel's text is lws_rtisi_march.h, compiled twice: as k_rtisi, and with the flag RTISI_TAPE as k_rtisi_tape<IN_LDS, START> (run
+// under GIVEN only), which also writes every projection argument X to tape[b][m][it-1][j-m][k] for the backward pass.
+#define RTISI_KERNEL k_rtisi
+#define RTISI_TAPE 0
+#define RTISI_TAPE_ARG
+#include "lws_rtisi_march.h"
+#undef RTISI_KERNEL
+#undef RTISI_TAPE
+#undef RTISI_TAPE_ARG
+#define RTISI_KERNEL k_rtisi_tape
+#define RTISI_TAPE 1
+#define RTISI_TAPE_ARG , float2 *tape
+#include "lws_rtisi_march.h"
+#undef RTISI_KERNEL
+#undef RTISI_TAPE
+#undef RTISI_TAPE_ARG
+
+// ---- RTISI-LA, backward: the gradient of a loss on the committed C and on the signal with respect to A and the start, from the tape
+// of k_rtisi_tape (lws.py's rtisi_la_grad is the definition).  One workgroup per spectrogram marches m = M-1 .. 0 and runs the inner
+// iterations of each commit step the other way.  Every active frame was projected from ONE sum, so the gradients on all f_j are
+// windows of one timeline vector and the state is three vectors over the active window [hop m, hop m + R), R = N + LA hop, sample t
+// at index t mod R (base = hop m mod R, counted, not divided):
+//   gdone : the gradient on the committed sum `done`; as the window moves down, the hop samples it gains take the cotangent of the
+//           signal (zero in the perfectrec cuts), and those it loses are no longer read;
+//   G     : the gradient on the f_j of the active frames but m, left by the iteration (or commit step) that read them;
+//   Gn    : the gradient on the sum the iteration under way projected from, swapped with G once it is complete.
+// They live behind the transform buffers in LDS (IN_LDS) or in a slice of device scratch of this workgroup alone.  Per pass `it` =
+// iters .. 1 and pair of active frames (j, j + 1) -- an odd last frame pairs with zeros: load (gf_j + i gf_{j+1}) swin, gf_j =
+// gdone under frame m in pass `iters` and G otherwise; one forward transform; separate and weight into gc_j, gc_{j+1} (the adjoint
+// of the inverse transform), plus the cotangent of C for frame m in pass `iters`; the projection's derivative per bin from the
+// tape, gA accumulated by the one thread that owns the bin; the Hermitian pair gX / 2; one raw inverse transform; times awin,
+// overlap-added into Gn, each sample by its owner, j ascending.  Then Gn *= keep, gdone += Gn, G <-> Gn.  Pass 0 takes the forward
+// half alone for the frames that entered in step m, into gS.  Without iterations pass 0 is all there is: gS_m = gC_m + the adjoint
+// of istft on the signal's cotangent under frame m.  No atomics: one fixed summation order, so a gradient repeats bit for bit.
+// Every loop that encloses a barrier runs over m, it, j or the direction: kernel arguments and counters derived from them alone.
+__device__ __forceinline__ float2 rtisi_bwd_bin(float2 g, float2 X, float a, float *gA, bool edge) {
+    const float mag = sqrtf(X.x * X.x + X.y * X.y);
+    float da = g.x;
+    float2 gX = make_float2(0.f, 0.f);
+    if (mag > 0.f) {
+        const float ux = X.x / mag, uy = X.y / mag;
+        da = ux * g.x + uy * g.y;
+        const float s = (a / mag) * (ux * g.y - uy * g.x);
+        gX = make_float2(-uy * s, ux * s);
+    }
+    *gA += da;
+    return edge ? make_float2(gX.x, 0.f) : make_float2(0.5f * gX.x, 0.5f * gX.y);
+}
+
+// a: RtisiArgs with state_floats = 3 R.  gC, gx, gS may be null (zeros; not wanted).  gA arrives zeroed.
+template <bool IN_LDS>
+__global__ void __launch_bounds__(RTISI_MAX_THREADS) k_rtisi_bwd(const float2 *gC, const float *gx, const float *A, const float2 *tape,
+                                                                 float *gA, float2 *gS, const float *awin, const float *swin,
+                                                                 float *scratch, RtisiArgs a) {
     extern __shared__ float2 lds[];
     const int b = blockIdx.x, N = a.N, F = N / 2 + 1, hop = a.hop, M = a.M, W = a.LA + 1, R = N + a.LA * hop;
     const int t_end = hop * (M - 1) + N - a.zero_hi;
-    float2 *bufA = lds, *bufB = lds + N, *bufC = lds + 2 * N;   // bufC: the twiddle table's place, N not a power of two only
+    float2 *bufA = lds, *bufB = lds + N, *bufC = lds + 2 * N;   // as in k_rtisi
     float *state = IN_LDS ? reinterpret_cast<float *>(lds + (a.odd > 1 ? 3 : 2) * N) : scratch + (size_t)b * a.state_floats;
-    float *ring = state, *fcur = state + R, *fnxt = fcur + (size_t)W * N;
-    float2 *Cb = C + (size_t)b * M * F;
-    const float *Ab = A ? A + (size_t)b * M * F : nullptr;   // null without iterations under GIVEN, and not read then
-    float *xb = xout ? xout + (size_t)b * a.len : nullptr;
-    for (int i = threadIdx.x; i < R; i += blockDim.x) ring[i] = 0.f;
+    float *gdone = state, *G = state + R, *Gn = G + R;
+    const float2 *gCb = gC ? gC + (size_t)b * M * F : nullptr;
+    const float *gxb = gx ? gx + (size_t)b * a.len : nullptr;
+    const float *Ab = A + (size_t)b * M * F;
+    const float2 *tb = tape + (size_t)b * M * a.iters * W * F;   // not read without iterations
+    float *gAb = gA + (size_t)b * M * F;
+    float2 *gSb = gS ? gS + (size_t)b * M * F : nullptr;
+    int base = (hop * (M - 1)) % R;
+    for (int d = threadIdx.x; d < R; d += blockDim.x) {          // the window of the last frame
+        const int t = hop * (M - 1) + d, i = t - a.zero_lo;
+        int pos = base + d;
+        if (pos >= R) pos -= R;
+        gdone[pos] = gxb && t >= a.zero_lo && t < t_end && i < a.len ? gxb[i] : 0.f;
+        G[pos] = 0.f;
+    }
     __syncthreads();
-    int base = 0, slot_m = 0;   // slot_m: the slot of frame m
-    for (int m = 0; m < M; ++m) {
+    for (int m = M - 1; m >= 0; --m) {
         const int last = m + a.LA < M - 1 ? m + a.LA : M - 1;
-        // pass 0: the frames that have not entered, f_j = inv(S_j) or inv of the entry estimate (LA + 1 frames at m = 0, one per step
-        // after that), into fcur; passes 1 .. iters: the active frames, from fcur into fnxt
-        for (int it = 0; it <= a.iters; ++it) {
-            float *dst = it == 0 ? fcur : fnxt;
-            const bool entry = START == LWS_START_OVERLAP && it == 0;   // frames enter one by one, through the projection
-            // pass 0 starts at frame 0 (slot 0) in the first step and at frame m + LA after that: the slot before slot_m, cyclically
-            const int j0 = it > 0 ? m : m == 0 ? 0 : m + a.LA;
-            int slot = it > 0 || m == 0 ? slot_m : slot_m == 0 ? a.LA : slot_m - 1;   // of frame j: j mod (LA + 1), counted, not divided
-            for (int j = j0; j <= last; j += entry ? 1 : 2) {
-                const bool two = !entry && j + 1 <= last;
-                const int upto = entry ? j - 1 : last;   // the frames in the sum the forward load gathers
-                // one transform call for both directions (ph 0: forward, not in pass 0; ph 1: inverse): its uniform state once
+        if (m < M - 1) {   // the window moves down by one hop; G's new samples are not read before Gn has replaced it
+            base -= hop;
+            if (base < 0) base += R;
+            for (int d = threadIdx.x; d < hop; d += blockDim.x) {
+                const int t = hop * m + d, i = t - a.zero_lo;
+                int pos = base + d;
+                if (pos >= R) pos -= R;
+                gdone[pos] = gxb && t >= a.zero_lo && t < t_end && i < a.len ? gxb[i] : 0.f;
+            }
+            __syncthreads();
+        }
+        for (int it = a.iters; it >= 0; --it) {
+            const bool entry = it == 0;   // the forward half alone, into gS
+            if (entry && !gSb) continue;
+            // pass 0 takes the frames that entered in step m: 0 .. last in the first step, m + LA (if there is one) after that;
+            // without iterations frame m itself, from gdone
+            const int j0 = !entry || a.iters == 0 ? m : m == 0 ? 0 : m + a.LA;
+            const int j1 = entry && a.iters == 0 ? m : last;
+            if (!entry)
+                for (int d = threadIdx.x; d < R; d += blockDim.x) Gn[d] = 0.f;   // its last readers are behind a barrier
+            for (int j = j0; j <= j1; j += 2) {
+                const bool two = j + 1 <= j1;
+                const bool head = it == a.iters && j == m;   // undoing done += f_m
+                const float *g0 = head ? gdone : G;
                 float2 *r = bufB;
 #pragma nounroll
-                for (int ph = it == 0 && !entry ? 1 : 0; ph < 2; ++ph) {
+                for (int ph = 0; ph < (entry ? 1 : 2); ++ph) {
                     float2 *x = bufA, *y = bufB;
                     if (ph == 0) {
                         for (int n = threadIdx.x; n < N; n += blockDim.x) {
-                            const float w = awin[n];
-                            const float re = rtisi_sample(ring, fcur, j * hop + n, m, upto, slot_m, base, R, t_end, a) * w;
-                            const float im = two ? rtisi_sample(ring, fcur, (j + 1) * hop + n, m, upto, slot_m, base, R, t_end, a) * w : 0.f;
-                            x[n] = make_float2(re, im);
+                            const float w = swin[n];
+                            int p0 = base + (j - m) * hop + n;   // below 2 R
+                            if (p0 >= R) p0 -= R;
+                            int p1 = p0 + hop;
+                            if (p1 >= R) p1 -= R;
+                            x[n] = make_float2(g0[p0] * w, two ? G[p1] * w : 0.f);
                         }
-                    } else if (it == 0 && !entry) {
-                        const float2 *r0 = Cb + (size_t)j * F, *r1 = r0 + F;
-                        for (int k = threadIdx.x; k < F; k += blockDim.x)
-                            rtisi_put_pair(x, k, N, r0[k], two ? r1[k] : make_float2(0.f, 0.f));
                     } else {
-                        // the projected pair goes where the forward result is not, and where the inverse transform finds room for
-                        // its table behind its second buffer: result in bufB -> (bufA, bufB, table bufC); in bufA -> (bufC, bufA,
-                        // table bufB)
-                        x = r == bufB ? bufA : (a.odd > 1 ? bufC : bufB);
+                        x = r == bufB ? bufA : (a.odd > 1 ? bufC : bufB);   // the buffers: as in k_rtisi
                         y = r;
-                        // an entry row is the result only where nothing iterates on it
-                        const bool commit = entry ? a.iters == 0 : it == a.iters && j == m;
-                        const float *A0 = Ab + (size_t)j * F, *A1 = A0 + F;
+                        const float inv = 1.0f / (float)N;
+                        const float2 *T0 = tb + (((size_t)m * a.iters + (it - 1)) * W + (j - m)) * F;
+                        const float *A0 = Ab + (size_t)j * F;
+                        float *gA0 = gAb + (size_t)j * F;
                         for (int k = threadIdx.x; k < F; k += blockDim.x) {
                             const float2 zk = r[k], zn = r[k == 0 ? 0 : N - k];
-                            const float2 u = rtisi_project(make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)), A0[k]);
+                            const bool edge = k == 0 || k == N / 2;
+                            const float w = edge ? 0.5f * inv : inv;             // (1/2 of the separation) (2/N, or 1/N)
+                            float2 c0 = make_float2(w * (zk.x + zn.x), edge ? 0.f : w * (zk.y - zn.y));
+                            if (head && gCb) {
+                                const float2 c = gCb[(size_t)m * F + k];
+                                c0 = make_float2(c0.x + c.x, c0.y + c.y);
+                            }
+                            const float2 u = rtisi_bwd_bin(c0, T0[k], A0[k], gA0 + k, edge);
                             float2 v = make_float2(0.f, 0.f);
-                            if (two) v = rtisi_project(make_float2(0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)), A1[k]);
-                            if (commit) Cb[(size_t)(entry ? j : m) * F + k] = u;
+                            if (two) {
+                                const float2 c1 = make_float2(w * (zk.y + zn.y), edge ? 0.f : w * (zn.x - zk.x));
+                                v = rtisi_bwd_bin(c1, T0[F + k], A0[F + k], gA0 + F + k, edge);
+                            }
                             rtisi_put_pair(x, k, N, u, v);
                         }
                     }
                     __syncthreads();
-                    // the transform's own uniforms (its strides, quotients and stage masks) are derived here, at the call, from
-                    // values the compiler cannot see through: hoisted over all five loops they cost more SGPRs than a wave has
-                    int n_ = N, odd_ = a.odd, log2e_ = a.log2e;
+                    int n_ = N, odd_ = a.odd, log2e_ = a.log2e;   // derived at the call: see k_rtisi.  An instance of its own
                     asm volatile("" : "+s"(n_), "+s"(odd_), "+s"(log2e_));
-                    r = fft_lds<START == LWS_START_GIVEN ? 1 : 5>(x, y, n_, odd_, log2e_, ph == 0 ? -1.0f : 1.0f);
+                    r = fft_lds<13>(x, y, n_, odd_, log2e_, ph == 0 ? -1.0f : 1.0f);
                 }
-                // times the synthesis window, into the slots of frames j and j + 1
-                const float inv = 1.0f / (float)N;
-                float *o0 = dst + (size_t)slot * N, *o1 = dst + (size_t)(slot < a.LA ? slot + 1 : 0) * N;
-                for (int n = threadIdx.x; n < N; n += blockDim.x) {
-                    const float w = inv * swin[n];
-                    o0[n] = r[n].x * w;
-                    if (two) o1[n] = r[n].y * w;
+                if (entry) {
+                    const float inv = 1.0f / (float)N;
+                    float2 *o0 = gSb + (size_t)j * F;
+                    for (int k = threadIdx.x; k < F; k += blockDim.x) {
+                        const float2 zk = r[k], zn = r[k == 0 ? 0 : N - k];
+                        const bool edge = k == 0 || k == N / 2;
+                        const float w = edge ? 0.5f * inv : inv;
+                        float2 c0 = make_float2(w * (zk.x + zn.x), edge ? 0.f : w * (zk.y - zn.y));
+                        if (head && gCb) {
+                            const float2 c = gCb[(size_t)m * F + k];
+                            c0 = make_float2(c0.x + c.x, c0.y + c.y);
+                        }
+                        o0[k] = c0;
+                        if (two) o0[F + k] = make_float2(w * (zk.y + zn.y), edge ? 0.f : w * (zn.x - zk.x));
+                    }
+                } else {
+                    // Gn += the pair times awin over the samples the two frames cover, each by the thread that owns it
+                    const int span = two ? N + hop : N;
+                    for (int d = threadIdx.x; d < span; d += blockDim.x) {
+                        int pos = base + (j - m) * hop + d;   // below 2 R
+                        if (pos >= R) pos -= R;
+                        float acc = Gn[pos];
+                        if (d < N) acc += r[d].x * awin[d];
+                        if (two && d >= hop) acc += r[d - hop].y * awin[d - hop];
+                        Gn[pos] = acc;
+                    }
                 }
-                __syncthreads();   // r is the next load's buffer, dst the next reader's
-                slot += entry ? 1 : 2;
-                if (slot > a.LA) slot -= W;
-                if (slot > a.LA) slot -= W;   // W == 1
+                __syncthreads();   // r is the next load's buffer, Gn the next pair's
             }
-            if (it > 0) { fnxt = fcur; fcur = dst; }
-        }
-        // done += f_m; what no later frame reaches is final: hop samples, or all N behind the last frame
-        const float *fm = fcur + (size_t)slot_m * N;
-        const int nfinal = m == M - 1 ? N : hop;
-        for (int n = threadIdx.x; n < N; n += blockDim.x) {
-            int pos = base + n;
-            if (pos >= R) pos -= R;
-            const float v = ring[pos] + fm[n];
-            const int t = hop * m + n;
-            if (n < nfinal) {
-                if (xb && t >= a.zero_lo && t < t_end) xb[t - a.zero_lo] = v;
-                ring[pos] = 0.f;
-            } else {
-                ring[pos] = v;
+            if (!entry) {
+                for (int d = threadIdx.x; d < R; d += blockDim.x) {
+                    const int t = hop * m + d;
+                    int pos = base + d;
+                    if (pos >= R) pos -= R;
+                    const float v = t >= a.zero_lo && t < t_end ? Gn[pos] : 0.f;
+                    Gn[pos] = v;
+                    gdone[pos] += v;
+                }
+                __syncthreads();
+                float *sw = G; G = Gn; Gn = sw;
             }
         }
-        base += hop;
-        if (base >= R) base -= R;
-        if (++slot_m > a.LA) slot_m = 0;
-        __syncthreads();
     }
 }
 
@@ -1405,6 +1488,8 @@ const LdsOptIn LDS_OPT_INS[] = {
     FFT_OPT_IN(k_gla_forward<false, true>), FFT_OPT_IN(k_gla_bwd_project), FFT_OPT_IN(k_gla_bwd_frames),
     FFT_OPT_IN(k_misi_forward<false>), FFT_OPT_IN(k_misi_forward<true>), FFT_OPT_IN(k_misi_bwd_project), FFT_OPT_IN(k_misi_bwd_frames),
     LA_OPT_IN(k_rtisi, LWS_START_GIVEN), LA_OPT_IN(k_rtisi, LWS_START_OVERLAP),
+    {&lws::allow_dynamic_lds<&k_rtisi_tape<true, LWS_START_GIVEN>>, (int)RTISI_LDS_CAP}, FFT_OPT_IN(k_rtisi_tape<false, LWS_START_GIVEN>),
+    {&lws::allow_dynamic_lds<&k_rtisi_bwd<true>>, (int)RTISI_LDS_CAP}, FFT_OPT_IN(k_rtisi_bwd<false>),
     LA_OPT_IN(k_misi_la, LWS_START_GIVEN), LA_OPT_IN(k_misi_la, LWS_START_MIXTURE),
     LA_OPT_IN(k_rtisi_stream, LWS_START_GIVEN), LA_OPT_IN(k_rtisi_stream, LWS_START_OVERLAP),
     LA_OPT_IN(k_misi_la_stream, LWS_START_GIVEN), LA_OPT_IN(k_misi_la_stream, LWS_START_MIXTURE),
@@ -1744,9 +1829,80 @@ extern "C" int lws_rtisi_la_dev(int device, void *C_dev, const float *A_dev, flo
                                stream);
 }
 
+namespace {
+
+// The state of k_rtisi_bwd: gdone, G and Gn over the active window, 3 R floats (never more than the forward's R + 2 (LA + 1) N),
+// behind the transform buffers in LDS if that fits, in device scratch otherwise.  The workgroup is the forward's.
+LaPlacement la_bwd_placement(int N, int hop, int LA) {
+    LaPlacement p;
+    p.source_floats = p.all_floats = 3 * ((size_t)N + (size_t)LA * hop);
+    const size_t all = fft_lds_bytes(N) + p.all_floats * sizeof(float);
+    p.in_lds = all <= RTISI_LDS_CAP;
+    p.lds_bytes = p.in_lds ? all : fft_lds_bytes(N);
+    p.threads = la_placement(N, hop, LA, 0).threads;
+    return p;
+}
+
+// lws_rtisi_la_dev_ex, and with a tape (taped, under LWS_START_GIVEN) lws_rtisi_la_tape_dev: the same launch, the projection writing
+// its argument as well
+int rtisi_run(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift, const double *awin,
+              const double *swin, int perfectrec, int iters, int look_ahead, int start, float2 *tape, bool taped, void *stream);
+
+}  // namespace
+
+extern "C" int lws_rtisi_la_bwd_placement(int N, int fshift, int look_ahead, int *in_lds, int *threads, size_t *lds_bytes) {
+    if (N < 1 || fshift < 1 || look_ahead < 0)
+        return lws::set_error(LWS_ERR_INVALID, "placement of N = %d, hop %d, look-ahead %d", N, fshift, look_ahead);
+    const LaPlacement p = la_bwd_placement(N, fshift, look_ahead);
+    if (in_lds) *in_lds = p.in_lds ? 1 : 0;
+    if (threads) *threads = p.threads;
+    if (lds_bytes) *lds_bytes = p.lds_bytes;
+    return LWS_OK;
+}
+
 extern "C" int lws_rtisi_la_dev_ex(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift,
                                    const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, int start,
                                    void *stream) {
+    return rtisi_run(device, C_dev, A_dev, x_dev, B, M, N, fshift, awin, swin, perfectrec, iters, look_ahead, start, nullptr, false,
+                     stream);
+}
+
+extern "C" int lws_rtisi_la_tape_dev(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift,
+                                     const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *tape_dev,
+                                     void *stream) {
+    return rtisi_run(device, C_dev, A_dev, x_dev, B, M, N, fshift, awin, swin, perfectrec, iters, look_ahead, LWS_START_GIVEN,
+                     static_cast<float2 *>(tape_dev), true, stream);
+}
+
+extern "C" int lws_rtisi_la_backward_dev(int device, const void *gC_dev, const float *gx_dev, const float *A_dev, const void *tape_dev,
+                                         int B, int M, int N, int fshift, const double *awin, const double *swin, int perfectrec,
+                                         int iters, int look_ahead, float *gA_out, void *gS_out, void *stream) {
+    int rc = check_shape(device, B, M, N, fshift);
+    if (rc) return rc;
+    if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
+    if (look_ahead < 0) return lws::set_error(LWS_ERR_INVALID, "look-ahead of %d frames", look_ahead);
+    if (!A_dev || !gA_out || !awin || !swin || (iters > 0 && !tape_dev)) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    if (iters > 0 && (rc = check_round_trip(M, N, fshift, perfectrec))) return rc;
+    if (B == 0) return LWS_OK;
+    GlaCall g(device, stream);
+    if ((rc = g.open(device, N, fshift, awin, swin, perfectrec))) return rc;
+    const int F = N / 2 + 1, LA = look_ahead < M - 1 ? look_ahead : M - 1, len = lws_istft_length(M, N, fshift, perfectrec);
+    STFT_TRY(hipMemsetAsync(gA_out, 0, (size_t)B * M * F * sizeof(float), g.s));   // the kernel adds to it
+    if (iters == 0 && !gS_out) return g.close();
+    const LaPlacement p = la_bwd_placement(N, fshift, LA);
+    if (!p.in_lds && (rc = g.c.state.ensure((size_t)B * p.all_floats * sizeof(float)))) return rc;
+    const RtisiArgs a{M, N, g.fc.odd, g.fc.log2e, fshift, LA, iters, g.zero_lo, g.zero_hi, len < 0 ? 0 : len, p.all_floats};
+    float *scratch = p.in_lds ? nullptr : static_cast<float *>(g.c.state.p);
+    auto *kernel = p.in_lds ? k_rtisi_bwd<true> : k_rtisi_bwd<false>;
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(p.threads), p.lds_bytes, g.s, static_cast<const float2 *>(gC_dev), len < 1 ? nullptr : gx_dev,
+                       A_dev, static_cast<const float2 *>(tape_dev), gA_out, static_cast<float2 *>(gS_out), g.wa, g.ws, scratch, a);
+    return g.close();
+}
+
+namespace {
+
+int rtisi_run(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift, const double *awin,
+              const double *swin, int perfectrec, int iters, int look_ahead, int start, float2 *tape, bool taped, void *stream) {
     int rc = check_shape(device, B, M, N, fshift);
     if (rc) return rc;
     if (start != LWS_START_GIVEN && start != LWS_START_OVERLAP) return lws::set_error(LWS_ERR_INVALID, "start %d for RTISI-LA", start);
@@ -1754,6 +1910,7 @@ extern "C" int lws_rtisi_la_dev_ex(int device, void *C_dev, const float *A_dev, 
     if (iters < 0) return lws::set_error(LWS_ERR_INVALID, "%d iterations", iters);
     if (look_ahead < 0) return lws::set_error(LWS_ERR_INVALID, "look-ahead of %d frames", look_ahead);
     if (!C_dev || !awin || !swin) return lws::set_error(LWS_ERR_INVALID, "null pointer");
+    if (taped && (!A_dev || (iters > 0 && !tape))) return lws::set_error(LWS_ERR_INVALID, "null magnitudes or tape");
     if (iters > 0 && (rc = check_round_trip(M, N, fshift, perfectrec))) return rc;
     const int len = lws_istft_length(M, N, fshift, perfectrec);
     if (B == 0 || (given && iters == 0 && (!x_dev || len < 1))) return LWS_OK;   // an entry estimate is a result without iterations too
@@ -1766,11 +1923,18 @@ extern "C" int lws_rtisi_la_dev_ex(int device, void *C_dev, const float *A_dev, 
     if ((iters > 0 || !given) && (rc = magnitudes(A_dev, C, (size_t)B * M * F, g.c.a, g.s))) return rc;   // the entry projection reads A
     const RtisiArgs a{M, N, g.fc.odd, g.fc.log2e, fshift, LA, iters, g.zero_lo, g.zero_hi, len, p.source_floats};
     float *x = len < 1 ? nullptr : x_dev, *scratch = p.in_lds ? nullptr : static_cast<float *>(g.c.state.p);
+    if (taped && iters > 0) {   // without iterations nothing is projected: the untaped kernel
+        auto *kernel = p.in_lds ? k_rtisi_tape<true, LWS_START_GIVEN> : k_rtisi_tape<false, LWS_START_GIVEN>;
+        hipLaunchKernelGGL(kernel, dim3(B), dim3(p.threads), p.lds_bytes, g.s, C, A_dev, x, g.wa, g.ws, scratch, a, tape);
+        return g.close();
+    }
     auto *kernel = p.in_lds ? (given ? k_rtisi<true, LWS_START_GIVEN> : k_rtisi<true, LWS_START_OVERLAP>)
                             : (given ? k_rtisi<false, LWS_START_GIVEN> : k_rtisi<false, LWS_START_OVERLAP>);
     hipLaunchKernelGGL(kernel, dim3(B), dim3(p.threads), p.lds_bytes, g.s, C, A_dev, x, g.wa, g.ws, scratch, a);
     return g.close();
 }
+
+}  // namespace
 
 extern "C" int lws_misi_la_dev(int device, void *C_dev, const float *A_dev, const float *y_dev, float *x_dev, int B, int K, int M, int N,
                                int fshift, const double *awin, const double *swin, int perfectrec, int iters, int look_ahead,

@@ -99,6 +99,13 @@ cdef extern from "lws_hip.h" nogil:
                                void *stream)
     void lws_misi_stream_destroy(lws_misi_stream *h)
     int lws_rtisi_la_placement(int N, int fshift, int look_ahead, int K, int *in_lds, int *threads, size_t *lds_bytes)
+    int lws_rtisi_la_bwd_placement(int N, int fshift, int look_ahead, int *in_lds, int *threads, size_t *lds_bytes)
+    int lws_rtisi_la_tape_dev(int device, void *C_dev, const float *A_dev, float *x_dev, int B, int M, int N, int fshift,
+                              const double *awin, const double *swin, int perfectrec, int iters, int look_ahead, void *tape_dev,
+                              void *stream)
+    int lws_rtisi_la_backward_dev(int device, const void *gC_dev, const float *gx_dev, const float *A_dev, const void *tape_dev, int B,
+                                  int M, int N, int fshift, const double *awin, const double *swin, int perfectrec, int iters,
+                                  int look_ahead, float *gA_out, void *gS_out, void *stream)
     int lws_hann(int n, int symmetric, int use_offset, double *out)
     int lws_synthwin(const double *awin, int fsize, int fshift, const double *swin, double *out)
     int lws_weights_shape(int fsize, int fshift, int use_summarized_weights, int *Qprime, int *Q)

@@ -1035,6 +1035,248 @@ def rtisi_la_dev(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitu
 
 
 # --------------------------------------------------------------------------------------------
+# Training through RTISI-LA: the gradient of a loss on rtisi_la()'s results under start='given', host fp64 definition and device
+# form.  Same convention for complex gradients as misi_grad.  Not covered: start='overlap', online MISI, the streams.
+# --------------------------------------------------------------------------------------------
+def _rtisi_inv_adjoint(g, fsize, swin):
+    """The gradient on c_j, (F,), of a loss whose gradient on f_j = swin irfft(c_j) is g: step 2 of griffin_lim_grad for one frame."""
+    c = np.fft.rfft(swin * g) * (2.0 / fsize)
+    c[0] = 0.5 * c[0].real
+    c[-1] = 0.5 * c[-1].real
+    return c
+
+
+def _rtisi_fwd_adjoint(gX, fsize, awin):
+    """The gradient on the fsize samples under a frame of a loss whose gradient on X = rfft(awin y) is gX: step 4 of
+    griffin_lim_grad for one frame."""
+    G = 0.5 * np.asarray(gX, dtype=np.complex128)
+    G[0] = gX[0].real
+    G[-1] = gX[-1].real
+    return fsize * awin * np.fft.irfft(G, fsize)
+
+
+def _rtisi_backward(tape, A, grad_out, grad_signal, fsize, fshift, awin, swin, LA, perfectrec=False, _perturb=None):
+    """The backward pass of rtisi_la() from a tape of its projections' arguments: tape (B, T, n, min(LA, T-1) + 1, F), row
+    [b, m, it-1, j-m] the X of frame j in inner iteration it of commit step m; A (B, T, F); the cotangents grad_out (B, T, F)
+    complex and grad_signal (B, len), either None for zeros.  Returns (gA, gS); see rtisi_la_grad, which records the tape and
+    calls this."""
+    tape, A = np.asarray(tape, dtype=np.complex128), np.asarray(A, dtype=np.float64)
+    B, T, F = A.shape
+    n = tape.shape[2]
+    total, lo, hi = _misi_cuts(T, fsize, fshift, perfectrec)
+    hi = max(hi, lo)
+    keep = np.zeros(total)
+    keep[lo:hi] = 1.0
+    gA, gS = np.zeros(A.shape), np.zeros(A.shape, dtype=np.complex128)
+    pert = (lambda kind, m, it, b, Z: Z) if _perturb is None else _perturb
+
+    def win(j):
+        return slice(fshift * j, fshift * j + fsize)
+
+    for b in range(B):
+        gdone = np.zeros(total)
+        if grad_signal is not None:
+            gdone[lo:hi] = grad_signal[b]
+        G = np.zeros(total)
+        for m in range(T - 1, -1, -1):
+            last = min(m + LA, T - 1)
+            if n == 0:
+                gS[b, m] = pert('gc', m, 0, b, _rtisi_inv_adjoint(gdone[win(m)], fsize, swin))
+                if grad_out is not None:
+                    gS[b, m] += grad_out[b, m]
+                continue
+            for it in range(n, 0, -1):
+                Gn = np.zeros(total)
+                for j in range(m, last + 1):
+                    head = it == n and j == m                       # undoing `done += f_m`
+                    gc = pert('gc', m, it, b, _rtisi_inv_adjoint(gdone[win(m)] if head else G[win(j)], fsize, swin))
+                    if head and grad_out is not None:
+                        gc = gc + grad_out[b, m]
+                    X = tape[b, m, it - 1, j - m]
+                    mag = np.abs(X)
+                    safe = np.where(mag > 0, mag, 1.0)
+                    u = np.where(mag > 0, X / safe, 1.0 + 0j)
+                    q = np.conj(u) * gc
+                    gA[b, j] += q.real
+                    gX = np.where(mag > 0, 1j * u * (A[b, j] / safe) * q.imag, 0j)
+                    Gn[win(j)] += np.real(pert('gv', m, it, b, _rtisi_fwd_adjoint(gX, fsize, awin)))
+                Gn *= keep                                          # Jacobi: one sum fed every active frame and `done`
+                gdone += Gn
+                G = Gn
+            for j in (range(0, last + 1) if m == 0 else range(m + LA, min(m + LA, T - 1) + 1)):   # the frames that entered in step m
+                gS[b, j] = pert('gc', m, 0, b, _rtisi_inv_adjoint(G[win(j)], fsize, swin))
+    return gA, gS
+
+
+def rtisi_la_grad(S, fsize, fshift, awin, swin, iterations, magnitudes, look_ahead=3, grad_out=None, grad_signal=None,
+                  perfectrec=False, _perturb=None, _tape=None):
+    """The gradient of a loss L on the results of rtisi_la(S, ..., magnitudes=A, return_signal=True, start='given'), in fp64 on the
+    host: the definition the device backward pass (rtisi_la_layer) is held to.  grad_out: the cotangent dL/dRe + j dL/dIm of the
+    returned spectrogram c, shaped as S, (T, F) or (B, T, F); grad_signal: the real cotangent of the returned signal, (len,) /
+    (B, len); either None for zeros.  Returns (gA, gS), the gradients on the magnitudes (real) and on the start S (complex, same
+    convention), shaped as S.  A is a variable of its own here: `magnitudes` is required.  Frame m of c and the samples it finalises
+    depend on no input frame later than m + look_ahead, so rows of gA and gS later than that get nothing from them.
+
+    With N = fsize, hop = fshift, keep and the cuts lo, hi as in rtisi_la, inv_adj(g) = (w / N) rfft(swin g) (w = 2 on the interior
+    bins, 1 and no imaginary part at the bins 0 and N/2) and fwd_adj(gX) = N awin irfft(G) (G = gX / 2 on the interior bins, Re gX
+    at the bins 0 and N/2) -- steps 2 and 4 of griffin_lim_grad for one frame -- X[m, it, j] the argument of the projection of frame
+    j in inner iteration it of commit step m, and v[j] the samples hop j : hop j + N of a timeline vector v:
+      gdone = keep (grad_signal placed at lo:hi)          the gradient on `done`
+      G = 0                                               the gradient on f_j is G[j] for every active frame but m
+      for m = T-1 .. 0, last = min(m + LA, T-1):
+        for it = n .. 1:
+          Gn = 0
+          for j = m .. last, ascending:
+            gf = gdone[m] if (it == n and j == m) else G[j]              undoing `done += f_m`
+            gc = inv_adj(gf), plus grad_out[m] if (it == n and j == m)
+            u = X / |X|, q = conj(u) gc;  gA[j] += Re q;  gX = j u (A_j / |X|) Im q     (u = 1, gX = 0 where |X| == 0)
+            Gn[j] += fwd_adj(gX)
+          Gn *= keep;  gdone += Gn;  G = Gn               Jacobi: one sum fed every active frame and `done`
+        gS[j] = inv_adj(G[j]) for the frames j that entered in step m (0 .. last at m == 0, else m + LA if that is a frame)
+    Because every active frame is projected from one sum, the gradients on all f_j are windows of ONE timeline vector.  The
+    perfectrec cuts carry no gradient.  Zero iterations: gA = 0, gS[m] = grad_out[m] + inv_adj(gdone[m]), the adjoint of istft.
+    (_perturb(kind, m, it, b, Z) -> Z: replaces each stacked projection argument, kind 'X'; each result of inv_adj, kind 'gc' (it
+    = 0 for the rows of gS); each result of fwd_adj, kind 'gv', of which the real part is taken.  The error model of the tests.
+    _tape: (T, n, W, F) / (B, T, n, W, F) with W = min(look_ahead, T - 1) + 1, row [m, it-1, j-m] the X above, from elsewhere -- a
+    device run's -- instead of this function's own forward pass: the backward pass alone, teacher-forced.  Rows beyond `last` are
+    not read.)"""
+    n, _ = _gla_args(iterations, 0.0)
+    LA = _look_ahead_arg(look_ahead)
+    S = np.asarray(S)
+    if S.ndim not in (2, 3):
+        raise ValueError('expected a (T, F) spectrogram or a (B, T, F) stack')
+    if magnitudes is None:
+        raise ValueError('rtisi_la_grad differentiates with respect to the magnitudes: give them')
+    A = np.asarray(magnitudes, dtype=np.float64)
+    if A.shape != S.shape:
+        raise ValueError('magnitudes of shape %s for a spectrogram of shape %s' % (A.shape, S.shape))
+    single = S.ndim == 2
+    S3, A3 = (S[None], A[None]) if single else (S, A)
+    B, T, F = S3.shape
+    if F != fsize // 2 + 1 or fsize % 2:
+        raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
+    awin, swin = np.asarray(awin, dtype=np.float64), np.squeeze(np.asarray(swin, dtype=np.float64))
+    _, lo, hi = _misi_cuts(T, fsize, fshift, perfectrec)
+    length = max(hi - lo, 0)
+    if perfectrec is True and n > 0:
+        back = stft(np.zeros(length), fsize, fshift, awin, perfectrec=True).shape[0]
+        if back != T:
+            raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
+    W = min(LA, T - 1) + 1
+    tape = np.zeros((B, T, n, W, F), dtype=np.complex128)
+
+    def record(m, it, b, X):
+        if _perturb is not None:
+            X = _perturb('X', m, it, b, X)
+        tape[b, m, it - 1, :X.shape[0]] = X
+        return X
+
+    if _tape is None:
+        rtisi_la(S3, fsize, fshift, awin, swin, n, look_ahead=LA, magnitudes=A3, perfectrec=perfectrec, _perturb=record)
+    else:
+        tape[...] = np.asarray(_tape).reshape(tape.shape)
+    gC = gx = None
+    if grad_out is not None:
+        gC = np.asarray(grad_out, dtype=np.complex128)
+        if gC.shape != S.shape:
+            raise ValueError('grad_out of shape %s for a spectrogram of shape %s' % (gC.shape, S.shape))
+        gC = gC[None] if single else gC
+    if grad_signal is not None:
+        gx = np.asarray(grad_signal, dtype=np.float64)
+        if gx.shape != S.shape[:-2] + (length,):
+            raise ValueError('grad_signal of shape %s: expected %s' % (gx.shape, S.shape[:-2] + (length,)))
+        gx = gx[None] if single else gx
+    gA, gS = _rtisi_backward(tape, A3, gC, gx, fsize, fshift, awin, swin, LA, perfectrec=perfectrec, _perturb=_perturb)
+    return (gA[0], gS[0]) if single else (gA, gS)
+
+
+_rtisi_function = None
+
+
+def _rtisi_autograd_function():
+    """The torch.autograd.Function behind rtisi_la_layer, made on first use: importing this module needs no torch."""
+    global _rtisi_function
+    if _rtisi_function is not None:
+        return _rtisi_function
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class RtisiLaLayer(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, A, S, fsize, fshift, awin, swin, n, LA, perfectrec):
+            dev = S.device
+            B, T, F = (1,) + tuple(S.shape) if S.dim() == 2 else tuple(S.shape)
+            length = max(_capi.istft_length(T, fsize, fshift, perfectrec), 0)
+            A = A.detach().contiguous()
+            C = S.detach().clone(memory_format=torch.contiguous_format)          # the iteration is in place: never on the caller's storage
+            sig = torch.empty(tuple(S.shape[:-2]) + (length,), dtype=torch.float32, device=dev)
+            tape = torch.empty((B, T, n, min(LA, T - 1) + 1, F), dtype=torch.complex64, device=dev)
+            _capi.rtisi_la_tape_dev(C.data_ptr(), A.data_ptr(), sig.data_ptr() if length else None, B, T, fsize, fshift, awin, swin,
+                                    perfectrec, n, LA, tape.data_ptr() if n else None, device=dev.index,
+                                    stream=torch.cuda.current_stream(dev).cuda_stream)
+            ctx.save_for_backward(A, tape)
+            ctx.set_materialize_grads(False)
+            ctx.rtisi = (B, T, fsize, fshift, awin, swin, perfectrec, n, LA)
+            return C, sig
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gC, gx):
+            A, tape = ctx.saved_tensors
+            B, T, fsize, fshift, awin, swin, perfectrec, n, LA = ctx.rtisi
+            dev = A.device
+            if gC is not None:
+                gC = gC.to(torch.complex64).contiguous()
+            if gx is not None:
+                gx = gx.to(torch.float32).contiguous() if gx.numel() else None
+            gA = torch.empty_like(A)
+            gS = torch.empty(A.shape, dtype=torch.complex64, device=dev) if ctx.needs_input_grad[1] else None
+            ptr = lambda t: None if t is None else t.data_ptr()
+            _capi.rtisi_la_backward_dev(ptr(gC), ptr(gx), A.data_ptr(), tape.data_ptr() if n else None, B, T, fsize, fshift, awin,
+                                        swin, perfectrec, n, LA, gA.data_ptr(), ptr(gS), device=dev.index,
+                                        stream=torch.cuda.current_stream(dev).cuda_stream)
+            return (gA if ctx.needs_input_grad[0] else None, gS) + (None,) * 7
+
+    _rtisi_function = RtisiLaLayer
+    return RtisiLaLayer
+
+
+def rtisi_la_layer(A, S, fsize, fshift, awin, swin, iterations, look_ahead=3, perfectrec=False, return_signal=False):
+    """rtisi_la_dev(S, ..., magnitudes=A, return_signal=True) as a differentiable torch operation, for training a model through the
+    causal iteration it will run under at inference: returns C, the committed spectrogram, or with return_signal (C, x), with the
+    bits rtisi_la_dev gives them, and loss.backward() reaches whichever of A and S require grad (the other gets None), from a loss
+    on C, on x or on both.  Takes device tensors, A float32 and S complex64 of shape (T, F) or (B, T, F); does not modify them; runs
+    on the current torch stream and only enqueues work, forward and backward.  Once differentiable.  The forward pass keeps the
+    argument of every projection for the backward pass: a complex64 tape of iterations * (LA + 1) times the size of S (LA the
+    look-ahead, at most T - 1), held by the autograd graph until backward() has run (or the results are dropped).  The backward
+    pass is one launch, one workgroup per spectrogram marching over the frames from the last to the first (k_rtisi_bwd of
+    lws_gla.hip), and repeats bit for bit; its definition is rtisi_la_grad.  Zero iterations: C is a copy of S.  Not covered:
+    start='overlap', online MISI and the stream classes.  Raises ValueError, as rtisi_la_dev does, for a frame count the round
+    trip does not keep."""
+    import torch
+    n, _ = _gla_args(iterations, 0.0)
+    LA = _look_ahead_arg(look_ahead)
+    for name, t, dtype in (('A', A, torch.float32), ('S', S, torch.complex64)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+            raise ValueError('%s must be a %s torch tensor on the device' % (name, str(dtype).replace('torch.', '')))
+    if S.dim() not in (2, 3):
+        raise ValueError('expected a (T, F) spectrogram or a (B, T, F) stack')
+    if A.shape != S.shape:
+        raise ValueError('magnitudes of shape %s for a spectrogram of shape %s' % (tuple(A.shape), tuple(S.shape)))
+    if A.device != S.device:
+        raise ValueError('A and S must be on one device')
+    T, F = S.shape[-2:]
+    if F != fsize // 2 + 1:
+        raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
+    back = _capi.stft_frames(_capi.istft_length(T, fsize, fshift, perfectrec), fsize, fshift, perfectrec)
+    if n > 0 and perfectrec and back != T:
+        raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
+    awin, swin = np.array(awin, dtype=np.float64), np.squeeze(np.array(swin, dtype=np.float64))
+    C, x = _rtisi_autograd_function().apply(A, S, int(fsize), int(fshift), awin, swin, n, LA, bool(perfectrec))
+    return (C, x) if return_signal else C
+
+
+# --------------------------------------------------------------------------------------------
 # Online MISI: the K sources of a known mixture under a look-ahead -- MISI as RTISI-LA is Griffin-Lim
 # --------------------------------------------------------------------------------------------
 def misi_la(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=None, perfectrec=False, return_signals=False,
@@ -1640,6 +1882,19 @@ class lws(object):
         return rtisi_la_dev(S, self.fsize, self.fshift, self.awin, self.swin, iterations,
                             look_ahead=self.look_ahead if look_ahead is None else look_ahead, magnitudes=magnitudes,
                             perfectrec=self.perfectrec, return_signal=return_signal, device=self.device, start=start)
+
+    def rtisi_la_grad(self, S, iterations, magnitudes, look_ahead=None, grad_out=None, grad_signal=None):
+        """Host fp64 gradient through rtisi_la with this object's windows, perfectrec and (look_ahead=None) look-ahead: (gA, gS),
+        see the module's rtisi_la_grad."""
+        return rtisi_la_grad(S, self.fsize, self.fshift, self.awin, self.swin, iterations, magnitudes,
+                             look_ahead=self.look_ahead if look_ahead is None else look_ahead, grad_out=grad_out,
+                             grad_signal=grad_signal, perfectrec=self.perfectrec)
+
+    def rtisi_la_layer(self, A, S, iterations, look_ahead=None, return_signal=False):
+        """rtisi_la_dev as a differentiable torch operation on device tensors: C or (C, x), see the module's rtisi_la_layer."""
+        return rtisi_la_layer(A, S, self.fsize, self.fshift, self.awin, self.swin, iterations,
+                              look_ahead=self.look_ahead if look_ahead is None else look_ahead, perfectrec=self.perfectrec,
+                              return_signal=return_signal)
 
     def rtisi_la_stream(self, iterations, look_ahead=None, batch=None, return_signal=False, start='given'):
         """A RtisiLaStream with the windows, look-ahead and device of this object: push() rows as they arrive, then finish()."""
