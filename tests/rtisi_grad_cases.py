@@ -23,6 +23,16 @@ GPU_SHAPES = gla_grad_cases.GPU_SHAPES + [
 ]
 # (look-ahead, iterations): an even look-ahead leaves an odd last pair; 5 exceeds T - 1 on several shapes
 LA_STEPS = [(0, 1), (0, 3), (1, 3), (2, 2), (3, 1), (3, 3), (3, 5), (5, 2)]
+# (fsize, fshift, perfectrec, T): [(look-ahead, iterations, backward state in LDS)] -- both placements of k_rtisi_bwd, asserted on the
+# device through lws_rtisi_la_bwd_placement and on the host against a restatement (tests/test_rtisi_bwd_placement.py).  At (4096, 1024)
+# and LA = 3 the forward kernel's state is in scratch and the backward's in LDS.  N = 3000 is no power of two and has a third transform
+# buffer: LA = 3 asks for 3 * 3000 * 8 + 12 * 7500 = 162000 bytes, 1840 under the cap, with the state at lds + 3 N; LA = 4 for 180000,
+# so the state goes to scratch beside three transform buffers.
+PLACEMENTS = {
+    (2048, 512, False, 6): [(3, 3, True)],
+    (4096, 1024, False, 6): [(3, 2, True), (5, 2, False)],
+    (3000, 1500, False, 6): [(3, 2, True), (4, 2, False)],
+}
 FAR, FAR_CAP = gla_grad_cases.FAR, gla_grad_cases.FAR_CAP   # 1e-3 max|gA|; at most 0.5 % of a spectrogram's gA entries
 START_NOISE = gla_grad_cases.START_NOISE       # 0.1 rad
 SEED = 2900000

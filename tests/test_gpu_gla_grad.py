@@ -22,6 +22,8 @@ capi = lws_amd._capi
 # per (fsize, fshift, perfectrec): [rows, max rel-L2 of gA, max rel-L2 / bar of the whole run (gA, gS), max far fraction of gA,
 # max rel-L2 / bar of the teacher-forced pass, max |lhs - rhs| / bar of the adjoint identity]
 MARGINS = {}
+FIGURES = ("rows", "max_rel_l2_gA", "max_rel_l2_over_bar", "max_far_fraction_gA", "max_teacher_forced_rel_l2_over_bar",
+           "max_adjoint_gap_over_bar")
 RUNS = [(n, alpha) for n in gc.STEPS for alpha in gc.ALPHAS]
 
 
@@ -50,8 +52,49 @@ def run(p, A, S, n, alpha, gC, want_S=True):
     return C, tape, gA, gS
 
 
-def on_device(key):
-    p, A, c0, gC = gc.case(*key)
+class Cases:
+    """Where the checks below take their inputs, host references, error model, forward calls and record from: tests/gla_grad_cases.py,
+    the plan's default windows, the methods of the plan.  tests/test_gpu_windows_grad.py runs the same checks from the window pairs of
+    tests/window_cases.py through the module-level calls."""
+    tag = "gla_grad"
+    ident = staticmethod(gc.ident)
+    host = staticmethod(gc.host)                          # (key, n, alpha) -> ((gA, gS), the same under the error model)
+
+    @staticmethod
+    def case(key):
+        return gc.case(*key)                              # p, A, c0, gC
+
+    @staticmethod
+    def grad(key, n, alpha, **kw):
+        p, A, c0, gC = gc.case(*key)
+        return lws_amd.griffin_lim_grad(c0, p.fsize, p.fshift, p.awin, p.swin, n, A.astype(np.float64), alpha=alpha, grad_out=gC,
+                                        perfectrec=p.perfectrec, **kw)
+
+    @staticmethod
+    def transform_model(seed):
+        return gc.perturbation(seed, kinds=("gc", "gv"))
+
+    @staticmethod
+    def forward(p, A, S, n, alpha):
+        return p.griffin_lim_dev(S, n, alpha=alpha, magnitudes=A), p.griffin_lim_layer(A, S, n, alpha=alpha)
+
+    @staticmethod
+    def seen(A):
+        """(B, T) bool, the frames gA is compared on, or None for all of them: every frame of these cases sounds."""
+        assert A.any(axis=-1).all()
+        return None
+
+    @staticmethod
+    def note(key, rows=0, **figures):
+        """Count `rows` whole-run rows and keep the largest of each figure, named as in FIGURES, for the shape of `key`."""
+        m = margins(key)
+        m[0] += rows
+        for name, v in figures.items():
+            m[FIGURES.index(name)] = max(m[FIGURES.index(name)], v)
+
+
+def on_device(key, src=Cases):
+    p, A, c0, gC = src.case(key)
     return (p,) + tuple(dev(a) for a in (A, c0, gC))
 
 
@@ -60,27 +103,75 @@ def f64(t):
     return a.astype(np.complex128 if np.iscomplexobj(a) else np.float64)
 
 
-def rows_of(name, got, ref, per):
-    """(label, distance, bar) per spectrogram."""
-    return [("%s b=%d" % (name, b), gc.rel(got[b], ref[b]), 3 * gc.rel(per[b], ref[b])) for b in range(ref.shape[0])]
+def rows_of(name, got, ref, per, seen=None):
+    """(label, distance, bar) per spectrogram; seen: (B, T) bool, the frames compared, None for all."""
+    pick = (lambda a, b: a[b]) if seen is None else (lambda a, b: a[b][seen[b]])
+    return [("%s b=%d" % (name, b), gc.rel(pick(got, b), pick(ref, b)), 3 * gc.rel(pick(per, b), pick(ref, b))) for b in range(ref.shape[0])]
+
+
+def check_bits(key, n, alpha, src=Cases):
+    """The tape call and the layer give the bits of griffin_lim_dev, and the last tape entry projected in fp64 is C."""
+    p, A, S, gC = on_device(key, src)
+    top = f64(A).max(axis=(1, 2))
+    want, C = src.forward(p, A, S, n, alpha)
+    C2, tape = run(p, A, S, n, alpha, None)[:2]
+    assert C.dtype == torch.complex64 and torch.equal(C, want) and torch.equal(C2, want)
+    X, a = f64(tape[n - 1]), f64(A)
+    mag = np.abs(X)
+    proj = np.where(mag > 0, a * X / np.where(mag > 0, mag, 1.0), a + 0j)
+    off = (np.abs(proj - f64(C)).max(axis=(1, 2)) / top).max()
+    print("%s %s n=%d alpha=%g: same bits as griffin_lim_dev; the last tape entry projected in fp64 is within %.2e max A "
+          "of C" % (src.tag, src.ident(key), n, alpha, off))
+    assert off <= 2e-6
+    return tape
+
+
+def check_teacher_forced(key, n, alpha, src=Cases):
+    """The device backward pass against the host one fed the device's own tape: the projections' arguments are the same numbers
+    on both sides, so the bar is what the host pass moves when only its transforms are perturbed (three times that)."""
+    p, A, c0, gC = src.case(key)
+    seen = src.seen(A.astype(np.float64))
+    _, tape, gA, gS = run(p, dev(A), dev(c0), n, alpha, dev(gC))
+    kw = dict(_tape=f64(tape))
+    ref = src.grad(key, n, alpha, **kw)
+    per = src.grad(key, n, alpha, _perturb=src.transform_model(n + 29), **kw)
+    for name, got, r, q in zip(("gA", "gS"), (f64(gA), f64(gS)), ref, per):
+        assert np.isfinite(got.view(np.float64)).all()
+        for b, (label, dist, bar) in enumerate(rows_of(name, got, r, q, seen if name == "gA" else None)):
+            if bar == 0 and name == "gA":
+                # one step: gA is Re(conj(u) gOut) per bin and no transform feeds it: nothing was perturbed and the bar above is
+                # no bar.  What is left is that product in float32: |X| by two multiplies, an add and a square root, u by a
+                # division, q by two multiplies and an add -- six roundings of 2^-24 of |gOut| per entry at most, taken as
+                # eight, relative to |gA| of the spectrogram (both norms over the frames compared)
+                assert n == 1
+                on = slice(None) if seen is None else seen[b]
+                bar = 8 * 2.0 ** -24 * np.linalg.norm(gC[b][on].astype(np.complex128)) / np.linalg.norm(r[b][on])
+            print("%s %s n=%d alpha=%g teacher-forced %s: rel-L2 %.3e (bar %.3e)" % (src.tag, src.ident(key), n, alpha, label, dist, bar))
+            src.note(key, max_teacher_forced_rel_l2_over_bar=dist / bar)
+            assert dist <= bar, (label, dist, bar)
+
+
+def check_whole_run(key, n, alpha, src=Cases):
+    p, A, S, gC = on_device(key, src)
+    ref, per = src.host(key, n, alpha)
+    seen = src.seen(f64(A))
+    got = [f64(t) for t in run(p, A, S, n, alpha, gC)[2:]]
+    for name, g, r, q in zip(("gA", "gS"), got, ref, per):
+        assert g.shape == r.shape and np.isfinite(g.view(np.float64)).all()
+        on = seen if name == "gA" else None
+        for b, (label, dist, bar) in enumerate(rows_of(name, g, r, q, on)):
+            far = (gc.far(g[b], r[b]) if on is None else gc.far(g[b][on[b]], r[b][on[b]])) if name == "gA" else 0.0
+            print("%s %s n=%d alpha=%g %s: rel-L2 %.3e (bar %.3e)%s"
+                  % (src.tag, src.ident(key), n, alpha, label, dist, bar, "  far entries %.4f%%" % (100 * far) if name == "gA" else ""))
+            src.note(key, rows=1, max_rel_l2_over_bar=dist / bar, max_far_fraction_gA=far, **({"max_rel_l2_gA": dist} if name == "gA" else {}))
+            assert dist <= bar, (label, dist, bar)
+            assert far <= gc.FAR_CAP, (label, far)
 
 
 @pytest.mark.parametrize("key", gc.GPU_SHAPES, ids=gc.ident)
 def test_same_bits_as_griffin_lim_dev(key):
-    p, A, S, gC = on_device(key)
-    top = f64(A).max(axis=(1, 2))
     for n, alpha in RUNS:
-        want = p.griffin_lim_dev(S, n, alpha=alpha, magnitudes=A)
-        C = p.griffin_lim_layer(A, S, n, alpha=alpha)
-        C2, tape = run(p, A, S, n, alpha, None)[:2]
-        assert C.dtype == torch.complex64 and torch.equal(C, want) and torch.equal(C2, want)
-        X, a = f64(tape[n - 1]), f64(A)
-        mag = np.abs(X)
-        proj = np.where(mag > 0, a * X / np.where(mag > 0, mag, 1.0), a + 0j)
-        off = (np.abs(proj - f64(C)).max(axis=(1, 2)) / top).max()
-        print("gla_grad %s n=%d alpha=%g: same bits as griffin_lim_dev; the last tape entry projected in fp64 is within %.2e max A "
-              "of C" % (gc.ident(key), n, alpha, off))
-        assert off <= 2e-6
+        check_bits(key, n, alpha)
 
 
 @pytest.mark.parametrize("key", gc.GPU_SHAPES, ids=gc.ident)
@@ -124,51 +215,14 @@ def test_adjoint_of_the_forward_kernels(key):
 
 @pytest.mark.parametrize("key", gc.GPU_SHAPES, ids=gc.ident)
 def test_teacher_forced_backward(key):
-    """The device backward pass against the host one fed the device's own tape: the projections' arguments are the same numbers
-    on both sides, so the bar is what the host pass moves when only its transforms are perturbed (three times that)."""
-    p, A, c0, gC = gc.case(*key)
-    dA, dS, dgC = (dev(a) for a in (A, c0, gC))
-    m = margins(key)
     for n, alpha in RUNS:
-        _, tape, gA, gS = run(p, dA, dS, n, alpha, dgC)
-        args = (c0, p.fsize, p.fshift, p.awin, p.swin, n, A.astype(np.float64))
-        kw = dict(alpha=alpha, grad_out=gC, perfectrec=p.perfectrec, _tape=f64(tape))
-        ref = lws_amd.griffin_lim_grad(*args, **kw)
-        per = lws_amd.griffin_lim_grad(*args, _perturb=gc.perturbation(n + 29, kinds=("gc", "gv")), **kw)
-        for name, got, r, q in zip(("gA", "gS"), (f64(gA), f64(gS)), ref, per):
-            assert np.isfinite(got.view(np.float64)).all()
-            for b, (label, dist, bar) in enumerate(rows_of(name, got, r, q)):
-                if bar == 0 and name == "gA":
-                    # one step: gA is Re(conj(u) gOut) per bin and no transform feeds it: nothing was perturbed and the bar above is
-                    # no bar.  What is left is that product in float32: |X| by two multiplies, an add and a square root, u by a
-                    # division, q by two multiplies and an add -- six roundings of 2^-24 of |gOut| per entry at most, taken as
-                    # eight, relative to |gA| of the spectrogram
-                    assert n == 1
-                    bar = 8 * 2.0 ** -24 * np.linalg.norm(gC[b].astype(np.complex128)) / np.linalg.norm(r[b])
-                print("gla_grad %s n=%d alpha=%g teacher-forced %s: rel-L2 %.3e (bar %.3e)" % (gc.ident(key), n, alpha, label, dist, bar))
-                m[4] = max(m[4], dist / bar)
-                assert dist <= bar, (label, dist, bar)
+        check_teacher_forced(key, n, alpha)
 
 
 @pytest.mark.parametrize("key", gc.GPU_SHAPES, ids=gc.ident)
 def test_matches_host(key):
-    p, A, S, gC = on_device(key)
-    m = margins(key)
     for n, alpha in RUNS:
-        ref, per = gc.host(key, n, alpha)
-        got = [f64(t) for t in run(p, A, S, n, alpha, gC)[2:]]
-        for name, g, r, q in zip(("gA", "gS"), got, ref, per):
-            assert g.shape == r.shape and np.isfinite(g.view(np.float64)).all()
-            for b, (label, dist, bar) in enumerate(rows_of(name, g, r, q)):
-                far = gc.far(g[b], r[b]) if name == "gA" else 0.0
-                print("gla_grad %s n=%d alpha=%g %s: rel-L2 %.3e (bar %.3e)%s"
-                      % (gc.ident(key), n, alpha, label, dist, bar, "  far entries %.4f%%" % (100 * far) if name == "gA" else ""))
-                m[0] += 1
-                m[2], m[3] = max(m[2], dist / bar), max(m[3], far)
-                if name == "gA":
-                    m[1] = max(m[1], dist)
-                assert dist <= bar, (label, dist, bar)
-                assert far <= gc.FAR_CAP, (label, far)
+        check_whole_run(key, n, alpha)
 
 
 def test_zero_projection_convention():
@@ -304,17 +358,16 @@ def test_invalid_arguments():
 
 def test_zz_margins_actually_achieved():
     """What the cases above reached, per shape (written to $LWS_MARGINS_DIR/gla_grad_margins.json when that variable names a
-    directory; profiles/gla_grad_margins.json is a copy).  On an MI355X, 288 whole-run rows (gA and gS per spectrogram at 8 shapes,
+    directory; profiles/gla_grad_margins.json is a copy).  On an MI355X, 504 whole-run rows (gA and gS per spectrogram at 14 shapes,
     3 step counts and 2 momenta): rel-L2 of gA 7.2e-8 ... 1.5e-5, every row at most 9.6 % of its bar, no entry of gA beyond 1e-3 max|gA|;
-    288 teacher-forced rows at most 9.7 % of their bar (the n = 1 rows of gA, of their rounding bound; gS at most 2.6 %); the adjoint
-    identity at most 11 % of its bar (3.7e-7 ... 1.8e-4 of |dC||gOut| apart, the host's own truncation); the whole file in 3.4 s."""
+    504 teacher-forced rows at most 9.7 % of their bar (the n = 1 rows of gA, of their rounding bound); the adjoint identity at most
+    19 % of its bar (at hop = N; 11 % on the shapes before it); the six shapes added last -- (512, 128), (600, 150), N = 36, hop = 1,
+    hop = N -- at most 3.2 % whole-run and 8.3 % teacher-forced; the whole file in 3.7 s."""
     if not MARGINS:
         test_matches_host((64, 16, True, 12))
         test_teacher_forced_backward((64, 16, True, 12))
         test_adjoint_of_the_forward_kernels((64, 16, True, 12))
-    report = {"%d,%d,%s" % k: {"rows": v[0], "max_rel_l2_gA": v[1], "max_rel_l2_over_bar": v[2], "max_far_fraction_gA": v[3],
-                               "max_teacher_forced_rel_l2_over_bar": v[4], "max_adjoint_gap_over_bar": v[5]}
-              for k, v in sorted(MARGINS.items())}
+    report = {"%d,%d,%s" % k: dict(zip(FIGURES, v)) for k, v in sorted(MARGINS.items())}
     out = os.environ.get("LWS_MARGINS_DIR", "")
     if out and os.path.isdir(out):
         with open(os.path.join(out, "gla_grad_margins.json"), "w") as f:

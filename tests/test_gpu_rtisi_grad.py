@@ -22,12 +22,11 @@ capi = lws_amd._capi
 # per (fsize, fshift, perfectrec): [rows, max rel-L2 of gA, max rel-L2 / bar of the whole run (gA, gS), max far fraction of gA,
 # max rel-L2 / bar of the teacher-forced pass, max rel-L2 / bar of the tape]
 MARGINS = {}
+FIGURES = ("rows", "max_rel_l2_gA", "max_rel_l2_over_bar", "max_far_fraction_gA", "max_teacher_forced_rel_l2_over_bar",
+           "max_tape_rel_l2_over_bar")
 # (fsize, fshift, perfectrec, T): [(look-ahead, iterations, backward state in LDS)] -- both placements of k_rtisi_bwd, asserted
-# through lws_rtisi_la_bwd_placement.  At (4096, 1024) and LA = 3 the forward kernel's state is in scratch and the backward's in LDS.
-PLACEMENTS = {
-    (2048, 512, False, 6): [(3, 3, True)],
-    (4096, 1024, False, 6): [(3, 2, True), (5, 2, False)],
-}
+# through lws_rtisi_la_bwd_placement; the table is with the cases, where the host tests read it too
+PLACEMENTS = rc.PLACEMENTS
 
 
 def margins(key):
@@ -58,8 +57,40 @@ def run(p, A, S, LA, n, gC, gx, want_S=True):
     return C, x, tape, gA, gS
 
 
-def on_device(key):
-    p, A, c0, gC, gx = rc.case(*key)
+class Cases:
+    """Where the checks below take their inputs, host references, error model and record from: tests/rtisi_grad_cases.py, the plan's
+    default windows.  tests/test_gpu_windows_grad.py runs the same checks from the window pairs of tests/window_cases.py."""
+    tag = "rtisi_grad"
+    ident = staticmethod(rc.ident)
+    host = staticmethod(rc.host)                          # (key, LA, n) -> ((gA, gS), the same under the error model)
+    grad = staticmethod(rc.grad)                          # (key, LA, n, **kw) -> (gA, gS) of lws_amd.rtisi_la_grad
+    host_tape = staticmethod(rc.host_tape)                # (key, LA, n, perturbed=False)
+
+    @staticmethod
+    def note(key, rows=0, **figures):
+        """Count `rows` whole-run rows and keep the largest of each figure, named as in FIGURES, for the shape of `key`."""
+        m = margins(key)
+        m[0] += rows
+        for name, v in figures.items():
+            m[FIGURES.index(name)] = max(m[FIGURES.index(name)], v)
+
+    @staticmethod
+    def case(key):
+        return rc.case(*key)                              # p, A, c0, gC, gx
+
+    @staticmethod
+    def transform_model(seed):
+        return rc.perturbation(seed, kinds=("gc", "gv"))
+
+    @staticmethod
+    def seen(A):
+        """(B, T) bool, the frames gA is compared on, or None for all of them: every frame of these cases sounds."""
+        assert A.any(axis=-1).all()
+        return None
+
+
+def on_device(key, src=Cases):
+    p, A, c0, gC, gx = src.case(key)
     return (p,) + tuple(dev(a) for a in (A, c0, gC, gx))
 
 
@@ -68,60 +99,58 @@ def f64(t):
     return a.astype(np.complex128 if np.iscomplexobj(a) else np.float64)
 
 
-def rows_of(name, got, ref, per):
-    """(label, distance, bar) per spectrogram."""
-    return [("%s b=%d" % (name, b), rc.rel(got[b], ref[b]), 3 * rc.rel(per[b], ref[b])) for b in range(ref.shape[0])]
+def rows_of(name, got, ref, per, seen=None):
+    """(label, distance, bar) per spectrogram; seen: (B, T) bool, the frames compared, None for all."""
+    pick = (lambda a, b: a[b]) if seen is None else (lambda a, b: a[b][seen[b]])
+    return [("%s b=%d" % (name, b), rc.rel(pick(got, b), pick(ref, b)), 3 * rc.rel(pick(per, b), pick(ref, b))) for b in range(ref.shape[0])]
 
 
-def check_whole_run(key, LA, n):
-    p, A, S, gC, gx = on_device(key)
-    m = margins(key)
-    ref, per = rc.host(key, LA, n)
+def check_whole_run(key, LA, n, src=Cases):
+    p, A, S, gC, gx = on_device(key, src)
+    ref, per = src.host(key, LA, n)
+    seen = src.seen(f64(A))
     got = [f64(t) for t in run(p, A, S, LA, n, gC, gx)[3:]]
     for name, g, r, q in zip(("gA", "gS"), got, ref, per):
         assert g.shape == r.shape and np.isfinite(g.view(np.float64)).all()
-        for b, (label, dist, bar) in enumerate(rows_of(name, g, r, q)):
-            far = rc.far(g[b], r[b]) if name == "gA" else 0.0
-            print("rtisi_grad %s LA=%d n=%d %s: rel-L2 %.3e (bar %.3e)%s"
-                  % (rc.ident(key), LA, n, label, dist, bar, "  far entries %.4f%%" % (100 * far) if name == "gA" else ""))
-            m[0] += 1
-            m[2], m[3] = max(m[2], dist / bar), max(m[3], far)
-            if name == "gA":
-                m[1] = max(m[1], dist)
+        on = seen if name == "gA" else None
+        for b, (label, dist, bar) in enumerate(rows_of(name, g, r, q, on)):
+            far = (rc.far(g[b], r[b]) if on is None else rc.far(g[b][on[b]], r[b][on[b]])) if name == "gA" else 0.0
+            print("%s %s LA=%d n=%d %s: rel-L2 %.3e (bar %.3e)%s"
+                  % (src.tag, src.ident(key), LA, n, label, dist, bar, "  far entries %.4f%%" % (100 * far) if name == "gA" else ""))
+            src.note(key, rows=1, max_rel_l2_over_bar=dist / bar, max_far_fraction_gA=far, **({"max_rel_l2_gA": dist} if name == "gA" else {}))
             assert dist <= bar, (label, dist, bar)
             assert far <= rc.FAR_CAP, (label, far)
 
 
-def check_teacher_forced(key, LA, n):
+def check_teacher_forced(key, LA, n, src=Cases):
     """The device backward pass against the host one fed the device's own tape: the projections' arguments are the same numbers
     on both sides, so the bar is what the host pass moves when only its transforms are perturbed (three times that)."""
-    p, A, c0, gC, gx = rc.case(*key)
-    m = margins(key)
+    p, A, c0, gC, gx = src.case(key)
+    seen = src.seen(A.astype(np.float64))
     _, _, tape, gA, gS = run(p, dev(A), dev(c0), LA, n, dev(gC), dev(gx))
     kw = dict(_tape=f64(tape))
-    ref = rc.grad(key, LA, n, **kw)
-    per = rc.grad(key, LA, n, _perturb=rc.perturbation(n + 29 + 100 * LA, kinds=("gc", "gv")), **kw)
+    ref = src.grad(key, LA, n, **kw)
+    per = src.grad(key, LA, n, _perturb=src.transform_model(n + 29 + 100 * LA), **kw)
     for name, got, r, q in zip(("gA", "gS"), (f64(gA), f64(gS)), ref, per):
         assert np.isfinite(got.view(np.float64)).all()
-        for label, dist, bar in rows_of(name, got, r, q):
-            print("rtisi_grad %s LA=%d n=%d teacher-forced %s: rel-L2 %.3e (bar %.3e)" % (rc.ident(key), LA, n, label, dist, bar))
-            m[4] = max(m[4], dist / bar)
+        for label, dist, bar in rows_of(name, got, r, q, seen if name == "gA" else None):
+            print("%s %s LA=%d n=%d teacher-forced %s: rel-L2 %.3e (bar %.3e)" % (src.tag, src.ident(key), LA, n, label, dist, bar))
+            src.note(key, max_teacher_forced_rel_l2_over_bar=dist / bar)
             assert dist <= bar, (label, dist, bar)
 
 
-def check_tape(key, LA, n):
+def check_tape(key, LA, n, src=Cases):
     """The device tape against the host's X, per spectrogram, held to the bar of tests/test_gpu_rtisi.py: three times what the host's
     own projection arguments move under the error model.  The rows of no frame are as the caller left them."""
-    p, A, S, gC, gx = on_device(key)
-    m = margins(key)
+    p, A, S, gC, gx = on_device(key, src)
     tape = f64(run(p, A, S, LA, n, None, None, want_S=False)[2])
-    ref, per = rc.host_tape(key, LA, n), rc.host_tape(key, LA, n, perturbed=True)
+    ref, per = src.host_tape(key, LA, n), src.host_tape(key, LA, n, perturbed=True)
     T = S.shape[1]
     for mm in range(T):
         assert not tape[:, mm, :, min(mm + LA, T - 1) - mm + 1:].any()
     for label, dist, bar in rows_of("tape", tape, ref, per):
-        print("rtisi_grad %s LA=%d n=%d %s: rel-L2 %.3e (bar %.3e)" % (rc.ident(key), LA, n, label, dist, bar))
-        m[5] = max(m[5], dist / bar)
+        print("%s %s LA=%d n=%d %s: rel-L2 %.3e (bar %.3e)" % (src.tag, src.ident(key), LA, n, label, dist, bar))
+        src.note(key, max_tape_rel_l2_over_bar=dist / bar)
         assert dist <= bar, (label, dist, bar)
 
 
@@ -294,17 +323,17 @@ def test_invalid_arguments():
 
 def test_zz_margins_actually_achieved():
     """What the cases above reached, per shape (written to $LWS_MARGINS_DIR/rtisi_grad_margins.json when that variable names a
-    directory; profiles/rtisi_grad_margins.json is a copy).  On an MI355X, 498 whole-run rows (gA and gS per spectrogram at 10 shapes
-    and 8 pairs of look-ahead and iterations, and the placement cases): rel-L2 of gA 1.0e-7 ... 2.1e-4, every row at most 26 % of its bar,
-    no entry of gA beyond 1e-3 max|gA|; 498 teacher-forced rows at most 6.3 % of their bar; the tape at most 3.0 % of its bar; the whole
-    file in 5.6 s."""
+    directory; profiles/rtisi_grad_margins.json is a copy).  On an MI355X, 798 whole-run rows (gA and gS per spectrogram at 16 shapes
+    and 8 pairs of look-ahead and iterations, and the five placement cases): rel-L2 of gA 9.7e-8 ... 1.0e-3, every row at most 26 % of its
+    bar, at most 0.1 % of a spectrogram's gA beyond 1e-3 max|gA| (at (3000, 1500), LA = 4, state in scratch; none anywhere else); 798
+    teacher-forced rows at most 6.8 % of their bar; the tape at most 5.4 % of its bar; (512, 128) at 512 threads at most 3.8 %, (600, 150)
+    at 768 threads 6.5 %, (3000, 1500) 19 % with the state 1840 bytes under the LDS cap and beside three transform buffers in scratch; the
+    whole file in 6.7 s."""
     if not MARGINS:
         check_whole_run((64, 16, True, 12), 3, 3)
         check_teacher_forced((64, 16, True, 12), 3, 3)
         check_tape((64, 16, True, 12), 3, 3)
-    report = {"%d,%d,%s" % k: {"rows": v[0], "max_rel_l2_gA": v[1], "max_rel_l2_over_bar": v[2], "max_far_fraction_gA": v[3],
-                               "max_teacher_forced_rel_l2_over_bar": v[4], "max_tape_rel_l2_over_bar": v[5]}
-              for k, v in sorted(MARGINS.items())}
+    report = {"%d,%d,%s" % k: dict(zip(FIGURES, v)) for k, v in sorted(MARGINS.items())}
     out = os.environ.get("LWS_MARGINS_DIR", "")
     if out and os.path.isdir(out):
         with open(os.path.join(out, "rtisi_grad_margins.json"), "w") as f:

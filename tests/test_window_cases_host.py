@@ -1,7 +1,8 @@
 """CPU: the window pairs of tests/window_cases.py -- that they are what they claim to be; the host fp64 definitions of the transform
 family under them against independent restatements (those definitions are what the device is held to, and the rest of the suite only
 ever gives them the mirror-symmetric default); how far each operation moves when a window is read backwards or the two windows change
-roles, which is the reason the pairs exist; and the gate on the inputs of tests/test_gpu_windows.py and tests/test_gpu_windows_la.py.
+roles, which is the reason the pairs exist; and the gate on the inputs of tests/test_gpu_windows.py, tests/test_gpu_windows_la.py and
+tests/test_gpu_windows_grad.py.
 Every figure is printed before it is asserted (pytest -s)."""
 import functools
 import types
@@ -210,6 +211,52 @@ def test_misi_grad_matches_central_differences_of_misi(kind, key):
             assert abs(fd - an) <= 1e-5 * abs(an)
 
 
+# ---- griffin_lim_grad and rtisi_la_grad against torch fp64 autograd -----------------------------------------------------------------------
+GRAD_AUTOGRAD_SHAPES = [(64, 16, True, 12, 3), (256, 96, False, 2, 3)]
+
+
+def grad_one(key, kind):
+    """Spectrogram 0 of grad_case in fp64: A, c0, gC, gx."""
+    return tuple(np.asarray(a[0], dtype=np.complex128 if np.iscomplexobj(a) else np.float64) for a in wc.grad_case(*key[:4], kind)[2:])
+
+
+@pytest.mark.parametrize("key", GRAD_AUTOGRAD_SHAPES, ids=wc.ident)
+@pytest.mark.parametrize("kind", wc.KINDS)
+def test_gla_and_rtisi_gradients_match_torch(kind, key):
+    """The restatements of tests/test_gla_grad_host.py and tests/test_rtisi_grad_host.py -- frames gathered by an index or placed by
+    padding, torch.fft, the projection -- under the pair: there the two windows are multiples of each other and the adjoint transforms
+    of the definitions, where they change roles, have only ever been held up to that."""
+    torch = pytest.importorskip("torch")
+    from test_gla_grad_host import torch_griffin_lim
+    from test_rtisi_grad_host import torch_rtisi_la
+    A, c0, gC, gx = grad_one(key, kind)
+    p = plan(key, kind)
+    leaves = lambda: tuple(torch.from_numpy(a.copy()).requires_grad_(True) for a in (A, c0))
+    grads = lambda tA, tS: tuple(np.zeros(a.shape, a.dtype) if t.grad is None else t.grad.numpy() for a, t in ((A, tA), (c0, tS)))
+    for n, alpha in ((0, 0.99),) + wc.GLA_GRAD_STEPS:
+        tA, tS = leaves()
+        C = torch_griffin_lim(torch, p, tA, tS, n, alpha)
+        (torch.from_numpy(gC).conj() * C).real.sum().backward()
+        ref = lws_amd.griffin_lim(c0, p.fsize, p.fshift, p.awin, p.swin, n, alpha=alpha, magnitudes=A, perfectrec=p.perfectrec)
+        dC = np.abs(C.detach().numpy() - ref).max() / np.abs(A).max()
+        got = lws_amd.griffin_lim_grad(c0, p.fsize, p.fshift, p.awin, p.swin, n, A, alpha=alpha, grad_out=gC, perfectrec=p.perfectrec)
+        d = [wc.rel(g, w) for g, w in zip(got, grads(tA, tS))]
+        print("%s %s n=%d alpha=%g: griffin_lim off the torch restatement by %.2e max A; griffin_lim_grad rel-L2 to autograd gA %.2e gS %.2e"
+              % ((kind, wc.ident(key), n, alpha, dC) + tuple(d)))
+        assert dC <= 1e-12 and max(d) <= 1e-10
+    for LA, n in ((3, 0),) + wc.LA_STEPS:
+        tA, tS = leaves()
+        C, x = torch_rtisi_la(torch, p, tA, tS, n, LA)
+        ((torch.from_numpy(gC).conj() * C).real.sum() + (torch.from_numpy(gx) * x).sum()).backward()
+        ref, sig = lws_amd.rtisi_la(c0, p.fsize, p.fshift, p.awin, p.swin, n, look_ahead=LA, magnitudes=A, perfectrec=p.perfectrec, return_signal=True)
+        dC = max(np.abs(C.detach().numpy() - ref).max(), np.abs(x.detach().numpy() - sig).max()) / np.abs(A).max()
+        got = lws_amd.rtisi_la_grad(c0, p.fsize, p.fshift, p.awin, p.swin, n, A, look_ahead=LA, grad_out=gC, grad_signal=gx, perfectrec=p.perfectrec)
+        d = [wc.rel(g, w) for g, w in zip(got, grads(tA, tS))]
+        print("%s %s LA=%d n=%d: rtisi_la off the torch restatement by %.2e max A; rtisi_la_grad rel-L2 to autograd gA %.2e gS %.2e"
+              % ((kind, wc.ident(key), LA, n, dC) + tuple(d)))
+        assert dC <= 1e-12 and max(d) <= 1e-10
+
+
 # ---- the look-ahead definitions ----------------------------------------------------------------------------------------------------
 def rtisi_restated(p, S, n, LA, A):
     """rtisi_la for one spectrogram, stated otherwise: no running sum and no stored frames -- in every inner iteration every frame
@@ -397,6 +444,65 @@ def test_under_the_default_pair_mirrored_windows_move_nothing_a_device_could_see
         assert moved <= 1e-6 * bar, (name, moved, bar)
 
 
+def grad_call(op, kind, key, step):
+    """(function of keywords giving (gA, gS) of the fp64 definition, (reference, the same under the error model))."""
+    if op == "gla_grad":
+        return functools.partial(wc.gla_grad, key, kind, *step), wc.host_gla_grad(key, kind, *step)
+    return functools.partial(wc.rtisi_grad, key, kind, *step), wc.host_rtisi_grad(key, kind, *step)
+
+
+def bars_moved(got, ref, per, A):
+    """Per spectrogram, on the frames with A != 0: rel-L2 of got from ref over the bar tests/test_gpu_windows_grad.py holds gA to."""
+    seen = A.any(axis=-1)
+    return [wc.rel(got[b][seen[b]], ref[b][seen[b]]) / (3 * wc.rel(per[b][seen[b]], ref[b][seen[b]])) for b in range(A.shape[0])]
+
+
+@pytest.mark.parametrize("kind", wc.KINDS)
+@pytest.mark.parametrize("op", ("gla_grad", "rtisi_grad"))
+def test_mirrored_or_exchanged_windows_move_every_gradient_by_10_bars(op, kind):
+    """On every combination the GPU file runs and every spectrogram of it: the fp64 gA under the mirrored pair, and under the
+    exchanged one, lies at least 10 of that spectrogram's bars from the fp64 gA under the pair itself.  One frame of Griffin-Lim
+    reads only the product awin swin, in the round trip and in its adjoint, so an exchange moves nothing there: those rows are exempt
+    from it.  Measured: at least 1359 (mirrored) and 1003 (exchanged) bars for Griffin-Lim, 28 and 25 for RTISI-LA."""
+    low = {"mirrored": np.inf, "exchanged": np.inf}
+    for _, key, step in wc.runs(op, kind):
+        awin, swin, A = wc.grad_case(*key[:4], kind)[:3]
+        f, (ref, per) = grad_call(op, kind, key, step)
+        for name, windows in (("mirrored", wc.mirrored(awin, swin)), ("exchanged", wc.exchanged(awin, swin))):
+            if name == "exchanged" and op == "gla_grad" and key[3] == 1:
+                continue
+            moved = min(bars_moved(f(windows=windows)[0], ref[0], per[0], A))
+            low[name] = min(low[name], moved)
+            assert moved >= 10, (op, kind, key, step, name, moved)
+    print("%s %s: mirrored windows move gA by at least %.0f bars, exchanged roles by at least %.0f" % (op, kind, low["mirrored"], low["exchanged"]))
+
+
+@pytest.mark.parametrize("kind", wc.KINDS)
+@pytest.mark.parametrize("op", ("gla_grad", "rtisi_grad"))
+def test_a_backward_pass_that_confuses_the_windows_misses_the_device_bar(op, kind):
+    """What a kernel bug of this kind would look like: the forward pass right (the definition's own tape, teacher-forced) and only the
+    backward transforms given awin and swin in each other's place -- the forward kernels' roles carried over -- or read backwards.
+    Under the pair the gA or the gS of such a pass is outside the bar the device's is held to (dist <= 1 bar), on every combination the GPU
+    file runs and every spectrogram.  The single-frame rows are exempt from the exchange: one frame reads only the product."""
+    low = {"mirrored": np.inf, "exchanged": np.inf}
+    for _, key, step in wc.runs(op, kind):
+        awin, swin, A = wc.grad_case(*key[:4], kind)[:3]
+        f, (ref, per) = grad_call(op, kind, key, step)
+        tape = wc.host_gla_tape(key, kind, *step) if op == "gla_grad" else wc.host_rtisi_tape(key, kind, *step)
+        assert all(np.array_equal(a, b) for a, b in zip(f(_tape=tape), ref))          # the teacher-forced definition is the definition
+        for name, windows in (("mirrored", wc.mirrored(awin, swin)), ("exchanged", (swin, awin))):
+            if name == "exchanged" and key[3] == 1:
+                continue
+            got = f(windows=windows, _tape=tape)
+            # one step of Griffin-Lim feeds gA from no transform: there the windows are in gS alone, held on every frame
+            out = zip(bars_moved(got[0], ref[0], per[0], A), bars_moved(got[1], ref[1], per[1], np.ones_like(A)))
+            moved = min(max(a, s) for a, s in out)
+            low[name] = min(low[name], moved)
+            assert moved > 1, (op, kind, key, step, name, moved)
+    print("%s %s: a backward pass with mirrored windows is at least %.0f bars out, one with the windows exchanged at least %.0f"
+          % (op, kind, low["mirrored"], low["exchanged"]))
+
+
 def test_overlap_entries_are_within_what_float32_can_compute_except_where_recorded():
     """start='overlap' estimates a frame from the inverse transforms of the frames before it.  The float32 transform model makes at most
     OVERLAP_SIGMA max|X| of that on every input but 'padded' under perfectrec, where the second frame reads the far tail of a zero-phase
@@ -417,12 +523,13 @@ def test_overlap_entries_are_within_what_float32_can_compute_except_where_record
 
 
 # ---- the gate on the inputs of the GPU files ------------------------------------------------------------------------------------------
-OPS = ("griffin_lim", "misi", "misi_grad", "rtisi_la", "misi_la")
+OPS = ("griffin_lim", "misi", "misi_grad", "rtisi_la", "misi_la", "gla_grad", "rtisi_grad")
+GRAD_OPS = ("misi_grad", "gla_grad", "rtisi_grad")       # gated on the share of the entries of gA, up to FAR_CAP
 
 
 @pytest.mark.parametrize("op", OPS)
 def test_gate_lets_through_what_the_model_keeps_and_nothing_else(op):
-    cap = wc.FAR_CAP if op == "misi_grad" else 0.0
+    cap = wc.FAR_CAP if op in GRAD_OPS else 0.0
     combos = wc.combinations(op)
     dropped = wc.DROPPED[op]
     assert set(dropped) <= set(combos)
@@ -441,6 +548,10 @@ def test_gate_lets_through_what_the_model_keeps_and_nothing_else(op):
         print("rtisi_la: %d more, start='overlap' beyond float32 (wc.NOT_AN_OVERLAP_CASE), run on the device for their properties and "
               "teacher-forced, not compared with the fp64 run: %d of %d without that comparison" % (beyond, beyond + len(dropped), beyond + len(combos)))
         assert beyond == 12 and len(combos) == 141
+    if op in ("gla_grad", "rtisi_grad"):
+        assert (len(combos), len(dropped)) == ((63, 0) if op == "gla_grad" else (90, 4))
+    if op == "rtisi_grad":                               # the gate keeps every scratch row
+        assert all((kind, s, (LA, n)) in wc.runs(op) for kind in wc.KINDS for s, LA, n in wc.SCRATCH_RTISI_GRAD)
     assert 10 * len(dropped) <= len(combos)
     for kind in wc.KINDS:
         assert {c[1] for c in wc.runs(op, kind)} == {c[1] for c in combos if c[0] == kind} or op in ("rtisi_la", "misi_la")

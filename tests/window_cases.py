@@ -1,6 +1,7 @@
 """Window pairs that are not mirror-symmetric, not each other's multiple, not always dual and not free of zeros, with the inputs,
 error model, host fp64 references and input gate of the tests that give them to the transform family: tests/
-test_window_cases_host.py (CPU), tests/test_gpu_windows.py and tests/test_gpu_windows_la.py (GPU).  Nothing here needs torch or a device.
+test_window_cases_host.py (CPU), tests/test_gpu_windows.py, tests/test_gpu_windows_la.py and tests/test_gpu_windows_grad.py (GPU).  Nothing
+here needs torch or a device.
 
 Every window the rest of the suite uses satisfies w[n] == w[N-1-n], and every synthesis window there is the normalised dual of its
 analysis window; a kernel that read a window backwards, or took one window for the other, would pass all of it.  pair() gives three
@@ -16,6 +17,7 @@ The inputs follow tests/misi_grad_cases.py: three mixtures at scales 1, 1e-3 and
 true phase plus 0.5 rad of Gaussian noise rounded to complex64, magnitudes and mixture rounded to float32, the magnitudes always
 passed explicitly.  Griffin-Lim and RTISI-LA run on source 0.  The error model is the suite's: every projection argument perturbed
 by seeded Gaussian noise of 1e-6 max|X| per component; three times what the fp64 definition moves under it is the device's bar.
+The backward passes of Griffin-Lim and RTISI-LA have inputs of their own, grad_case(): see there.
 
 Which inputs the GPU files run is decided here, on the host: DROPPED lists the combinations on which the fp64 model itself moves a bin
 far (at most one in ten per operation), NOT_AN_OVERLAP_CASE the inputs whose overlap entries float32 cannot compute, by the float32
@@ -27,6 +29,7 @@ import numpy as np
 import lws_amd
 from lws_amd.lws import _perfectrec_prepad
 import fft_model as fm
+import gla_grad_cases
 
 KINDS = ("tilt", "nondual", "padded")
 SCALES = np.array([1.0, 1e-3, 300.0])          # of the B = 3 mixtures
@@ -55,6 +58,12 @@ LA_STEPS = ((0, 2), (1, 3), (3, 3), (5, 2))    # (look_ahead, iterations) from a
 # 5 of the 21 inputs each, at two iterations on 0, 2 and 1.  Every shape is also held teacher-forced, at no iterations, where nothing can
 # drift (tests/start_cases.entry_check).
 START_STEPS = ((0, 2), (1, 2), (3, 2))
+# The backward passes of Griffin-Lim and RTISI-LA (k_gla_bwd_*, k_rtisi_tape, k_rtisi_bwd), on the inputs of grad_case().  RTISI-LA runs at
+# LA_STEPS with both cotangents.
+GLA_GRAD_STEPS = ((1, 0.0), (3, 0.99), (5, 0.99))   # (iterations, alpha)
+GRAD_SEED = 5200000
+# the backward state of k_rtisi_bwd in device scratch, with two transform buffers and with three: (shape, look_ahead, iterations)
+SCRATCH_RTISI_GRAD = (((4096, 1024, False, 6, 1), 5, 2), ((3000, 1500, False, 6, 1), 4, 2))
 # the look-ahead kernels with their state in device scratch: (shape, look_ahead, iterations)
 SCRATCH_RTISI = ((2048, 512, False, 9, 1), 7, 2)
 SCRATCH_MISI = ((1000, 250, True, 5, 4), 3, 2)
@@ -87,6 +96,16 @@ DROPPED = {
         ('tilt', (1000, 250, True, 5, 4), (3, 2, 'mixture')): 0.00080,
         ('padded', (64, 16, True, 12, 3), (5, 2, 'given')): 0.00253,
         ('padded', (1000, 250, True, 5, 4), (3, 2, 'mixture')): 0.00040,
+    },
+    # The two below on the inputs of grad_case(), GRAD_SEED: entries of gA beyond FAR max|gA| on the frames with A != 0, cap FAR_CAP.  Of
+    # the seeds 5000000, 5100000 .. 5900000 in that draw order (dropped of 63 and of 90: 7 5, 5 10, 0 4, 2 6, 0 5, 4 5, 2 9, 2 9, 4 7, 2 10)
+    # 5000000, 5100000 and 5900000 drop more than one combination in ten of an operation, and this one drops the fewest.
+    "gla_grad": {},                                                              # 0 of 63; no entry far on any of them
+    "rtisi_grad": {                                                              # 4 of 90; the others at 0.337 % at most
+        ('tilt', (64, 16, True, 12, 3), (0, 2)): 0.03535,
+        ('tilt', (256, 96, False, 2, 3), (5, 2)): 0.08915,
+        ('tilt', (100, 30, True, 6, 2), (3, 3)): 0.00980,
+        ('padded', (64, 16, True, 12, 3), (1, 3)): 0.00551,
     },
 }
 # Inputs on which start='overlap' is not compared with the fp64 run: float32 cannot compute their entry estimates to the 1e-6 max|X| that the error model and
@@ -195,6 +214,29 @@ def case(fsize, fshift, perfectrec, T, K, kind, B=3):
     return awin, swin, A, c0, y, gC, gs
 
 
+@functools.lru_cache(maxsize=None)
+def grad_case(fsize, fshift, perfectrec, T, kind, B=3):
+    """The inputs of the backward passes of Griffin-Lim and RTISI-LA under a pair: awin, swin, A = |stft(white noise)| (B, T, F) at SCALES
+    rounded to float32, the start c_0 the true phase plus gla_grad_cases.START_NOISE (0.1 rad) rounded to complex64, and the cotangents gC
+    (complex64) and gx (float32, standard normal times max|gC_b|, the scale tests/rtisi_grad_cases.case gives it), drawn in this order
+    from one generator under GRAD_SEED.  Not
+    case() above: from its 0.5 rad an iteration that no mixture anchors moves most of gA under the error model alone (the docstring of
+    tests/gla_grad_cases.case), and a draw added to case() would move every input the other GPU files are gated on."""
+    rng = np.random.default_rng(GRAD_SEED + 1000 * fsize + 10 * fshift + perfectrec)
+    awin, swin = pair(fsize, fshift, kind)
+    n = length(fsize, fshift, perfectrec, T)
+    src = rng.standard_normal((B, n)) * SCALES[:B, None]
+    X = np.stack([lws_amd.stft(x, fsize, fshift, awin, perfectrec=perfectrec) for x in src])
+    assert X.shape == (B, T, fsize // 2 + 1)
+    A = np.abs(X).astype(np.float32)
+    c0 = (A * np.exp(1j * (np.angle(X) + gla_grad_cases.START_NOISE * rng.standard_normal(X.shape)))).astype(np.complex64)
+    gC = ((rng.standard_normal(X.shape) + 1j * rng.standard_normal(X.shape)) / np.sqrt(fsize)).astype(np.complex64)
+    gx = (rng.standard_normal((B, n)) * np.abs(gC).max(axis=(1, 2))[:, None]).astype(np.float32)
+    for a in (A, c0, gC, gx):
+        a.setflags(write=False)
+    return awin, swin, A, c0, gC, gx
+
+
 def open_mixture(key, y):
     """The mixture an open end reads: y and, with perfectrec, the fsize - fshift zeros stft pads behind the signal."""
     if not key[2]:
@@ -231,10 +273,12 @@ def perturbation(seed, per_source=False):
 
 
 def grad_perturbation(seed, kinds=("X", "gc", "gv")):
-    """The error model of tests/misi_grad_cases.py."""
+    """The error model of tests/misi_grad_cases.py, and with the hooks' other signatures -- (kind, i, b, Z) and (kind, m, it, b, Z) -- of
+    tests/gla_grad_cases.py and tests/rtisi_grad_cases.py: the array is the last argument of all three."""
     rng = np.random.default_rng(seed)
 
-    def f(kind, i, b, k, Z):
+    def f(kind, *where):
+        Z = where[-1]
         if kind not in kinds:
             return Z
         sigma = 1e-6 * np.abs(Z).max() * _seen(Z)
@@ -277,6 +321,79 @@ def host_grad(key, kind, n):
     run = functools.partial(lws_amd.misi_grad, c0, y, key[0], key[1], awin, swin, n, A.astype(np.float64), grad_out=gC, grad_signals=gs,
                             perfectrec=key[2])
     return _frozen(run()), _frozen(run(_perturb=grad_perturbation(n + 17)))
+
+
+def gla_grad(key, kind, n, alpha, **kw):
+    """lws_amd.griffin_lim_grad on grad_case() of `key` under `kind`; windows=(awin, swin) puts another pair in their place."""
+    awin, swin, A, c0, gC, gx = grad_case(*key[:4], kind)
+    awin, swin = kw.pop("windows", (awin, swin))
+    return lws_amd.griffin_lim_grad(c0, key[0], key[1], awin, swin, n, A.astype(np.float64), alpha=alpha, grad_out=gC, perfectrec=key[2], **kw)
+
+
+def rtisi_grad(key, kind, LA, n, **kw):
+    """lws_amd.rtisi_la_grad on grad_case() of `key` under `kind`, both cotangents; windows=(awin, swin) as above."""
+    awin, swin, A, c0, gC, gx = grad_case(*key[:4], kind)
+    awin, swin = kw.pop("windows", (awin, swin))
+    return lws_amd.rtisi_la_grad(c0, key[0], key[1], awin, swin, n, A.astype(np.float64), look_ahead=LA, grad_out=gC, grad_signal=gx,
+                                 perfectrec=key[2], **kw)
+
+
+@functools.lru_cache(maxsize=None)
+def host_gla_grad(key, kind, n, alpha):
+    """((gA, gS), (gA, gS)) of griffin_lim_grad."""
+    return _frozen(gla_grad(key, kind, n, alpha)), _frozen(gla_grad(key, kind, n, alpha, _perturb=grad_perturbation(n + 17)))
+
+
+@functools.lru_cache(maxsize=None)
+def host_rtisi_grad(key, kind, LA, n):
+    """((gA, gS), (gA, gS)) of rtisi_la_grad."""
+    return _frozen(rtisi_grad(key, kind, LA, n)), _frozen(rtisi_grad(key, kind, LA, n, _perturb=grad_perturbation(n + 17 + 100 * LA)))
+
+
+@functools.lru_cache(maxsize=None)
+def host_gla_tape(key, kind, n, alpha, perturbed=False):
+    """The projection arguments of the host's griffin_lim on grad_case(), (n, B, T, F); perturbed: of the run under the error model on
+    them, as that run used them."""
+    awin, swin, A, c0, gC, gx = grad_case(*key[:4], kind)
+    tape = np.zeros((n,) + c0.shape, dtype=np.complex128)
+    model = grad_perturbation(n + 17, kinds=("X",)) if perturbed else None
+
+    def rec(i, b, X):
+        if model is not None:
+            X = model("X", i, b, X)
+        tape[i - 1, b] = X
+        return X
+    lws_amd.griffin_lim(c0, key[0], key[1], awin, swin, n, alpha=alpha, magnitudes=A.astype(np.float64), perfectrec=key[2], _perturb=rec)
+    tape.setflags(write=False)
+    return tape
+
+
+@functools.lru_cache(maxsize=None)
+def host_rtisi_tape(key, kind, LA, n, perturbed=False):
+    """The same of rtisi_la, (B, T, n, W, F) as tests/rtisi_grad_cases.host_tape lays it out."""
+    awin, swin, A, c0, gC, gx = grad_case(*key[:4], kind)
+    B, T, F = c0.shape
+    tape = np.zeros((B, T, n, min(LA, T - 1) + 1, F), dtype=np.complex128)
+    model = grad_perturbation(n + 17 + 100 * LA, kinds=("X",)) if perturbed else None
+
+    def rec(m, it, b, X):
+        if model is not None:
+            X = model("X", m, it, b, X)
+        tape[b, m, it - 1, :X.shape[0]] = X
+        return X
+    lws_amd.rtisi_la(c0, key[0], key[1], awin, swin, n, look_ahead=LA, magnitudes=A.astype(np.float64), perfectrec=key[2], _perturb=rec)
+    tape.setflags(write=False)
+    return tape
+
+
+def seen_far(per, ref, A):
+    """The largest share, over the spectrograms of a stack, of the entries of gA the model moves further than FAR max|gA|, on the frames
+    with A != 0 (_seen())."""
+    worst = 0.0
+    for p, r, a in zip(per, ref, A):
+        seen = a.any(axis=-1)
+        worst = max(worst, float(np.mean(np.abs(p[seen] - r[seen]) > FAR * np.abs(r[seen]).max())))
+    return worst
 
 
 def rtisi_input(key, kind, start):
@@ -393,6 +510,12 @@ def combinations(op):
                 out += [(kind, s, n) for n in MISI_STEPS]
             elif op == "misi_grad":
                 out += [(kind, s, n) for n in GRAD_STEPS]
+            elif op == "gla_grad":
+                out += [(kind, s, step) for step in GLA_GRAD_STEPS]
+            elif op == "rtisi_grad":
+                out += [(kind, s, step) for step in LA_STEPS]
+        if op == "rtisi_grad":
+            out += [(kind, s, (LA, n)) for s, LA, n in SCRATCH_RTISI_GRAD if has_pair(s[0], s[1], kind)]
         if op in ("rtisi_la", "misi_la"):
             out += [(kind, s, (LA, n, start)) for start in ("given", "overlap" if op == "rtisi_la" else "mixture")
                     for s, LA, n in la_runs(op, start) if has_pair(s[0], s[1], kind) and (start != "overlap" or has_overlap_case(kind, s))]
@@ -407,6 +530,12 @@ def runs(op, kind=None):
 def model_share(op, combo):
     """The gate's figure of one combination: the far-bin share of the fp64 error model (for misi_grad: of the entries of gA)."""
     kind, key, step = combo
+    if op == "gla_grad":
+        ref, per = host_gla_grad(key, kind, *step)
+        return seen_far(per[0], ref[0], grad_case(*key[:4], kind)[2])
+    if op == "rtisi_grad":
+        ref, per = host_rtisi_grad(key, kind, *step)
+        return seen_far(per[0], ref[0], grad_case(*key[:4], kind)[2])
     A = case(*key, kind)[2]
     if op == "griffin_lim":
         (ref, _), (per, _) = host_gla(key, kind, *step)
