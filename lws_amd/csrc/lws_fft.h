@@ -25,7 +25,23 @@ constexpr int MAXN = 4096, MINN = 32, FFT_THREADS = 256;   // two N-point comple
 // takes an instance of its own, so that what the compiler derives from the other callers' arguments (all alike) stays derived; with
 // one shared instance a scalar shift moves by two slots in each of them.  Nothing computed depends on that: it only keeps their
 // instruction streams what they were.  tools/compare_kernel_isa.py checks it, kernel by kernel, against another build's assembly.
-template <int USER = 0> __device__ float2 *fft_lds(float2 *x, float2 *y, int n, int m, int a, float sign) {
+// The instances and their owners (plain ints, not an enum: the value is all a mangled name may see of them).  A kernel added to
+// lws_gla.hip that passes other arguments than a present owner does takes the next number.
+constexpr int FFT_USER_SHARED = 0;                  // lws_stft.hip; k_gla_inverse, k_gla_forward without a tape, k_misi_forward
+constexpr int FFT_USER_RTISI = 1;                   // k_rtisi under LWS_START_GIVEN
+constexpr int FFT_USER_MISI_LA = 2;                 // k_misi_la, the passes
+constexpr int FFT_USER_RTISI_STREAM = 3;            // k_rtisi_stream under LWS_START_GIVEN
+constexpr int FFT_USER_MISI_LA_STREAM = 4;          // k_misi_la_stream, the passes
+constexpr int FFT_USER_RTISI_OVERLAP = 5;           // k_rtisi under LWS_START_OVERLAP
+constexpr int FFT_USER_RTISI_STREAM_OVERLAP = 6;    // k_rtisi_stream under LWS_START_OVERLAP
+constexpr int FFT_USER_MISI_LA_ENTRY = 7;           // k_misi_la, the entry block of LWS_START_MIXTURE
+constexpr int FFT_USER_MISI_LA_STREAM_ENTRY = 8;    // k_misi_la_stream, the same block
+constexpr int FFT_USER_MISI_BWD = 9;                // k_misi_bwd_project, k_misi_bwd_frames
+constexpr int FFT_USER_GLA_TAPE = 10;               // k_gla_forward with a tape
+constexpr int FFT_USER_GLA_BWD = 11;                // k_gla_bwd_project, k_gla_bwd_frames
+constexpr int FFT_USER_RTISI_TAPE = 12;             // k_rtisi_tape
+constexpr int FFT_USER_RTISI_BWD = 13;              // k_rtisi_bwd
+template <int USER = FFT_USER_SHARED> __device__ float2 *fft_lds(float2 *x, float2 *y, int n, int m, int a, float sign) {
     const int tid = threadIdx.x, nthr = blockDim.x;
     const int n2 = n / m;                                // 2^a
     float2 *tw = y + n;

@@ -17,7 +17,7 @@ struct Factors { int odd, log2e; };
 Factors factor(int n) { Factors f{n, 0}; while (!(f.odd & 1)) { f.odd >>= 1; ++f.log2e; } return f; }
 int prepad(int N, int hop) { const int r = N % hop; return r == 0 ? N - hop : N - r; }   // lws.pyx:55-60
 
-// The arguments of k_rtisi_stream and k_misi_la_stream (their comments in lws_gla.hip say what the kernels do with them).
+// The arguments of k_rtisi_stream and k_misi_la_stream (their comments in lws_la_stream_kernels.h say what the kernels do with them).
 struct RtisiStreamArgs {
     int N, odd, log2e, hop, LA, iters;
     int nsteps, Mrel;            // steps of this launch; frames from its first step to the end of the stream (nsteps + LA while open)

@@ -1,10 +1,10 @@
-// lws_rtisi_march.h -- the text of k_rtisi (lws_gla.hip, where its comment is), included there once per value of the compile-time flag
+// lws_rtisi_march.h -- the text of k_rtisi (lws_rtisi_kernels.h, where its comment is), included there once per value of the compile-time flag
 // RTISI_TAPE: 0 gives k_rtisi, the kernel and arguments it always was; 1 gives k_rtisi_tape, which also stores the argument X of every
 // projection to tape[b][m][it-1][j-m][k], of extent (B, M, iters, LA + 1, F), for the backward pass (rows beyond `last` are never
 // written; used under LWS_START_GIVEN only).  A flag of the preprocessor and not of the template: any template parameter or argument
 // more renames the untaped kernels, and a shared device function inlined into both changes their register allocation -- they are to
-// keep the instruction streams they had (tools/compare_kernel_isa.py).  No include guard: RTISI_KERNEL, RTISI_TAPE and
-// RTISI_TAPE_ARG are set by the includer.
+// keep the instruction streams they had (tools/compare_kernel_isa.py); for the same reason each has a transform instance of its own
+// (the FFT_USER_* of lws_fft.h).  No include guard: RTISI_KERNEL, RTISI_TAPE and RTISI_TAPE_ARG are set by the includer.
 template <bool IN_LDS, int START>
 __global__ void __launch_bounds__(RTISI_MAX_THREADS) RTISI_KERNEL(float2 *C, const float *A, float *xout, const float *awin, const float *swin,
                                                         float *scratch, RtisiArgs a RTISI_TAPE_ARG) {
@@ -79,7 +79,8 @@ __global__ void __launch_bounds__(RTISI_MAX_THREADS) RTISI_KERNEL(float2 *C, con
                     // values the compiler cannot see through: hoisted over all five loops they cost more SGPRs than a wave has
                     int n_ = N, odd_ = a.odd, log2e_ = a.log2e;
                     asm volatile("" : "+s"(n_), "+s"(odd_), "+s"(log2e_));
-                    r = fft_lds<RTISI_TAPE ? 12 : START == LWS_START_GIVEN ? 1 : 5>(x, y, n_, odd_, log2e_, ph == 0 ? -1.0f : 1.0f);
+                    r = fft_lds<RTISI_TAPE ? FFT_USER_RTISI_TAPE : START == LWS_START_GIVEN ? FFT_USER_RTISI : FFT_USER_RTISI_OVERLAP>(
+                        x, y, n_, odd_, log2e_, ph == 0 ? -1.0f : 1.0f);
                 }
                 // times the synthesis window, into the slots of frames j and j + 1
                 const float inv = 1.0f / (float)N;

@@ -191,6 +191,12 @@ def _gla_args(iterations, alpha):
     return int(iterations), float(alpha)
 
 
+def _project(X, A):
+    """A X / |X|, and A + 0j where |X| == 0: the magnitude projection of every iteration below."""
+    mag = np.abs(X)
+    return np.where(mag > 0, A * X / np.where(mag > 0, mag, 1.0), A + 0j)
+
+
 def griffin_lim(S, fsize, fshift, awin, swin, iterations, alpha=0.99, magnitudes=None, perfectrec=False, return_trace=False,
                 _perturb=None):
     """(Fast) Griffin-Lim iterations from the start S, (T, F) or a stack (B, T, F), in fp64 on the host: the definition the
@@ -220,8 +226,7 @@ def griffin_lim(S, fsize, fshift, awin, swin, iterations, alpha=0.99, magnitudes
             if _perturb is not None:
                 X = _perturb(i, b, X)
             db[i - 1, b] = 10 * np.log10(np.sum(np.abs(c) ** 2) / np.sum(np.abs(X - c) ** 2))
-            mag = np.abs(X)
-            t = np.where(mag > 0, A3[b] * X / np.where(mag > 0, mag, 1.0), A3[b] + 0j)
+            t = _project(X, A3[b])
             c = t if i == 1 else t + alpha * (t - t_prev)
             t_prev = t
         out[b] = t_prev
@@ -322,8 +327,7 @@ def misi(S, mixture, fsize, fshift, awin, swin, iterations, magnitudes=None, per
                     raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, X.shape[0]))
                 if _perturb is not None:
                     X = _perturb(i, b, k, X)
-                mag = np.abs(X)
-                c[k] = np.where(mag > 0, A4[b, k] * X / np.where(mag > 0, mag, 1.0), A4[b, k] + 0j)
+                c[k] = _project(X, A4[b, k])
         if return_signals:
             sig[b] = _misi_share(np.stack([istft(c[k], fshift, swin, perfectrec=perfectrec) for k in range(K)]), y2[b])[0]
     if n == 0:
@@ -414,6 +418,156 @@ def _misi_stft_adjoint(gX, fsize, fshift, awin, perfectrec):
     return fsize * istft(G, fshift, np.asarray(awin, dtype=np.float64), perfectrec=perfectrec)
 
 
+# ---- what the three trainings (MISI, Griffin-Lim, RTISI-LA) do alike, stated once: the projection's derivative, the front and back of
+# the *_grad definitions, the argument checks of the *_layer operations and the autograd scaffold they are built from
+def _project_backward(X, A, g):
+    """Step 3 of every backward pass below: (Re q, gX) with u = X / |X|, q = conj(u) g and gX = j u (A / |X|) Im q, g being the
+    gradient on _project(X, A); where |X| == 0 the forward gives A + 0j, so u = 1 and gX = 0."""
+    mag = np.abs(X)
+    safe = np.where(mag > 0, mag, 1.0)
+    u = np.where(mag > 0, X / safe, 1.0 + 0j)
+    q = np.conj(u) * g
+    return q.real, np.where(mag > 0, 1j * u * (A / safe) * q.imag, 0j)
+
+
+def _grad_call(fn, sources, S, magnitudes, grad_out, grad_sig, _tape, plan):
+    """misi_grad (sources: S holds K spectrograms per mixture), griffin_lim_grad and rtisi_la_grad around what is their own: S and
+    the required magnitudes as stacks (a single one becomes a stack of one, and the results come back single), the cotangents
+    converted and held to their shapes, the tape from _tape or from a recording forward run.  plan(S_stack, A_stack, single) ->
+    (tape, forward, backward, length, sig_name): the empty tape, forward() that fills it, backward(gC, gs) -> the gradients as
+    stacks, and the length and argument name of the signal cotangent grad_sig (None for a function that takes none)."""
+    S = np.asarray(S)
+    rank = 3 if sources else 2
+    if S.ndim not in (rank, rank + 1):
+        raise ValueError('expected (K, T, F) spectrograms of the sources or a (B, K, T, F) stack' if sources else
+                         'expected a (T, F) spectrogram or a (B, T, F) stack')
+    noun = 'spectrograms' if sources else 'a spectrogram'
+    if magnitudes is None:
+        raise ValueError('%s differentiates with respect to the magnitudes: give them' % fn)
+    A = np.asarray(magnitudes, dtype=np.float64)
+    if A.shape != S.shape:
+        raise ValueError('magnitudes of shape %s for %s of shape %s' % (A.shape, noun, S.shape))
+    single = S.ndim == rank
+    tape, forward, backward, length, sig_name = plan(*((S[None], A[None]) if single else (S, A)), single)
+    if _tape is None:
+        forward()
+    else:
+        tape[...] = np.asarray(_tape).reshape(tape.shape)
+    gC = gs = None
+    if grad_out is not None:
+        gC = np.asarray(grad_out, dtype=np.complex128)
+        if gC.shape != S.shape:
+            raise ValueError('grad_out of shape %s for %s of shape %s' % (gC.shape, noun, S.shape))
+        gC = gC[None] if single else gC
+    if grad_sig is not None:
+        gs = np.asarray(grad_sig, dtype=np.float64)
+        if gs.shape != S.shape[:-2] + (length,):
+            raise ValueError('%s of shape %s: expected %s' % (sig_name, gs.shape, S.shape[:-2] + (length,)))
+        gs = gs[None] if single else gs
+    grads = backward(gC, gs)
+    return tuple(g[0] for g in grads) if single else grads
+
+
+def _layer_args(A, S, fsize, fshift, awin, swin, n, perfectrec, mixture=None, round_trip_always=True, squeeze_swin=False):
+    """The checks of misi_layer (mixture given: K sources per mixture), griffin_lim_layer and rtisi_la_layer (which holds the round
+    trip to the frame count under perfectrec only, and squeezes swin): float32 / complex64 device tensors on one device, S a
+    single input or a stack, A shaped as S, fsize // 2 + 1 bins, a mixture of istft's length, a frame count the round trip keeps.
+    Returns the windows as fp64 arrays."""
+    import torch
+    sources = mixture is not None
+    for name, t, dtype in (('A', A, torch.float32), ('S', S, torch.complex64)) + ((('mixture', mixture, torch.float32),) if sources else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+            raise ValueError('%s must be a %s torch tensor on the device' % (name, str(dtype).replace('torch.', '')))
+    rank = 3 if sources else 2
+    if S.dim() not in (rank, rank + 1):
+        raise ValueError('expected (K, T, F) spectrograms of the sources or a (B, K, T, F) stack' if sources else
+                         'expected a (T, F) spectrogram or a (B, T, F) stack')
+    if A.shape != S.shape:
+        raise ValueError('magnitudes of shape %s for %s of shape %s' %
+                         (tuple(A.shape), 'spectrograms' if sources else 'a spectrogram', tuple(S.shape)))
+    if A.device != S.device or (sources and mixture.device != S.device):
+        raise ValueError('A, S and mixture must be on one device' if sources else 'A and S must be on one device')
+    T, F = S.shape[-2:]
+    if sources and S.shape[-3] < 1:
+        raise ValueError('no sources')
+    if F != fsize // 2 + 1:
+        raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
+    length = _capi.istft_length(T, fsize, fshift, perfectrec)
+    if sources and tuple(mixture.shape) != tuple(S.shape[:-3]) + (length,):
+        raise ValueError('mixture of shape %s for %s spectrograms of %d frames: expected %s' %
+                         (tuple(mixture.shape), tuple(S.shape[:-2]), T, tuple(S.shape[:-3]) + (length,)))
+    if n > 0 and (perfectrec or round_trip_always):
+        back = _capi.stft_frames(length, fsize, fshift, perfectrec)
+        if back != T:
+            raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
+    awin, swin = np.array(awin, dtype=np.float64), np.array(swin, dtype=np.float64)
+    return awin, (np.squeeze(swin) if squeeze_swin else swin)
+
+
+class _Layer(object):
+    """What a differentiable layer gives the scaffold below: the rank of a single S, whether it returns signals beside C, the
+    shape of its tape, tape_shape(n, dims, extra), and its two _capi calls, forward(p, dims, mid, extra, kw) and backward(...)
+    alike, with p the device pointers by name (None where there is no tensor), dims = (B, [K,] T, F) of the stack, mid = (fsize,
+    fshift, awin, swin, perfectrec, n) as every call takes them in a row, extra the layer's own numbers (alpha, or the look-ahead),
+    kw the device and the stream."""
+
+    def __init__(self, rank, signals, tape_shape, forward, backward):
+        self.rank, self.signals, self.tape_shape, self.forward, self.backward = rank, signals, tape_shape, forward, backward
+
+
+_layer_function = None
+
+
+def _layer_apply(layer, A, S, y, fsize, fshift, awin, swin, n, perfectrec, *extra):
+    """The one torch.autograd.Function behind misi_layer, griffin_lim_layer and rtisi_la_layer, made on first use (importing this
+    module needs no torch), applied to checked arguments: y the mixture or None; returns C, or (C, signals)."""
+    global _layer_function
+    if _layer_function is None:
+        import types
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        def pointers(**tensors):
+            return types.SimpleNamespace(**{k: None if t is None else t.data_ptr() for k, t in tensors.items()})
+
+        class Layer(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, layer, A, S, y, fsize, fshift, awin, swin, n, perfectrec, *extra):
+                dev = S.device
+                dims = ((1,) if S.dim() == layer.rank else ()) + tuple(S.shape)
+                length = max(_capi.istft_length(dims[-2], fsize, fshift, perfectrec), 0)
+                A, y = A.detach().contiguous(), None if y is None else y.detach().contiguous()
+                C = S.detach().clone(memory_format=torch.contiguous_format)      # the iteration is in place: never on the caller's storage
+                sig = torch.empty(tuple(S.shape[:-2]) + (length,), dtype=torch.float32, device=dev) if layer.signals else None
+                tape = torch.empty(layer.tape_shape(n, dims, extra), dtype=torch.complex64, device=dev)
+                mid, kw = (fsize, fshift, awin, swin, perfectrec, n), dict(device=dev.index, stream=torch.cuda.current_stream(dev).cuda_stream)
+                layer.forward(pointers(C=C, A=A, y=y, sig=sig if length else None, tape=tape if n else None), dims, mid, extra, kw)
+                ctx.save_for_backward(A, tape)
+                ctx.set_materialize_grads(False)
+                ctx.call = (layer, dims, mid, extra, None if y is None else tuple(y.shape))
+                return (C, sig) if layer.signals else C
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, gC, gs=None):
+                A, tape = ctx.saved_tensors
+                layer, dims, mid, extra, y_shape = ctx.call
+                dev = A.device
+                if gC is not None:
+                    gC = gC.to(torch.complex64).contiguous()
+                if gs is not None:
+                    gs = gs.to(torch.float32).contiguous() if gs.numel() else None
+                gA = torch.empty_like(A)
+                gS = torch.empty(A.shape, dtype=torch.complex64, device=dev) if ctx.needs_input_grad[2] else None
+                gy = torch.empty(y_shape, dtype=torch.float32, device=dev) if y_shape is not None and ctx.needs_input_grad[3] else None
+                kw = dict(device=dev.index, stream=torch.cuda.current_stream(dev).cuda_stream)
+                layer.backward(pointers(gC=gC, gs=gs, A=A, tape=tape if mid[-1] else None, gA=gA, gS=gS, gy=gy), dims, mid, extra, kw)
+                return (None, gA if ctx.needs_input_grad[1] else None, gS, gy) + (None,) * (6 + len(extra))
+
+        _layer_function = Layer
+    return _layer_function.apply(layer, A, S, y, int(fsize), int(fshift), awin, swin, n, bool(perfectrec), *extra)
+
+
 def _misi_backward(tape, A, grad_out, grad_signals, fsize, fshift, awin, swin, perfectrec=False, _perturb=None):
     """The backward pass of misi() from a tape of its projections' arguments: tape (n, B, K, T, F) the X_k of the steps 1..n, A
     (B, K, T, F), and the cotangents grad_out (B, K, T, F) complex of the returned spectrograms and grad_signals (B, K, len) of
@@ -447,12 +601,8 @@ def _misi_backward(tape, A, grad_out, grad_signals, fsize, fshift, awin, swin, p
         for i in range(n, 0, -1):
             gv = np.empty((K, length))
             for k in range(K):
-                X = tape[i - 1, b, k]
-                mag = np.abs(X)
-                u = np.where(mag > 0, X / np.where(mag > 0, mag, 1.0), 1.0 + 0j)      # step 3
-                q = np.conj(u) * gc[k]
-                gA[b, k] += q.real
-                gX = np.where(mag > 0, 1j * u * (A[b, k] / np.where(mag > 0, mag, 1.0)) * q.imag, 0j)
+                ga, gX = _project_backward(tape[i - 1, b, k], A[b, k], gc[k])          # step 3
+                gA[b, k] += ga
                 v = _misi_stft_adjoint(gX, fsize, fshift, awin, perfectrec)            # step 4
                 gv[k] = v if _perturb is None else np.real(_perturb('gv', i, b, k, v))
             gc = frames_back(share_back(gv, b), i - 1, b)
@@ -479,97 +629,33 @@ def misi_grad(S, mixture, fsize, fshift, awin, swin, iterations, magnitudes, gra
     _tape: (n, K, T, F) / (n, B, K, T, F), the X of every step from elsewhere -- a device run's -- instead of this function's own
     forward pass: the backward pass alone, teacher-forced.)"""
     n, _ = _gla_args(iterations, 0.0)
-    S = np.asarray(S)
-    if S.ndim not in (3, 4):
-        raise ValueError('expected (K, T, F) spectrograms of the sources or a (B, K, T, F) stack')
-    if magnitudes is None:
-        raise ValueError('misi_grad differentiates with respect to the magnitudes: give them')
-    A = np.asarray(magnitudes, dtype=np.float64)
-    if A.shape != S.shape:
-        raise ValueError('magnitudes of shape %s for spectrograms of shape %s' % (A.shape, S.shape))
-    single = S.ndim == 3
-    S4, A4 = (S[None], A[None]) if single else (S, A)
-    y = np.asarray(mixture, dtype=np.float64)
-    B, K, T, F = S4.shape
-    tape = np.empty((n,) + S4.shape, dtype=np.complex128)
 
-    def record(i, b, k, X):
-        if _perturb is not None:
-            X = _perturb('X', i, b, k, X)
-        tape[i - 1, b, k] = X
-        return X
+    def plan(S4, A4, single):
+        y = np.asarray(mixture, dtype=np.float64)
+        tape = np.empty((n,) + S4.shape, dtype=np.complex128)
 
-    if _tape is None:
-        misi(S4, y[None] if single else y, fsize, fshift, awin, swin, n, magnitudes=A4, perfectrec=perfectrec, _perturb=record)
-    else:
-        tape[...] = np.asarray(_tape).reshape(tape.shape)
-    _, lo, hi = _misi_cuts(T, fsize, fshift, perfectrec)
-    length = hi - lo
-    gC = gs = None
-    if grad_out is not None:
-        gC = np.asarray(grad_out, dtype=np.complex128)
-        if gC.shape != S.shape:
-            raise ValueError('grad_out of shape %s for spectrograms of shape %s' % (gC.shape, S.shape))
-        gC = gC[None] if single else gC
-    if grad_signals is not None:
-        gs = np.asarray(grad_signals, dtype=np.float64)
-        if gs.shape != S.shape[:-2] + (length,):
-            raise ValueError('grad_signals of shape %s: expected %s' % (gs.shape, S.shape[:-2] + (length,)))
-        gs = gs[None] if single else gs
-    gA, gS, gy = _misi_backward(tape, A4, gC, gs, fsize, fshift, awin, swin, perfectrec=perfectrec, _perturb=_perturb)
-    return (gA[0], gS[0], gy[0]) if single else (gA, gS, gy)
+        def record(i, b, k, X):
+            if _perturb is not None:
+                X = _perturb('X', i, b, k, X)
+            tape[i - 1, b, k] = X
+            return X
+
+        def forward():
+            misi(S4, y[None] if single else y, fsize, fshift, awin, swin, n, magnitudes=A4, perfectrec=perfectrec, _perturb=record)
+
+        def backward(gC, gs):
+            return _misi_backward(tape, A4, gC, gs, fsize, fshift, awin, swin, perfectrec=perfectrec, _perturb=_perturb)
+
+        _, lo, hi = _misi_cuts(S4.shape[2], fsize, fshift, perfectrec)
+        return tape, forward, backward, hi - lo, 'grad_signals'
+
+    return _grad_call('misi_grad', True, S, magnitudes, grad_out, grad_signals, _tape, plan)
 
 
-_misi_function = None
-
-
-def _misi_autograd_function():
-    """The torch.autograd.Function behind misi_layer, made on first use: importing this module needs no torch."""
-    global _misi_function
-    if _misi_function is not None:
-        return _misi_function
-    import torch
-    from torch.autograd.function import once_differentiable
-
-    class MisiLayer(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, A, S, y, fsize, fshift, awin, swin, n, perfectrec):
-            dev = S.device
-            B, K, T, F = (1,) + tuple(S.shape) if S.dim() == 3 else tuple(S.shape)
-            length = _capi.istft_length(T, fsize, fshift, perfectrec)
-            A, y = A.detach().contiguous(), y.detach().contiguous()
-            C = S.detach().clone(memory_format=torch.contiguous_format)          # the iteration is in place: never on the caller's storage
-            sig = torch.empty(tuple(S.shape[:-2]) + (length,), dtype=torch.float32, device=dev)
-            tape = torch.empty((n, B, K, T, F), dtype=torch.complex64, device=dev)
-            _capi.misi_tape_dev(C.data_ptr(), A.data_ptr(), y.data_ptr(), B, K, T, fsize, fshift, awin, swin, perfectrec, n,
-                                sig.data_ptr(), tape.data_ptr() if n else None, device=dev.index,
-                                stream=torch.cuda.current_stream(dev).cuda_stream)
-            ctx.save_for_backward(A, tape)
-            ctx.set_materialize_grads(False)
-            ctx.misi = (B, K, T, fsize, fshift, awin, swin, perfectrec, n, tuple(y.shape))
-            return C, sig
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, gC, gs):
-            A, tape = ctx.saved_tensors
-            B, K, T, fsize, fshift, awin, swin, perfectrec, n, y_shape = ctx.misi
-            dev = A.device
-            if gC is not None:
-                gC = gC.to(torch.complex64).contiguous()
-            if gs is not None:
-                gs = gs.to(torch.float32).contiguous()
-            gA = torch.empty_like(A)
-            gS = torch.empty(A.shape, dtype=torch.complex64, device=dev) if ctx.needs_input_grad[1] else None
-            gy = torch.empty(y_shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
-            ptr = lambda t: None if t is None else t.data_ptr()
-            _capi.misi_backward_dev(ptr(gC), ptr(gs), A.data_ptr(), tape.data_ptr() if n else None, B, K, T, fsize, fshift, awin,
-                                    swin, perfectrec, n, gA.data_ptr(), ptr(gS), ptr(gy), device=dev.index,
-                                    stream=torch.cuda.current_stream(dev).cuda_stream)
-            return (gA if ctx.needs_input_grad[0] else None, gS, gy) + (None,) * 6
-
-    _misi_function = MisiLayer
-    return MisiLayer
+_MISI_LAYER = _Layer(
+    3, True, lambda n, dims, extra: (n,) + dims,
+    lambda p, dims, mid, extra, kw: _capi.misi_tape_dev(p.C, p.A, p.y, *dims[:3], *mid, p.sig, p.tape, **kw),
+    lambda p, dims, mid, extra, kw: _capi.misi_backward_dev(p.gC, p.gs, p.A, p.tape, *dims[:3], *mid, p.gA, p.gS, p.gy, **kw))
 
 
 def misi_layer(A, S, mixture, fsize, fshift, awin, swin, iterations, perfectrec=False):
@@ -581,31 +667,9 @@ def misi_layer(A, S, mixture, fsize, fshift, awin, swin, iterations, perfectrec=
     of every projection for the backward pass: a complex64 tape of `iterations` times the size of S, held by the autograd graph
     until backward() has run (or the results are dropped).  The backward pass is three launches per iteration, as the forward
     pass (lws_gla.hip), and repeats bit for bit; its definition is misi_grad.  Zero iterations: C is a copy of S."""
-    import torch
     n, _ = _gla_args(iterations, 0.0)
-    for name, t, dtype in (('A', A, torch.float32), ('S', S, torch.complex64), ('mixture', mixture, torch.float32)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
-            raise ValueError('%s must be a %s torch tensor on the device' % (name, str(dtype).replace('torch.', '')))
-    if S.dim() not in (3, 4):
-        raise ValueError('expected (K, T, F) spectrograms of the sources or a (B, K, T, F) stack')
-    if A.shape != S.shape:
-        raise ValueError('magnitudes of shape %s for spectrograms of shape %s' % (tuple(A.shape), tuple(S.shape)))
-    if A.device != S.device or mixture.device != S.device:
-        raise ValueError('A, S and mixture must be on one device')
-    K, T, F = S.shape[-3:]
-    if K < 1:
-        raise ValueError('no sources')
-    if F != fsize // 2 + 1:
-        raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
-    length = _capi.istft_length(T, fsize, fshift, perfectrec)
-    if tuple(mixture.shape) != tuple(S.shape[:-3]) + (length,):
-        raise ValueError('mixture of shape %s for %s spectrograms of %d frames: expected %s' %
-                         (tuple(mixture.shape), tuple(S.shape[:-2]), T, tuple(S.shape[:-3]) + (length,)))
-    if n > 0 and _capi.stft_frames(length, fsize, fshift, perfectrec) != T:
-        raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' %
-                         (T, _capi.stft_frames(length, fsize, fshift, perfectrec)))
-    awin, swin = np.array(awin, dtype=np.float64), np.array(swin, dtype=np.float64)
-    return _misi_autograd_function().apply(A, S, mixture, int(fsize), int(fshift), awin, swin, n, bool(perfectrec))
+    awin, swin = _layer_args(A, S, fsize, fshift, awin, swin, n, perfectrec, mixture=mixture)
+    return _layer_apply(_MISI_LAYER, A, S, mixture, fsize, fshift, awin, swin, n, perfectrec)
 
 
 # --------------------------------------------------------------------------------------------
@@ -630,12 +694,8 @@ def _gla_backward(tape, A, grad_out, alpha, fsize, fshift, awin, swin, perfectre
                 gt = (1.0 + (alpha if i >= 2 else 0.0)) * gc
                 if i + 1 < n:               # gc_n = 0
                     gt = gt - alpha * gc_next
-            X = tape[i - 1, b]
-            mag = np.abs(X)
-            u = np.where(mag > 0, X / np.where(mag > 0, mag, 1.0), 1.0 + 0j)                  # step 3
-            q = np.conj(u) * gt
-            gA[b] += q.real
-            gX = np.where(mag > 0, 1j * u * (A[b] / np.where(mag > 0, mag, 1.0)) * q.imag, 0j)
+            ga, gX = _project_backward(tape[i - 1, b], A[b], gt)                               # step 3
+            gA[b] += ga
             gv = _misi_stft_adjoint(gX, fsize, fshift, awin, perfectrec)                       # step 4
             if _perturb is not None:
                 gv = np.real(_perturb('gv', i, b, gv))
@@ -669,83 +729,31 @@ def griffin_lim_grad(S, fsize, fshift, awin, swin, iterations, magnitudes, alpha
     _tape: (n, T, F) / (n, B, T, F), the X of every step from elsewhere -- a device run's -- instead of this function's own forward
     pass: the backward pass alone, teacher-forced.)"""
     n, alpha = _gla_args(iterations, alpha)
-    S = np.asarray(S)
-    if S.ndim not in (2, 3):
-        raise ValueError('expected a (T, F) spectrogram or a (B, T, F) stack')
-    if magnitudes is None:
-        raise ValueError('griffin_lim_grad differentiates with respect to the magnitudes: give them')
-    A = np.asarray(magnitudes, dtype=np.float64)
-    if A.shape != S.shape:
-        raise ValueError('magnitudes of shape %s for a spectrogram of shape %s' % (A.shape, S.shape))
-    single = S.ndim == 2
-    S3, A3 = (S[None], A[None]) if single else (S, A)
-    tape = np.empty((n,) + S3.shape, dtype=np.complex128)
 
-    def record(i, b, X):
-        if _perturb is not None:
-            X = _perturb('X', i, b, X)
-        tape[i - 1, b] = X
-        return X
+    def plan(S3, A3, single):
+        tape = np.empty((n,) + S3.shape, dtype=np.complex128)
 
-    if _tape is None:
-        griffin_lim(S3, fsize, fshift, awin, swin, n, alpha=alpha, magnitudes=A3, perfectrec=perfectrec, _perturb=record)
-    else:
-        tape[...] = np.asarray(_tape).reshape(tape.shape)
-    gC = None
-    if grad_out is not None:
-        gC = np.asarray(grad_out, dtype=np.complex128)
-        if gC.shape != S.shape:
-            raise ValueError('grad_out of shape %s for a spectrogram of shape %s' % (gC.shape, S.shape))
-        gC = gC[None] if single else gC
-    gA, gS = _gla_backward(tape, A3, gC, alpha, fsize, fshift, awin, swin, perfectrec=perfectrec, _perturb=_perturb)
-    return (gA[0], gS[0]) if single else (gA, gS)
+        def record(i, b, X):
+            if _perturb is not None:
+                X = _perturb('X', i, b, X)
+            tape[i - 1, b] = X
+            return X
+
+        def forward():
+            griffin_lim(S3, fsize, fshift, awin, swin, n, alpha=alpha, magnitudes=A3, perfectrec=perfectrec, _perturb=record)
+
+        def backward(gC, _):
+            return _gla_backward(tape, A3, gC, alpha, fsize, fshift, awin, swin, perfectrec=perfectrec, _perturb=_perturb)
+
+        return tape, forward, backward, None, None
+
+    return _grad_call('griffin_lim_grad', False, S, magnitudes, grad_out, None, _tape, plan)
 
 
-_gla_function = None
-
-
-def _gla_autograd_function():
-    """The torch.autograd.Function behind griffin_lim_layer, made on first use: importing this module needs no torch."""
-    global _gla_function
-    if _gla_function is not None:
-        return _gla_function
-    import torch
-    from torch.autograd.function import once_differentiable
-
-    class GriffinLimLayer(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, A, S, fsize, fshift, awin, swin, n, alpha, perfectrec):
-            dev = S.device
-            B, T, F = (1,) + tuple(S.shape) if S.dim() == 2 else tuple(S.shape)
-            A = A.detach().contiguous()
-            C = S.detach().clone(memory_format=torch.contiguous_format)          # the iteration is in place: never on the caller's storage
-            tape = torch.empty((n, B, T, F), dtype=torch.complex64, device=dev)
-            _capi.griffin_lim_tape_dev(C.data_ptr(), A.data_ptr(), B, T, fsize, fshift, awin, swin, perfectrec, n, alpha,
-                                       tape.data_ptr() if n else None, device=dev.index,
-                                       stream=torch.cuda.current_stream(dev).cuda_stream)
-            ctx.save_for_backward(A, tape)
-            ctx.set_materialize_grads(False)
-            ctx.gla = (B, T, fsize, fshift, awin, swin, perfectrec, n, alpha)
-            return C
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, gC):
-            A, tape = ctx.saved_tensors
-            B, T, fsize, fshift, awin, swin, perfectrec, n, alpha = ctx.gla
-            dev = A.device
-            if gC is not None:
-                gC = gC.to(torch.complex64).contiguous()
-            gA = torch.empty_like(A)
-            gS = torch.empty(A.shape, dtype=torch.complex64, device=dev) if ctx.needs_input_grad[1] else None
-            ptr = lambda t: None if t is None else t.data_ptr()
-            _capi.griffin_lim_backward_dev(ptr(gC), A.data_ptr(), tape.data_ptr() if n else None, B, T, fsize, fshift, awin, swin,
-                                           perfectrec, n, alpha, gA.data_ptr(), ptr(gS), device=dev.index,
-                                           stream=torch.cuda.current_stream(dev).cuda_stream)
-            return (gA if ctx.needs_input_grad[0] else None, gS) + (None,) * 7
-
-    _gla_function = GriffinLimLayer
-    return GriffinLimLayer
+_GLA_LAYER = _Layer(
+    2, False, lambda n, dims, extra: (n,) + dims,
+    lambda p, dims, mid, extra, kw: _capi.griffin_lim_tape_dev(p.C, p.A, *dims[:2], *mid, extra[0], p.tape, **kw),
+    lambda p, dims, mid, extra, kw: _capi.griffin_lim_backward_dev(p.gC, p.A, p.tape, *dims[:2], *mid, extra[0], p.gA, p.gS, **kw))
 
 
 def griffin_lim_layer(A, S, fsize, fshift, awin, swin, iterations, alpha=0.99, perfectrec=False):
@@ -758,25 +766,9 @@ def griffin_lim_layer(A, S, fsize, fshift, awin, swin, iterations, alpha=0.99, p
     until backward() has run (or the result is dropped); the momentum needs no tape of its own.  The backward pass is two launches
     per iteration, as the forward pass (lws_gla.hip), and repeats bit for bit; its definition is griffin_lim_grad.  Zero
     iterations: C is a copy of S.  Raises ValueError, as griffin_lim_dev does, for a frame count the round trip does not keep."""
-    import torch
     n, alpha = _gla_args(iterations, alpha)
-    for name, t, dtype in (('A', A, torch.float32), ('S', S, torch.complex64)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
-            raise ValueError('%s must be a %s torch tensor on the device' % (name, str(dtype).replace('torch.', '')))
-    if S.dim() not in (2, 3):
-        raise ValueError('expected a (T, F) spectrogram or a (B, T, F) stack')
-    if A.shape != S.shape:
-        raise ValueError('magnitudes of shape %s for a spectrogram of shape %s' % (tuple(A.shape), tuple(S.shape)))
-    if A.device != S.device:
-        raise ValueError('A and S must be on one device')
-    T, F = S.shape[-2:]
-    if F != fsize // 2 + 1:
-        raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
-    back = _capi.stft_frames(_capi.istft_length(T, fsize, fshift, perfectrec), fsize, fshift, perfectrec)
-    if n > 0 and back != T:
-        raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
-    awin, swin = np.array(awin, dtype=np.float64), np.array(swin, dtype=np.float64)
-    return _gla_autograd_function().apply(A, S, int(fsize), int(fshift), awin, swin, n, alpha, bool(perfectrec))
+    awin, swin = _layer_args(A, S, fsize, fshift, awin, swin, n, perfectrec)
+    return _layer_apply(_GLA_LAYER, A, S, None, fsize, fshift, awin, swin, n, perfectrec, alpha)
 
 
 # --------------------------------------------------------------------------------------------
@@ -786,11 +778,6 @@ def _look_ahead_arg(look_ahead):
     if int(look_ahead) != look_ahead or look_ahead < 0:
         raise ValueError('look_ahead must be a non-negative integer, got %r' % (look_ahead,))
     return int(look_ahead)
-
-
-def _rtisi_project(X, A):
-    mag = np.abs(X)
-    return np.where(mag > 0, A * X / np.where(mag > 0, mag, 1.0), A + 0j)
 
 
 def _start_arg(start, allowed):
@@ -861,7 +848,7 @@ def rtisi_la(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=
                     X = np.fft.rfft(awin * y[fshift * entered: fshift * entered + fsize])
                     if _perturb is not None:
                         X = _perturb(m, 0, b, X[None])[0]
-                    c[entered] = _rtisi_project(X, A3[b, entered])
+                    c[entered] = _project(X, A3[b, entered])
                 f[entered] = swin * np.fft.irfft(c[entered], fsize)
                 entered += 1
             for it in range(1, n + 1):
@@ -872,7 +859,7 @@ def rtisi_la(S, fsize, fshift, awin, swin, iterations, look_ahead=3, magnitudes=
                 X = np.stack([np.fft.rfft(awin * y[fshift * j: fshift * j + fsize]) for j in range(m, last + 1)])
                 if _perturb is not None:
                     X = _perturb(m, it, b, X)
-                c[m: last + 1] = _rtisi_project(X, A3[b, m: last + 1])
+                c[m: last + 1] = _project(X, A3[b, m: last + 1])
                 for j in range(m, last + 1):
                     f[j] = swin * np.fft.irfft(c[j], fsize)
             done[fshift * m: fshift * m + fsize] += f[m]
@@ -1092,13 +1079,8 @@ def _rtisi_backward(tape, A, grad_out, grad_signal, fsize, fshift, awin, swin, L
                     gc = pert('gc', m, it, b, _rtisi_inv_adjoint(gdone[win(m)] if head else G[win(j)], fsize, swin))
                     if head and grad_out is not None:
                         gc = gc + grad_out[b, m]
-                    X = tape[b, m, it - 1, j - m]
-                    mag = np.abs(X)
-                    safe = np.where(mag > 0, mag, 1.0)
-                    u = np.where(mag > 0, X / safe, 1.0 + 0j)
-                    q = np.conj(u) * gc
-                    gA[b, j] += q.real
-                    gX = np.where(mag > 0, 1j * u * (A[b, j] / safe) * q.imag, 0j)
+                    ga, gX = _project_backward(tape[b, m, it - 1, j - m], A[b, j], gc)
+                    gA[b, j] += ga
                     Gn[win(j)] += np.real(pert('gv', m, it, b, _rtisi_fwd_adjoint(gX, fsize, awin)))
                 Gn *= keep                                          # Jacobi: one sum fed every active frame and `done`
                 gdone += Gn
@@ -1142,103 +1124,41 @@ def rtisi_la_grad(S, fsize, fshift, awin, swin, iterations, magnitudes, look_ahe
     not read.)"""
     n, _ = _gla_args(iterations, 0.0)
     LA = _look_ahead_arg(look_ahead)
-    S = np.asarray(S)
-    if S.ndim not in (2, 3):
-        raise ValueError('expected a (T, F) spectrogram or a (B, T, F) stack')
-    if magnitudes is None:
-        raise ValueError('rtisi_la_grad differentiates with respect to the magnitudes: give them')
-    A = np.asarray(magnitudes, dtype=np.float64)
-    if A.shape != S.shape:
-        raise ValueError('magnitudes of shape %s for a spectrogram of shape %s' % (A.shape, S.shape))
-    single = S.ndim == 2
-    S3, A3 = (S[None], A[None]) if single else (S, A)
-    B, T, F = S3.shape
-    if F != fsize // 2 + 1 or fsize % 2:
-        raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
-    awin, swin = np.asarray(awin, dtype=np.float64), np.squeeze(np.asarray(swin, dtype=np.float64))
-    _, lo, hi = _misi_cuts(T, fsize, fshift, perfectrec)
-    length = max(hi - lo, 0)
-    if perfectrec is True and n > 0:
-        back = stft(np.zeros(length), fsize, fshift, awin, perfectrec=True).shape[0]
-        if back != T:
-            raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
-    W = min(LA, T - 1) + 1
-    tape = np.zeros((B, T, n, W, F), dtype=np.complex128)
 
-    def record(m, it, b, X):
-        if _perturb is not None:
-            X = _perturb('X', m, it, b, X)
-        tape[b, m, it - 1, :X.shape[0]] = X
-        return X
+    def plan(S3, A3, single):
+        B, T, F = S3.shape
+        if F != fsize // 2 + 1 or fsize % 2:
+            raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
+        wa, ws = np.asarray(awin, dtype=np.float64), np.squeeze(np.asarray(swin, dtype=np.float64))
+        _, lo, hi = _misi_cuts(T, fsize, fshift, perfectrec)
+        length = max(hi - lo, 0)
+        if perfectrec is True and n > 0:
+            back = stft(np.zeros(length), fsize, fshift, wa, perfectrec=True).shape[0]
+            if back != T:
+                raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
+        tape = np.zeros((B, T, n, min(LA, T - 1) + 1, F), dtype=np.complex128)
 
-    if _tape is None:
-        rtisi_la(S3, fsize, fshift, awin, swin, n, look_ahead=LA, magnitudes=A3, perfectrec=perfectrec, _perturb=record)
-    else:
-        tape[...] = np.asarray(_tape).reshape(tape.shape)
-    gC = gx = None
-    if grad_out is not None:
-        gC = np.asarray(grad_out, dtype=np.complex128)
-        if gC.shape != S.shape:
-            raise ValueError('grad_out of shape %s for a spectrogram of shape %s' % (gC.shape, S.shape))
-        gC = gC[None] if single else gC
-    if grad_signal is not None:
-        gx = np.asarray(grad_signal, dtype=np.float64)
-        if gx.shape != S.shape[:-2] + (length,):
-            raise ValueError('grad_signal of shape %s: expected %s' % (gx.shape, S.shape[:-2] + (length,)))
-        gx = gx[None] if single else gx
-    gA, gS = _rtisi_backward(tape, A3, gC, gx, fsize, fshift, awin, swin, LA, perfectrec=perfectrec, _perturb=_perturb)
-    return (gA[0], gS[0]) if single else (gA, gS)
+        def record(m, it, b, X):
+            if _perturb is not None:
+                X = _perturb('X', m, it, b, X)
+            tape[b, m, it - 1, :X.shape[0]] = X
+            return X
+
+        def forward():
+            rtisi_la(S3, fsize, fshift, wa, ws, n, look_ahead=LA, magnitudes=A3, perfectrec=perfectrec, _perturb=record)
+
+        def backward(gC, gx):
+            return _rtisi_backward(tape, A3, gC, gx, fsize, fshift, wa, ws, LA, perfectrec=perfectrec, _perturb=_perturb)
+
+        return tape, forward, backward, length, 'grad_signal'
+
+    return _grad_call('rtisi_la_grad', False, S, magnitudes, grad_out, grad_signal, _tape, plan)
 
 
-_rtisi_function = None
-
-
-def _rtisi_autograd_function():
-    """The torch.autograd.Function behind rtisi_la_layer, made on first use: importing this module needs no torch."""
-    global _rtisi_function
-    if _rtisi_function is not None:
-        return _rtisi_function
-    import torch
-    from torch.autograd.function import once_differentiable
-
-    class RtisiLaLayer(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, A, S, fsize, fshift, awin, swin, n, LA, perfectrec):
-            dev = S.device
-            B, T, F = (1,) + tuple(S.shape) if S.dim() == 2 else tuple(S.shape)
-            length = max(_capi.istft_length(T, fsize, fshift, perfectrec), 0)
-            A = A.detach().contiguous()
-            C = S.detach().clone(memory_format=torch.contiguous_format)          # the iteration is in place: never on the caller's storage
-            sig = torch.empty(tuple(S.shape[:-2]) + (length,), dtype=torch.float32, device=dev)
-            tape = torch.empty((B, T, n, min(LA, T - 1) + 1, F), dtype=torch.complex64, device=dev)
-            _capi.rtisi_la_tape_dev(C.data_ptr(), A.data_ptr(), sig.data_ptr() if length else None, B, T, fsize, fshift, awin, swin,
-                                    perfectrec, n, LA, tape.data_ptr() if n else None, device=dev.index,
-                                    stream=torch.cuda.current_stream(dev).cuda_stream)
-            ctx.save_for_backward(A, tape)
-            ctx.set_materialize_grads(False)
-            ctx.rtisi = (B, T, fsize, fshift, awin, swin, perfectrec, n, LA)
-            return C, sig
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, gC, gx):
-            A, tape = ctx.saved_tensors
-            B, T, fsize, fshift, awin, swin, perfectrec, n, LA = ctx.rtisi
-            dev = A.device
-            if gC is not None:
-                gC = gC.to(torch.complex64).contiguous()
-            if gx is not None:
-                gx = gx.to(torch.float32).contiguous() if gx.numel() else None
-            gA = torch.empty_like(A)
-            gS = torch.empty(A.shape, dtype=torch.complex64, device=dev) if ctx.needs_input_grad[1] else None
-            ptr = lambda t: None if t is None else t.data_ptr()
-            _capi.rtisi_la_backward_dev(ptr(gC), ptr(gx), A.data_ptr(), tape.data_ptr() if n else None, B, T, fsize, fshift, awin,
-                                        swin, perfectrec, n, LA, gA.data_ptr(), ptr(gS), device=dev.index,
-                                        stream=torch.cuda.current_stream(dev).cuda_stream)
-            return (gA if ctx.needs_input_grad[0] else None, gS) + (None,) * 7
-
-    _rtisi_function = RtisiLaLayer
-    return RtisiLaLayer
+_RTISI_LAYER = _Layer(
+    2, True, lambda n, dims, extra: (dims[0], dims[1], n, min(extra[0], dims[1] - 1) + 1, dims[2]),
+    lambda p, dims, mid, extra, kw: _capi.rtisi_la_tape_dev(p.C, p.A, p.sig, *dims[:2], *mid, extra[0], p.tape, **kw),
+    lambda p, dims, mid, extra, kw: _capi.rtisi_la_backward_dev(p.gC, p.gs, p.A, p.tape, *dims[:2], *mid, extra[0], p.gA, p.gS, **kw))
 
 
 def rtisi_la_layer(A, S, fsize, fshift, awin, swin, iterations, look_ahead=3, perfectrec=False, return_signal=False):
@@ -1253,26 +1173,10 @@ def rtisi_la_layer(A, S, fsize, fshift, awin, swin, iterations, look_ahead=3, pe
     lws_gla.hip), and repeats bit for bit; its definition is rtisi_la_grad.  Zero iterations: C is a copy of S.  Not covered:
     start='overlap', online MISI and the stream classes.  Raises ValueError, as rtisi_la_dev does, for a frame count the round
     trip does not keep."""
-    import torch
     n, _ = _gla_args(iterations, 0.0)
     LA = _look_ahead_arg(look_ahead)
-    for name, t, dtype in (('A', A, torch.float32), ('S', S, torch.complex64)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
-            raise ValueError('%s must be a %s torch tensor on the device' % (name, str(dtype).replace('torch.', '')))
-    if S.dim() not in (2, 3):
-        raise ValueError('expected a (T, F) spectrogram or a (B, T, F) stack')
-    if A.shape != S.shape:
-        raise ValueError('magnitudes of shape %s for a spectrogram of shape %s' % (tuple(A.shape), tuple(S.shape)))
-    if A.device != S.device:
-        raise ValueError('A and S must be on one device')
-    T, F = S.shape[-2:]
-    if F != fsize // 2 + 1:
-        raise ValueError('frames of %d samples have %d bins, got %d' % (fsize, fsize // 2 + 1, F))
-    back = _capi.stft_frames(_capi.istft_length(T, fsize, fshift, perfectrec), fsize, fshift, perfectrec)
-    if n > 0 and perfectrec and back != T:
-        raise ValueError('the round trip turns %d frames into %d (too few frames for perfectrec)' % (T, back))
-    awin, swin = np.array(awin, dtype=np.float64), np.squeeze(np.array(swin, dtype=np.float64))
-    C, x = _rtisi_autograd_function().apply(A, S, int(fsize), int(fshift), awin, swin, n, LA, bool(perfectrec))
+    awin, swin = _layer_args(A, S, fsize, fshift, awin, swin, n, perfectrec, round_trip_always=False, squeeze_swin=True)
+    C, x = _layer_apply(_RTISI_LAYER, A, S, None, fsize, fshift, awin, swin, n, perfectrec, LA)
     return (C, x) if return_signal else C
 
 
@@ -1366,7 +1270,7 @@ def misi_la(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3, mag
                     X = np.fft.rfft(awin * (keep * yfull)[fshift * entered: fshift * entered + fsize])[None, None]
                     if _perturb is not None:
                         X = _perturb(m, 0, b, X)
-                    c[:, entered] = _rtisi_project(X[0], A4[b, :, entered])
+                    c[:, entered] = _project(X[0], A4[b, :, entered])
                 for k in range(K):
                     f[k, entered] = swin * np.fft.irfft(c[k, entered], fsize)
                 num[fshift * entered: fshift * entered + fsize] += w
@@ -1386,7 +1290,7 @@ def misi_la(S, mixture, fsize, fshift, awin, swin, iterations, look_ahead=3, mag
                               for k in range(K)])
                 if _perturb is not None:
                     X = _perturb(m, it, b, X)
-                c[:, m: last + 1] = _rtisi_project(X, A4[b, :, m: last + 1])
+                c[:, m: last + 1] = _project(X, A4[b, :, m: last + 1])
                 for k in range(K):
                     for j in range(m, last + 1):
                         f[k, j] = swin * np.fft.irfft(c[k, j], fsize)

@@ -6,14 +6,12 @@ value checks have no fixed tolerance: a bar is the rel-L2 distance the host fp64
 measured here on the host side only; tests/test_gla_grad_host.py holds the model itself to the far-entry cap.  Distances, caps and
 bars are taken per spectrogram, so that the small-scale members of a stack are held as tightly as the loud ones.  Every figure is
 printed before it is asserted (pytest -s)."""
-import json
-import os
-
 import numpy as np
 import pytest
 
 import lws_amd
 import gla_grad_cases as gc
+from gpu_grad_helpers import Margins, dev, f64, ptr, rows_of
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -21,22 +19,11 @@ pytestmark = pytest.mark.gpu
 capi = lws_amd._capi
 # per (fsize, fshift, perfectrec): [rows, max rel-L2 of gA, max rel-L2 / bar of the whole run (gA, gS), max far fraction of gA,
 # max rel-L2 / bar of the teacher-forced pass, max |lhs - rhs| / bar of the adjoint identity]
-MARGINS = {}
 FIGURES = ("rows", "max_rel_l2_gA", "max_rel_l2_over_bar", "max_far_fraction_gA", "max_teacher_forced_rel_l2_over_bar",
            "max_adjoint_gap_over_bar")
+MARGINS = Margins(FIGURES)
+margins = MARGINS.row
 RUNS = [(n, alpha) for n in gc.STEPS for alpha in gc.ALPHAS]
-
-
-def margins(key):
-    return MARGINS.setdefault(key[:3], [0, 0.0, 0.0, 0.0, 0.0, 0.0])
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a)).cuda()          # (a copy: the cases are read-only)
-
-
-def ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def run(p, A, S, n, alpha, gC, want_S=True):
@@ -84,29 +71,12 @@ class Cases:
         assert A.any(axis=-1).all()
         return None
 
-    @staticmethod
-    def note(key, rows=0, **figures):
-        """Count `rows` whole-run rows and keep the largest of each figure, named as in FIGURES, for the shape of `key`."""
-        m = margins(key)
-        m[0] += rows
-        for name, v in figures.items():
-            m[FIGURES.index(name)] = max(m[FIGURES.index(name)], v)
+    note = staticmethod(MARGINS.note)             # (key, rows=0, **figures): count rows, keep the largest of each figure
 
 
 def on_device(key, src=Cases):
     p, A, c0, gC = src.case(key)
     return (p,) + tuple(dev(a) for a in (A, c0, gC))
-
-
-def f64(t):
-    a = t.cpu().numpy()
-    return a.astype(np.complex128 if np.iscomplexobj(a) else np.float64)
-
-
-def rows_of(name, got, ref, per, seen=None):
-    """(label, distance, bar) per spectrogram; seen: (B, T) bool, the frames compared, None for all."""
-    pick = (lambda a, b: a[b]) if seen is None else (lambda a, b: a[b][seen[b]])
-    return [("%s b=%d" % (name, b), gc.rel(pick(got, b), pick(ref, b)), 3 * gc.rel(pick(per, b), pick(ref, b))) for b in range(ref.shape[0])]
 
 
 def check_bits(key, n, alpha, src=Cases):
@@ -367,11 +337,5 @@ def test_zz_margins_actually_achieved():
         test_matches_host((64, 16, True, 12))
         test_teacher_forced_backward((64, 16, True, 12))
         test_adjoint_of_the_forward_kernels((64, 16, True, 12))
-    report = {"%d,%d,%s" % k: dict(zip(FIGURES, v)) for k, v in sorted(MARGINS.items())}
-    out = os.environ.get("LWS_MARGINS_DIR", "")
-    if out and os.path.isdir(out):
-        with open(os.path.join(out, "gla_grad_margins.json"), "w") as f:
-            json.dump(report, f, indent=1)
-            f.write("\n")
-    print(report)
+    MARGINS.report("gla_grad_margins.json")
     assert all(v[2] <= 1.0 and v[3] <= gc.FAR_CAP and v[4] <= 1.0 and v[5] <= 1.0 for v in MARGINS.values())

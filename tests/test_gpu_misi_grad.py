@@ -6,14 +6,12 @@ checks have no fixed tolerance: a bar is the rel-L2 distance the host fp64 pass 
 here on the host side only; tests/test_misi_grad_host.py holds the model itself to the far-entry cap.  Distances, caps and bars are
 taken per mixture and per source (per mixture for gy), so that the weak source of a mixture and the small-scale members of a stack
 are held as tightly as the loud ones.  Every figure is printed before it is asserted (pytest -s)."""
-import json
-import os
-
 import numpy as np
 import pytest
 
 import lws_amd
 import misi_grad_cases as gc
+from gpu_grad_helpers import Margins, dev, f64, ptr
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -21,15 +19,8 @@ pytestmark = pytest.mark.gpu
 capi = lws_amd._capi
 # per (fsize, fshift, perfectrec): [rows, max rel-L2 of gA, max rel-L2 / bar of the whole run (gA, gS, gy), max far fraction of gA,
 # max rel-L2 / bar of the teacher-forced pass]
-MARGINS = {}
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a)).cuda()          # (a copy: the cases are read-only)
-
-
-def ptr(t):
-    return None if t is None else t.data_ptr()
+FIGURES = ("rows", "max_rel_l2_gA", "max_rel_l2_over_bar", "max_far_fraction_gA", "max_teacher_forced_rel_l2_over_bar")
+MARGINS = Margins(FIGURES)
 
 
 def run(p, A, S, y, n, gC, gs, want_S=True, want_y=True):
@@ -50,11 +41,6 @@ def run(p, A, S, y, n, gC, gs, want_S=True, want_y=True):
 def on_device(key):
     p, A, c0, y, gC, gs = gc.case(*key)
     return (p,) + tuple(dev(a) for a in (A, c0, y, gC, gs))
-
-
-def f64(t):
-    a = t.cpu().numpy()
-    return a.astype(np.complex128 if np.iscomplexobj(a) else np.float64)
 
 
 def ratio(dist, bar):
@@ -324,12 +310,5 @@ def test_zz_margins_actually_achieved():
     if not MARGINS:
         test_matches_host((64, 16, True, 12, 3))
         test_teacher_forced_backward((64, 16, True, 12, 3))
-    report = {"%d,%d,%s" % k: {"rows": v[0], "max_rel_l2_gA": v[1], "max_rel_l2_over_bar": v[2], "max_far_fraction_gA": v[3],
-                               "max_teacher_forced_rel_l2_over_bar": v[4]} for k, v in sorted(MARGINS.items())}
-    out = os.environ.get("LWS_MARGINS_DIR", "")
-    if out and os.path.isdir(out):
-        with open(os.path.join(out, "misi_grad_margins.json"), "w") as f:
-            json.dump(report, f, indent=1)
-            f.write("\n")
-    print(report)
+    MARGINS.report("misi_grad_margins.json")
     assert all(v[2] <= 1.0 and v[3] <= gc.FAR_CAP and v[4] <= 1.0 for v in MARGINS.values())

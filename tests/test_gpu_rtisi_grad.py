@@ -6,14 +6,12 @@ value checks have no fixed tolerance: a bar is the rel-L2 distance the host fp64
 measured here on the host side only; tests/test_rtisi_grad_host.py holds the model itself to the far-entry cap.  Distances, caps
 and bars are taken per spectrogram, so that the small-scale members of a stack are held as tightly as the loud ones.  Every case
 has at most 12 frames.  Every figure is printed before it is asserted (pytest -s)."""
-import json
-import os
-
 import numpy as np
 import pytest
 
 import lws_amd
 import rtisi_grad_cases as rc
+from gpu_grad_helpers import Margins, dev, f64, ptr, rows_of
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -21,24 +19,12 @@ pytestmark = pytest.mark.gpu
 capi = lws_amd._capi
 # per (fsize, fshift, perfectrec): [rows, max rel-L2 of gA, max rel-L2 / bar of the whole run (gA, gS), max far fraction of gA,
 # max rel-L2 / bar of the teacher-forced pass, max rel-L2 / bar of the tape]
-MARGINS = {}
 FIGURES = ("rows", "max_rel_l2_gA", "max_rel_l2_over_bar", "max_far_fraction_gA", "max_teacher_forced_rel_l2_over_bar",
            "max_tape_rel_l2_over_bar")
+MARGINS = Margins(FIGURES)
 # (fsize, fshift, perfectrec, T): [(look-ahead, iterations, backward state in LDS)] -- both placements of k_rtisi_bwd, asserted
 # through lws_rtisi_la_bwd_placement; the table is with the cases, where the host tests read it too
 PLACEMENTS = rc.PLACEMENTS
-
-
-def margins(key):
-    return MARGINS.setdefault(key[:3], [0, 0.0, 0.0, 0.0, 0.0, 0.0])
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a)).cuda()          # (a copy: the cases are read-only)
-
-
-def ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def run(p, A, S, LA, n, gC, gx, want_S=True):
@@ -66,13 +52,7 @@ class Cases:
     grad = staticmethod(rc.grad)                          # (key, LA, n, **kw) -> (gA, gS) of lws_amd.rtisi_la_grad
     host_tape = staticmethod(rc.host_tape)                # (key, LA, n, perturbed=False)
 
-    @staticmethod
-    def note(key, rows=0, **figures):
-        """Count `rows` whole-run rows and keep the largest of each figure, named as in FIGURES, for the shape of `key`."""
-        m = margins(key)
-        m[0] += rows
-        for name, v in figures.items():
-            m[FIGURES.index(name)] = max(m[FIGURES.index(name)], v)
+    note = staticmethod(MARGINS.note)             # (key, rows=0, **figures): count rows, keep the largest of each figure
 
     @staticmethod
     def case(key):
@@ -92,17 +72,6 @@ class Cases:
 def on_device(key, src=Cases):
     p, A, c0, gC, gx = src.case(key)
     return (p,) + tuple(dev(a) for a in (A, c0, gC, gx))
-
-
-def f64(t):
-    a = t.cpu().numpy()
-    return a.astype(np.complex128 if np.iscomplexobj(a) else np.float64)
-
-
-def rows_of(name, got, ref, per, seen=None):
-    """(label, distance, bar) per spectrogram; seen: (B, T) bool, the frames compared, None for all."""
-    pick = (lambda a, b: a[b]) if seen is None else (lambda a, b: a[b][seen[b]])
-    return [("%s b=%d" % (name, b), rc.rel(pick(got, b), pick(ref, b)), 3 * rc.rel(pick(per, b), pick(ref, b))) for b in range(ref.shape[0])]
 
 
 def check_whole_run(key, LA, n, src=Cases):
@@ -333,11 +302,5 @@ def test_zz_margins_actually_achieved():
         check_whole_run((64, 16, True, 12), 3, 3)
         check_teacher_forced((64, 16, True, 12), 3, 3)
         check_tape((64, 16, True, 12), 3, 3)
-    report = {"%d,%d,%s" % k: dict(zip(FIGURES, v)) for k, v in sorted(MARGINS.items())}
-    out = os.environ.get("LWS_MARGINS_DIR", "")
-    if out and os.path.isdir(out):
-        with open(os.path.join(out, "rtisi_grad_margins.json"), "w") as f:
-            json.dump(report, f, indent=1)
-            f.write("\n")
-    print(report)
+    MARGINS.report("rtisi_grad_margins.json")
     assert all(v[2] <= 1.0 and v[3] <= rc.FAR_CAP and v[4] <= 1.0 and v[5] <= 1.0 for v in MARGINS.values())

@@ -25,7 +25,7 @@ pytestmark = pytest.mark.gpu
 
 import test_gpu_gla_grad as gg  # noqa: E402
 import test_gpu_rtisi_grad as rg  # noqa: E402
-from test_gpu_gla_grad import dev, f64  # noqa: E402
+from gpu_grad_helpers import dev, f64, rows_of  # noqa: E402
 
 capi = lws_amd._capi
 MARGINS = {}
@@ -114,7 +114,7 @@ def test_gla_tape_and_layer_give_the_bits_of_griffin_lim_dev(kind, key):
         tape = f64(gg.check_bits(key, n, alpha, src))
         stack = lambda t: np.moveaxis(t, 1, 0)                          # (B, n, T, F)
         ref, per = src.host_tape(key, n, alpha), src.host_tape(key, n, alpha, perturbed=True)
-        for label, dist, bar in gg.rows_of("tape", stack(tape), stack(ref), stack(per)):
+        for label, dist, bar in rows_of("tape", stack(tape), stack(ref), stack(per)):
             print("%s %s n=%d alpha=%g %s: rel-L2 %.3e (bar %.3e)" % (src.tag, wc.ident(key), n, alpha, label, dist, bar))
             src.note(key, max_tape_rel_l2_over_bar=dist / bar)
             assert dist <= bar, (label, dist, bar)

@@ -1,6 +1,7 @@
 """Compare two device assembly listings kernel by kernel: which functions have the same instruction stream (basic-block label
 numbers and comments aside), which differ and where, and which exist in one listing only.  The way to check that a change to a
-translation unit left its other kernels alone, e.g. for lws_gla.hip against the parent commit:
+translation unit left its other kernels alone, e.g. for lws_gla.hip -- the unit: the file and the kernel headers it includes, lws_*_kernels.h,
+lws_rtisi_march.h and lws_fft.h with its named transform instances (FFT_USER_*) -- against the parent commit:
     cd lws_amd/csrc
     hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 --cuda-device-only -S lws_gla.hip -o new.s
     git stash; hipcc ... -S lws_gla.hip -o old.s; git stash pop
