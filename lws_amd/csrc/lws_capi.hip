@@ -320,7 +320,7 @@ Route choose_engine(const lws_plan *p, const Stage &st, Engine from = Engine::Sy
     };
 
     // 1. fp32 batch sweeps of the plans a systolic build was made for (plan creation)
-    if (at(Engine::Systolic) && !fp64 && batch && !generic && p->sysb && p->sysb->supports(p->sys, st.wsel, T)) return pick(Engine::Systolic);
+    if (at(Engine::Systolic) && !fp64 && batch && !generic && p->sysb && lws::systolic_supports(p->sys, st.wsel, T)) return pick(Engine::Systolic);
     if (at(Engine::TeamFirst) && sw.team_first && (!fp64 || sw.team_fp64 || online) && team()) return pick(Engine::TeamFirst);
     // 2. online and no-future sweeps: the moving window / the last Q + 1 frames in LDS (fp64: the generic engine's bits)
     if (at(Engine::OnlineLds) && !fp64 && online && !generic &&
@@ -392,8 +392,8 @@ int launch_route(lws_plan *p, const Route &r, const lws::GenericArgs<real> &a, i
     if (!self_timed) begin_timing(p, s);
     switch (r.engine) {
     case Engine::Systolic:
-        if constexpr (!fp64) e = p->sysb->launch(p->sys, a.wsel, a.state, a.amp, a.thr, B, a.T, a.n_thr, s, &launches, p->ev0, p->ev1);
-        name = p->sysb->name(p->sys), what = "systolic";
+        if constexpr (!fp64) e = lws::launch_systolic(*p->sysb, p->sys, a.wsel, a.state, a.amp, a.thr, B, a.T, a.n_thr, s, &launches, p->ev0, p->ev1);
+        name = lws::systolic_name(p->sys), what = "systolic";
         break;
     case Engine::TeamFirst:
     case Engine::Team:
@@ -498,10 +498,10 @@ int run_direct_batch(lws_plan *p, const float2 *in_dev, float2 *out_dev, int B, 
     if ((rc = p->mean_amp.ensure((size_t)B * sizeof(double)))) return rc;
     if ((rc = p->thr_host_copy.ensure((size_t)st.iters * sizeof(double)))) return rc;
     if ((rc = p->thr_scaled.ensure((size_t)B * st.iters * sizeof(float)))) return rc;
-    const size_t n_part = p->sysb->io_partials(p->sys, T);
+    const size_t n_part = lws::systolic_io_partials(*p->sysb, p->sys, T);
     if ((rc = p->row_sums.ensure((size_t)B * n_part * sizeof(double)))) return rc;
     double *partial = static_cast<double *>(p->row_sums.p), *mean = static_cast<double *>(p->mean_amp.p);
-    hipError_t e = p->sysb->io_load(p->sys, in_dev, B, T, st.iters, partial, mean, s);
+    hipError_t e = lws::systolic_io_load(*p->sysb, p->sys, in_dev, B, T, st.iters, partial, mean, s);
     if (e != hipSuccess) return fail(LWS_ERR_HIP, "systolic load failed: %s", hipGetErrorString(e));
     HIP_TRY(hipMemcpyAsync(p->thr_host_copy.p, st.thr, sizeof(double) * st.iters, hipMemcpyHostToDevice, s));
     HIP_TRY(lws::launch_scale_thresholds<float>(static_cast<const double *>(p->thr_host_copy.p), mean,
@@ -509,11 +509,11 @@ int run_direct_batch(lws_plan *p, const float2 *in_dev, float2 *out_dev, int B, 
     if (p->ev_after_load) HIP_TRY(hipEventRecord(p->ev_after_load, s));
     int launches = 0;
     const float *th = static_cast<const float *>(p->thr_scaled.p);
-    e = p->sysb->io_run(p->sys, st.wsel, th, in_dev, out_dev, partial, B, T, st.iters, s, &launches, p->ev0, p->ev1);
+    e = lws::systolic_io_run(*p->sysb, p->sys, st.wsel, th, in_dev, out_dev, partial, B, T, st.iters, s, &launches, p->ev0, p->ev1);
     p->timing_pending = true;
     if (e != hipSuccess) return fail(LWS_ERR_HIP, "systolic launch failed: %s", hipGetErrorString(e));
     p->last_launches = launches;
-    p->last_name = p->sysb->name(p->sys);
+    p->last_name = lws::systolic_name(p->sys);
     return LWS_OK;
 }
 
@@ -574,7 +574,7 @@ int need_weights(const lws_plan *p, const StageSpec *st, int n) {
 
 // After a synchronisation point: did a multi-workgroup systolic launch give up waiting (workgroups of one spectrogram
 // not co-scheduled, e.g. the device was shared)?  Not an error: the call was then re-run on the device with one
-// workgroup per spectrogram before it completed (lws_systolic.hip: run_kernel); the kernel name says so.
+// workgroup per spectrogram before it completed (lws_systolic_driver.hip: run_kernel); the kernel name says so.
 int check_systolic_flag(lws_plan *p) {
     for (lws::SystolicPlan *sp : {&p->sys}) {
         if (sp->last_nwg > 1 && sp->err_dev) {
@@ -1145,7 +1145,7 @@ int lws_plan_create(lws_plan **plan, int device, int F, int L, int Q, int Qp, co
             // twiddle) would leave the batch stage on the generic engine
             const int first = p->have[0] ? 0 : (p->have[1] ? 1 : 2);
             if (p->sys.ok[first]) { p->sysb = b; break; }
-            if (p->sys.ok[0] || p->sys.ok[1] || p->sys.ok[2]) b->release(p->sys);
+            if (p->sys.ok[0] || p->sys.ok[1] || p->sys.ok[2]) lws::systolic_release(p->sys);
         }
         if (e != hipSuccess) rc = fail(LWS_ERR_HIP, "systolic table upload failed: %s", hipGetErrorString(e));
     }
@@ -1168,7 +1168,7 @@ void lws_plan_destroy(lws_plan *p) {
     p->pipe.release();
     delete static_cast<HostWorkers *>(p->host_pool);
     p->host_pool = nullptr;
-    (p->sysb ? p->sysb : &lws::systolic_entry())->release(p->sys);
+    lws::systolic_release(p->sys);
     if (p->ev_busy) (void)hipEventDestroy(p->ev_busy);
     if (p->ev0) (void)hipEventDestroy(p->ev0);
     if (p->ev1) (void)hipEventDestroy(p->ev1);
@@ -1274,9 +1274,9 @@ int lws_plan_reserve(lws_plan *p, int B, int T, int max_iters) {
     if ((rc = p->resid_out.ensure((size_t)B * 2 * sizeof(double)))) return rc;
     if (!p->fp64) {
         if (p->sysb) {
-            const size_t n_part = p->sysb->io_partials(p->sys, T);
+            const size_t n_part = lws::systolic_io_partials(*p->sysb, p->sys, T);
             if ((rc = p->row_sums.ensure((size_t)B * (n_part > (size_t)T ? n_part : (size_t)T) * sizeof(double)))) return rc;
-            hipError_t e = p->sysb->reserve(p->sys, B, T, max_iters);
+            hipError_t e = lws::systolic_reserve(*p->sysb, p->sys, B, T, max_iters);
             if (e != hipSuccess) return fail(LWS_ERR_NOMEM, "systolic scratch: %s", hipGetErrorString(e));
         }
     }

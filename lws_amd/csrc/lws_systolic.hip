@@ -32,7 +32,9 @@
 // edge reads its image taps there.  The Nyquist bin (bin F-1) does not fit the 512-step frame period and is
 // computed by the service wave (one lane per sweep in flight), which also runs the loader.
 //
-// Scope of this file (one source, one build per row of lws_systolic_builds.h: the switches below): weights with the twiddle structure create_weights produces
+// This file is what a BUILD of the engine is -- its constants, the update kernel k_systolic, the packing of a weight tensor and the choice
+// of the kernel's instantiation; the layout passes and the host side of a call are the same for every build and live in
+// lws_systolic_layout.h / lws_systolic_driver.hip.  Scope (one source, one build per row of lws_systolic_builds.h: the switches below): weights with the twiddle structure create_weights produces
 // (lws.pyx:160-181: W[p][r][k] = W[0][r][k] exp(2j pi p r s / P), summarised or general tensors), fp32 arithmetic, fp32 or fp16
 // storage, F-1 even (a multiple of 8, or a frame end inside a block of 8 steps: one instantiation per phase, th0) and >= 16:
 //   static twiddles (P = Q, s = 1): Q in {2,4}, L <= 5, F-1 <= 512 (narrow; half / quarter: <= 256 / 128 with 2 / 4 sweep slots
@@ -45,12 +47,10 @@
 // lws_capi.hip's choose_engine (band, sys64 for fp64 plans, the generic engine).
 #include "lws_common.h"
 #include "lws_systolic.h"
+#include "lws_systolic_store.h"
 
-#include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 #include <utility>
@@ -168,7 +168,6 @@ constexpr int NSLOTS = LWS_NSLOTS;                       // sweeps in flight (co
 constexpr int NSETS = NSLOTS + 1;
 constexpr int NYQ_OFF = NSETS * SET_BYTES;               // Nyquist values: [set][lane] float2
 constexpr int THR_OFF = NYQ_OFF + NSETS * SLOT_BYTES;    // effective thresholds: floats
-constexpr int MAX_ITERS = 440;                           // sweeps of one launch (their thresholds live in LDS); longer schedules run as several launches
 constexpr int META_OFF = THR_OFF + MAX_ITERS * 4;        // n_eff
 constexpr int DONE_OFF = META_OFF + 16;               // per-wave count of completed steps (flow control)
 constexpr int DUMMY_OFF = DONE_OFF + 64;               // 64 x 8 B: where predicated-off lanes park their conditional writes
@@ -337,41 +336,7 @@ __device__ __forceinline__ v4f lds_read128(int addr) {
 }
 __device__ __forceinline__ float2 cj(float2 v) { return make_float2(v.x, -v.y); }
 
-// ---- storage formats of the skewed HBM layout --------------------------------------------------------------------
-// H16 = false: float2 state, float magnitudes (20 B per active bin and sweep).  H16 = true (LWS_STORAGE_FP16): half2 state
-// and half magnitudes (10 B), both multiplied by store_scale(largest magnitude of the spectrogram), a power of two that
-// brings the data to [0, 2): exact, and the whole kernel then works in that scaled domain (its thresholds are scaled the
-// same way; the weighted sums are only ever normalised, so nothing else changes).  Arithmetic and the LDS rings are fp32
-// in both formats; the rounding to half happens once per pass over HBM (NSLOTS sweeps).
-typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-__host__ __device__ __forceinline__ float store_scale(float amax) {
-    unsigned b;
-    __builtin_memcpy(&b, &amax, 4);
-    const unsigned e = (b >> 23) & 0xffu;
-    const unsigned sb = (e == 0u || e == 0xffu) ? 0x3f800000u : ((e >= 254u ? 1u : 254u - e) << 23);
-    float sc;
-    __builtin_memcpy(&sc, &sb, 4);
-    return sc;
-}
-__device__ __forceinline__ float2 unpack_h2(unsigned u) {
-    const h2_t h = __builtin_bit_cast(h2_t, u);
-    return make_float2((float)h.x, (float)h.y);
-}
-__device__ __forceinline__ unsigned pack_h2(float2 v) {   // round to nearest even
-    const h2_t h = {(_Float16)v.x, (_Float16)v.y};
-    return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ float unpack_h(unsigned short u) { return (float)__builtin_bit_cast(_Float16, u); }
-__device__ __forceinline__ unsigned short pack_h(float v) { return __builtin_bit_cast(unsigned short, (_Float16)v); }
-template <bool H16> struct Store {
-    using cplx = float2; using real = float;
-    static constexpr int CB = 8, RB = 4;
-};
-template <> struct Store<true> {
-    using cplx = unsigned; using real = unsigned short;
-    static constexpr int CB = 4, RB = 2;
-};
-
+// (the storage formats of the skewed HBM layout, Store<H16> and its conversions: lws_systolic_store.h)
 // A complex value as it travels from the global load to its use one block later: the raw bits (a conversion at the load
 // would wait for it there and then).
 template <bool H16> __device__ __forceinline__ float2 raw_value(float2 raw) { return H16 ? unpack_h2(__float_as_uint(raw.x)) : raw; }
@@ -2044,389 +2009,17 @@ __global__ void __launch_bounds__(NTHREADS, (NTHREADS + 255) / 256) k_systolic(S
 #endif
 }
 
-// ---------------------------------------------------------------------------------------------
-// layout conversion: reference extended layout <-> time-skewed layout
-// ---------------------------------------------------------------------------------------------
-// Both directions move 64 x 64 tiles (64 frames of one lane round x 64 production times) through LDS: in the reference
-// layout a frame's bins are contiguous, in the skewed layout the 64 lanes of a time step are, so the tile is read along
-// one and written along the other and both sides of the copy are full 512-byte segments.
-// grid: (Kt * NT, B) with Kt = ceil(Tp / 64) groups of 64 frames and NT = ceil((SKEW*63 + C) / 64) time tiles per group;
-// 256 threads.  Frame me sits in column me mod ROWL of the rows (SKEW*me + c) mod G: with two waves per sweep slot
-// (wide build) a ring row, hence a row of the layout, is 128 frames wide and two groups of 64 frames share its rows.
-//
-// fp16 storage (H16): the values are stored multiplied by store_scale(largest magnitude), so that magnitude has to be
-// known before the first store -- a reduction pass of its own (k_amax_*) instead of the atomic maximum the fp32 kernels
-// take on the way.  On the way out the state only contributes its PHASE: a bin that some sweep could have updated is
-// returned with the fp32 target magnitude it was given (the caller's |S|), a bin no sweep could touch keeps the caller's
-// value bit for bit; so fp16 storage costs phase accuracy, never magnitude accuracy.
-constexpr int TILE = 64, TPAD = TILE + 1;
-
-// |S| of a complex64 input exactly as k_prep forms it (fp64 square root, rounded once)
-__device__ __forceinline__ float mag_of(float2 v, double *mag64 = nullptr) {
-    const double m = sqrt((double)v.x * (double)v.x + (double)v.y * (double)v.y);
-    if (mag64) *mag64 = m;
-    return (float)m;
-}
-
-// largest magnitude of the real frames of each spectrogram; grid (blocks, B)
-__global__ void __launch_bounds__(256) k_amax_in(const float2 *in, unsigned *amax_bits, size_t n_per) {
-    __shared__ float red[256];
-    const float2 *p = in + (size_t)blockIdx.y * n_per;
-    float mx = 0.f;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n_per; i += (size_t)gridDim.x * 256) mx = fmaxf(mx, mag_of(p[i]));
-    red[threadIdx.x] = mx;
-    __syncthreads();
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-        if (threadIdx.x < s2) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s2]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && red[0] > 0.f) atomicMax(amax_bits + blockIdx.y, __float_as_uint(red[0]));
-}
-// the same from the extended magnitude buffer [B][Tp][Np] (real frames only; the pad columns repeat real bins)
-__global__ void __launch_bounds__(256) k_amax_ext(const float *amp, unsigned *amax_bits, int T, int Np, int Q) {
-    __shared__ float red[256];
-    const int Tp = T + 2 * (Q - 1);
-    const float *p = amp + ((size_t)blockIdx.y * Tp + (Q - 1)) * Np;
-    const size_t n_per = (size_t)T * Np;
-    float mx = 0.f;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n_per; i += (size_t)gridDim.x * 256) mx = fmaxf(mx, p[i]);
-    red[threadIdx.x] = mx;
-    __syncthreads();
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-        if (threadIdx.x < s2) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s2]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && red[0] > 0.f) atomicMax(amax_bits + blockIdx.y, __float_as_uint(red[0]));
-}
-// smallest threshold of each spectrogram that any of its bins exceeds (+inf if none): a bin whose stored magnitude is not
-// above it is never updated by this call
-__global__ void __launch_bounds__(64) k_thr_min(const float *thr, const float *amax, int n_iters, float *thr_min) {
-    const int b = blockIdx.x;
-    float m = __builtin_inff();
-    for (int i = threadIdx.x; i < n_iters; i += 64) {
-        const float th = thr[(size_t)b * n_iters + i];
-        if (amax[b] > th) m = fminf(m, th);
-    }
-    for (int o = 32; o > 0; o >>= 1) m = fminf(m, __shfl_xor(m, o));
-    if (threadIdx.x == 0) thr_min[b] = m;
-}
-// fp16 storage: could any sweep of the call have updated a bin of fp32 magnitude `a`?  (the kernel's own test, on the stored
-// half value in the scaled domain)
-__device__ __forceinline__ bool ever_active_h16(float a, float sc, float thr_min) { return unpack_h(pack_h(a * sc)) > thr_min * sc; }
-// fp16 storage: phase of the stored value v, magnitude a
-__device__ __forceinline__ float2 with_magnitude(float2 v, float a, bool *ok) {
-    const float m2 = v.x * v.x + v.y * v.y;
-    *ok = m2 > 0.f;
-    const float s = a / sqrtf(m2);
-    return make_float2(v.x * s, v.y * s);
-}
-
-template <bool H16>
-__global__ void __launch_bounds__(256) k_to_skew(const float2 *state, const float *amp, void *state_w_, void *amp_w_,
-                                                  void *state_nyq_, void *amp_nyq_, unsigned *amax_bits, int T, int F,
-                                                  int L, int Q, int G, int TpPad, int NT, const int *gate) {
-    using ST = Store<H16>;
-    __shared__ float2 ts[TILE][TPAD];
-    __shared__ float ta[TILE][TPAD];
-    __shared__ float red[256];
-    if (gate != nullptr && *gate == 0) return;
-    const int kk = blockIdx.x / NT, tt = blockIdx.x - kk * NT, b = blockIdx.y;
-    const int Np = F + 2 * L, Tp = T + 2 * (Q - 1), C = F - 1;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int tau0 = SKEW * LANES * kk + TILE * tt;          // first production time of the tile (before the mod G)
-    typename ST::cplx *sw = static_cast<typename ST::cplx *>(state_w_) + (size_t)b * G * ROWL;
-    typename ST::real *aw = static_cast<typename ST::real *>(amp_w_) + (size_t)b * G * ROWL;
-    typename ST::cplx *snq = static_cast<typename ST::cplx *>(state_nyq_) + (size_t)b * TpPad;
-    typename ST::real *anq = static_cast<typename ST::real *>(amp_nyq_) + (size_t)b * TpPad;
-    const float sc = H16 ? store_scale(__uint_as_float(amax_bits[b])) : 1.f;   // (H16: k_amax_ext ran before)
-    float mx = 0.f;
-    float2 vin[TILE / 4];
-    float ain[TILE / 4];
-#pragma unroll
-    for (int i = 0; i < TILE / 4; ++i) {                     // one frame per wave: 64 consecutive bins; all loads first
-        const int ml = wave + 4 * i;
-        const int me = LANES * kk + ml, c = tau0 + lane - SKEW * me;   // tile column = production time - tau0
-        const bool in_range = me < Tp && c >= 0 && c < C;
-        const size_t idx = ((size_t)b * Tp + me) * Np + L + c;
-        vin[i] = in_range ? state[idx] : make_float2(0.f, 0.f);
-        ain[i] = in_range ? amp[idx] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < TILE / 4; ++i) {
-        const int ml = wave + 4 * i;
-        const int me = LANES * kk + ml;
-        if (me >= Q - 1 && me < T + Q - 1) mx = fmaxf(mx, ain[i]);
-        ts[ml][lane] = vin[i];
-        ta[ml][lane] = ain[i];
-    }
-    if (tt == 0 && wave == 0) {                              // Nyquist bins of the round's frames
-        const int me = LANES * kk + lane;
-        if (me < Tp) {
-            const size_t i = ((size_t)b * Tp + me) * Np + L + C;
-            const float av = amp[i];
-            const float2 v = state[i];
-            if constexpr (H16) { snq[me] = pack_h2(make_float2(v.x * sc, v.y * sc)); anq[me] = pack_h(av * sc); }
-            else { snq[me] = v; anq[me] = av; }
-            if (me >= Q - 1 && me < T + Q - 1) mx = fmaxf(mx, av);
-        }
-    }
-    __syncthreads();
-    for (int tl = wave; tl < TILE; tl += 4) {                // one production time per wave: 64 consecutive lanes
-        const int me = LANES * kk + lane, c = tau0 + tl - SKEW * me;
-        if (me < Tp && c >= 0 && c < C) {
-            const size_t idx = (size_t)((tau0 + tl) % G) * ROWL + (me & (ROWL - 1));
-            const float2 v = ts[lane][tl];
-            if constexpr (H16) { sw[idx] = pack_h2(make_float2(v.x * sc, v.y * sc)); aw[idx] = pack_h(ta[lane][tl] * sc); }
-            else { sw[idx] = v; aw[idx] = ta[lane][tl]; }
-        }
-    }
-    if constexpr (!H16) {
-        // block max -> atomic max on the bit pattern (non-negative floats order like unsigned ints)
-        red[threadIdx.x] = mx;
-        __syncthreads();
-        for (int s2 = 128; s2 > 0; s2 >>= 1) {
-            if (threadIdx.x < s2) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s2]);
-            __syncthreads();
-        }
-        if (threadIdx.x == 0 && red[0] > 0.f) atomicMax(amax_bits + b, __float_as_uint(red[0]));
-    }
-}
-
-// Also restores the Hermitian pad columns and the Nyquist column of the extended layout.
-template <bool H16>
-__global__ void __launch_bounds__(256) k_from_skew(float2 *state, const float *amp, const void *state_w_, const void *state_nyq_,
-                                                    const float *amax, const float *thr_min, int T, int F, int L, int Q, int G,
-                                                    int TpPad, int NT) {
-    using ST = Store<H16>;
-    __shared__ float2 ts[TILE][TPAD];
-    const int kk = blockIdx.x / NT, tt = blockIdx.x - kk * NT, b = blockIdx.y;
-    const int Np = F + 2 * L, Tp = T + 2 * (Q - 1), C = F - 1;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int tau0 = SKEW * LANES * kk + TILE * tt;
-    const typename ST::cplx *sw = static_cast<const typename ST::cplx *>(state_w_) + (size_t)b * G * ROWL;
-    const typename ST::cplx *snq = static_cast<const typename ST::cplx *>(state_nyq_) + (size_t)b * TpPad;
-    const float sc = H16 ? store_scale(amax[b]) : 1.f, tmin = H16 ? thr_min[b] : 0.f;
-    float2 vin[TILE / 4];
-#pragma unroll
-    for (int i = 0; i < TILE / 4; ++i) {           // all loads first
-        const int tl = wave + 4 * i;
-        const int me = LANES * kk + lane, c = tau0 + tl - SKEW * me;
-        const bool in_range = me < Tp && c >= 0 && c < C;
-        if constexpr (H16) vin[i] = in_range ? unpack_h2(sw[(size_t)((tau0 + tl) % G) * ROWL + (me & (ROWL - 1))]) : make_float2(0.f, 0.f);
-        else vin[i] = in_range ? sw[(size_t)((tau0 + tl) % G) * ROWL + (me & (ROWL - 1))] : make_float2(0.f, 0.f);
-    }
-#pragma unroll
-    for (int i = 0; i < TILE / 4; ++i) ts[lane][wave + 4 * i] = vin[i];
-    __syncthreads();
-    for (int ml = wave; ml < TILE; ml += 4) {
-        const int me = LANES * kk + ml, c = tau0 + lane - SKEW * me;
-        if (me < Tp && c >= 0 && c < C) {
-            float2 *orow = state + ((size_t)b * Tp + me) * Np;
-            float2 v = ts[ml][lane];
-            if constexpr (H16) {     // phase from the fp16 state, magnitude from the fp32 target; untouched bins stay as they are
-                const float a = amp[((size_t)b * Tp + me) * Np + L + c];
-                bool ok;
-                v = with_magnitude(v, a, &ok);
-                if (!(ok && me >= Q - 1 && me < T + Q - 1 && ever_active_h16(a, sc, tmin))) continue;
-            }
-            orow[L + c] = v;
-            const float2 vc = make_float2(v.x, -v.y);
-            if (c >= 1 && c <= L) orow[L - c] = vc;                 // image below DC
-            if (c >= C - L) orow[L + 2 * C - c] = vc;               // image above Nyquist
-        }
-    }
-    if (tt == 0 && wave == 0) {
-        const int me = LANES * kk + lane;
-        if (me < Tp) {
-            const size_t i = ((size_t)b * Tp + me) * Np + L + C;
-            if constexpr (H16) {
-                const float a = amp[i];
-                bool ok;
-                const float2 v = with_magnitude(unpack_h2(snq[me]), a, &ok);
-                if (ok && me >= Q - 1 && me < T + Q - 1 && ever_active_h16(a, sc, tmin)) state[i] = v;
-            } else {
-                state[i] = snq[me];
-            }
-        }
-    }
-}
-
-// The same two conversions straight from / to the caller's unpadded [B][T][F] complex64 spectrograms, for calls that
-// are one batch stage: what k_prep + k_to_skew and k_from_skew + k_extract do in two passes each.
-// partial: [B][tiles] sums of |S| over the real frames in fp64, one per tile (block), for mean|S|.
-template <bool H16>
-__global__ void __launch_bounds__(256) k_in_to_skew(const float2 *in, void *state_w_, void *amp_w_, void *state_nyq_,
-                                                     void *amp_nyq_, unsigned *amax_bits, double *partial, int T, int F,
-                                                     int Q, int G, int TpPad, int NT, const int *gate) {
-    using ST = Store<H16>;
-    __shared__ float2 ts[TILE][TPAD];
-    __shared__ float ta[TILE][TPAD];
-    __shared__ float red[256];
-    __shared__ double dred[256];
-    if (gate != nullptr && *gate == 0) return;
-    const int kk = blockIdx.x / NT, tt = blockIdx.x - kk * NT, b = blockIdx.y;
-    const int Tp = T + 2 * (Q - 1), C = F - 1;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int tau0 = SKEW * LANES * kk + TILE * tt;
-    typename ST::cplx *sw = static_cast<typename ST::cplx *>(state_w_) + (size_t)b * G * ROWL;
-    typename ST::real *aw = static_cast<typename ST::real *>(amp_w_) + (size_t)b * G * ROWL;
-    typename ST::cplx *snq = static_cast<typename ST::cplx *>(state_nyq_) + (size_t)b * TpPad;
-    typename ST::real *anq = static_cast<typename ST::real *>(amp_nyq_) + (size_t)b * TpPad;
-    const float sc = H16 ? store_scale(__uint_as_float(amax_bits[b])) : 1.f;   // (H16: k_amax_in ran before)
-    float mx = 0.f;
-    double msum = 0.0;                                       // this thread's share of sum |S| over the real frames
-    // all of a thread's loads are issued before the first one is used: 16 x 512 bytes in flight per wave
-    float2 vin[TILE / 4];
-#pragma unroll
-    for (int i = 0; i < TILE / 4; ++i) {
-        const int ml = wave + 4 * i;
-        const int me = LANES * kk + ml, c = tau0 + lane - SKEW * me;
-        int src = me - (Q - 1);                                  // edge-pad frames repeat the first / last frame
-        src = src < 0 ? 0 : (src > T - 1 ? T - 1 : src);
-        vin[i] = (me < Tp && c >= 0 && c < C) ? in[((size_t)b * T + src) * F + c] : make_float2(0.f, 0.f);
-    }
-#pragma unroll
-    for (int i = 0; i < TILE / 4; ++i) {
-        const int ml = wave + 4 * i;
-        const int me = LANES * kk + ml, c = tau0 + lane - SKEW * me;
-        const bool real_frame = me >= Q - 1 && me < T + Q - 1;
-        const float2 v = vin[i];
-        float av = 0.f;
-        if (me < Tp && c >= 0 && c < C) {
-            double mag;
-            av = mag_of(v, &mag);                                // as k_prep: |S| in fp64, then rounded
-            if (real_frame) { mx = fmaxf(mx, av); msum += mag; }
-        }
-        ts[ml][lane] = v;
-        ta[ml][lane] = av;
-    }
-    if (tt == 0 && wave == 0) {                                  // Nyquist bins of the round's frames
-        const int me = LANES * kk + lane;
-        if (me < Tp) {
-            int src = me - (Q - 1);
-            src = src < 0 ? 0 : (src > T - 1 ? T - 1 : src);
-            const float2 v = in[((size_t)b * T + src) * F + C];
-            double mag;
-            const float av = mag_of(v, &mag);
-            if constexpr (H16) { snq[me] = pack_h2(make_float2(v.x * sc, v.y * sc)); anq[me] = pack_h(av * sc); }
-            else { snq[me] = v; anq[me] = av; }
-            if (me >= Q - 1 && me < T + Q - 1) {
-                mx = fmaxf(mx, av);
-                msum += mag;
-            }
-        }
-    }
-    __syncthreads();
-    for (int tl = wave; tl < TILE; tl += 4) {
-        const int me = LANES * kk + lane, c = tau0 + tl - SKEW * me;
-        if (me < Tp && c >= 0 && c < C) {
-            const size_t idx = (size_t)((tau0 + tl) % G) * ROWL + (me & (ROWL - 1));
-            const float2 v = ts[lane][tl];
-            if constexpr (H16) { sw[idx] = pack_h2(make_float2(v.x * sc, v.y * sc)); aw[idx] = pack_h(ta[lane][tl] * sc); }
-            else { sw[idx] = v; aw[idx] = ta[lane][tl]; }
-        }
-    }
-    red[threadIdx.x] = mx;
-    dred[threadIdx.x] = msum;
-    __syncthreads();
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {               // fixed tree: deterministic
-        if (threadIdx.x < s2) {
-            red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s2]);
-            dred[threadIdx.x] += dred[threadIdx.x + s2];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (!H16 && red[0] > 0.f) atomicMax(amax_bits + b, __float_as_uint(red[0]));
-        partial[(size_t)b * gridDim.x + blockIdx.x] = dred[0];   // one partial sum per tile
-    }
-}
-
-// mean|S| of each spectrogram from the partial sums, fixed order
-__global__ void __launch_bounds__(256) k_mean_partials(const double *partial, double *mean_amp, int n, double denom) {
-    __shared__ double red[256];
-    const int b = blockIdx.x;
-    double acc = 0;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) acc += partial[(size_t)b * n + i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-        if (threadIdx.x < s2) red[threadIdx.x] += red[threadIdx.x + s2];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) mean_amp[b] = red[0] / denom;
-}
-
-// skewed layout -> unpadded [B][T][F] output (real frames only, no pad columns).  `in`: the caller's input (fp16 storage
-// only; may be the same buffer as `out`: every element is read and written by the same thread).
-template <bool H16>
-__global__ void __launch_bounds__(256) k_skew_to_out(float2 *out, const float2 *in, const void *state_w_, const void *state_nyq_,
-                                                      const float *amax, const float *thr_min, int T, int F, int Q, int G,
-                                                      int TpPad, int NT) {
-    using ST = Store<H16>;
-    __shared__ float2 ts[TILE][TPAD];
-    const int kk = blockIdx.x / NT, tt = blockIdx.x - kk * NT, b = blockIdx.y;
-    const int Tp = T + 2 * (Q - 1), C = F - 1;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int tau0 = SKEW * LANES * kk + TILE * tt;
-    const typename ST::cplx *sw = static_cast<const typename ST::cplx *>(state_w_) + (size_t)b * G * ROWL;
-    const typename ST::cplx *snq = static_cast<const typename ST::cplx *>(state_nyq_) + (size_t)b * TpPad;
-    const float sc = H16 ? store_scale(amax[b]) : 1.f, tmin = H16 ? thr_min[b] : 0.f;
-    float2 vin[TILE / 4];
-#pragma unroll
-    for (int i = 0; i < TILE / 4; ++i) {           // all loads first
-        const int tl = wave + 4 * i;
-        const int me = LANES * kk + lane, c = tau0 + tl - SKEW * me;
-        const bool in_range = me < Tp && c >= 0 && c < C;
-        if constexpr (H16) vin[i] = in_range ? unpack_h2(sw[(size_t)((tau0 + tl) % G) * ROWL + (me & (ROWL - 1))]) : make_float2(0.f, 0.f);
-        else vin[i] = in_range ? sw[(size_t)((tau0 + tl) % G) * ROWL + (me & (ROWL - 1))] : make_float2(0.f, 0.f);
-    }
-#pragma unroll
-    for (int i = 0; i < TILE / 4; ++i) ts[lane][wave + 4 * i] = vin[i];
-    __syncthreads();
-    for (int ml = wave; ml < TILE; ml += 4) {
-        const int me = LANES * kk + ml, c = tau0 + lane - SKEW * me;
-        if (me >= Q - 1 && me < T + Q - 1 && c >= 0 && c < C) {
-            const size_t o = ((size_t)b * T + (me - (Q - 1))) * F + c;
-            if constexpr (H16) {
-                const float2 orig = in[o];
-                const float a = mag_of(orig);
-                bool ok;
-                const float2 v = with_magnitude(ts[ml][lane], a, &ok);
-                out[o] = (ok && ever_active_h16(a, sc, tmin)) ? v : orig;
-            } else {
-                out[o] = ts[ml][lane];
-            }
-        }
-    }
-    if (tt == 0 && wave == 0) {
-        const int me = LANES * kk + lane;
-        if (me >= Q - 1 && me < T + Q - 1) {
-            const size_t o = ((size_t)b * T + (me - (Q - 1))) * F + C;
-            if constexpr (H16) {
-                const float2 orig = in[o];
-                const float a = mag_of(orig);
-                bool ok;
-                const float2 v = with_magnitude(unpack_h2(snq[me]), a, &ok);
-                out[o] = (ok && ever_active_h16(a, sc, tmin)) ? v : orig;
-            } else {
-                out[o] = snq[me];
-            }
-        }
-    }
-}
-
 constexpr uint64_t mask_all(int Q, int L) { return (1ull << (Q * (L + 1))) - 1ull; }
 
 template <int Q, int L, uint64_t MASK, bool MULTI, bool H16, int RE> hipError_t launch_km(const SysArgs &a, int grid, hipStream_t s) {
     const hipError_t e = lws::allow_dynamic_lds<&k_systolic<Q, L, MASK, MULTI, H16, RE>>(LDS_BYTES);
     if (e != hipSuccess) return e;
     if constexpr (MULTI) {
-        // The workgroups of a spectrogram wait for each other: all of the grid must be resident at once.  prepare() sizes the
+        // The workgroups of a spectrogram wait for each other: all of the grid must be resident at once.  systolic_geometry() sizes the
         // grid to at most one workgroup per CU; here the other half of that argument is checked against the runtime's own
         // occupancy figure for this very kernel (once per kernel and process): a grid it cannot hold is refused, not launched.
         // (What no query sees -- a device shared with another process -- is covered by the hand-over time-out and the
-        // device-side re-run with one workgroup per spectrogram, run_kernel.)
+        // device-side re-run with one workgroup per spectrogram: run_kernel, lws_systolic_driver.hip.)
         static std::atomic<int> per_cu[64];             // per device (zero-initialised: 0 = not asked yet, else figure + 1)
         int dev = 0, n_cu = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return hipErrorUnknown;
@@ -2474,23 +2067,11 @@ constexpr uint64_t MASK_Q4_L5_DEFAULT = 0b111111'010111'111111'000011u;  // (r=3
 constexpr uint64_t MASK_Q2_L5_DEFAULT = 0b010111'000011u;                            // r=0:{0,1} r=1:{0,1,2,4}
 #endif
 
-struct Tables {
-    int Q, L;
-    uint64_t mask;
-    bool k0real, r13;  // structure the kernels can exploit (FLAG_K0REAL / FLAG_R13)
-    // W[p][r][k] = W[0][r][k] exp(2 pi j p r tw_s / tw_P); LWS_TW: the table of the kernel on the device
-    // (these fields sit at the same offsets in every build of this file -- w[] below does not have the same length in all)
-    int tw_P = 0, tw_s = 0;
-    float *tw_dev = nullptr;
-    float tw_nyq[16] = {0};  // tau_r(F-1), r = 0..7
-    float w[2 * NW];   // (re, im) in the order of SysArgs::w
-};
-
-}  // namespace
-
 // =============================================================================================
-// host side
+// host side: what is this build's own (the rest of a call: lws_systolic_driver.hip)
 // =============================================================================================
+static_assert(NW <= SYSTOLIC_NW_MAX, "SystolicTables::w");
+
 hipError_t systolic_build(SystolicPlan &sp, int F, int Lu, int Q, int Qp, const double *const W[3], const WeightStructure ws[3], bool fp16_storage) {
     // Lu: the caller's stencil half-width (its weight tensors have Lu + 1 columns, its extended buffers 2 Lu pad columns);
     // L: that of the kernel build -- the next odd number, the extra tap with weight zero (its mask bit is clear: never fetched)
@@ -2541,7 +2122,7 @@ hipError_t systolic_build(SystolicPlan &sp, int F, int Lu, int Q, int Qp, const 
         // the static builds: the twiddle of a bin is exp(2 pi j (bin mod Q) r / Q), compiled into the unrolled step loop
         if (twP != Q || twS != 1) continue;
 #endif
-        Tables *tb = new Tables();
+        SystolicTables *tb = new SystolicTables();
         tb->Q = Q; tb->L = L; tb->mask = 0;
         tb->tw_P = twP; tb->tw_s = twS;
 #if LWS_TW
@@ -2606,131 +2187,10 @@ hipError_t systolic_build(SystolicPlan &sp, int F, int Lu, int Q, int Qp, const 
     return hipSuccess;
 }
 
-void systolic_release(SystolicPlan &sp) {
-    for (int i = 0; i < 3; ++i) {
-        if (sp.tables[i] && static_cast<Tables *>(sp.tables[i])->tw_dev) (void)hipFree(static_cast<Tables *>(sp.tables[i])->tw_dev);
-        delete static_cast<Tables *>(sp.tables[i]);
-        sp.tables[i] = nullptr;
-        sp.ok[i] = false;
-    }
-    if (sp.sk_state) (void)hipFree(sp.sk_state);
-    if (sp.sk_amp) (void)hipFree(sp.sk_amp);
-    if (sp.thr_chunk) (void)hipFree(sp.thr_chunk);
-    sp.sk_state = sp.sk_amp = sp.thr_chunk = nullptr;
-    sp.sk_state_cap = sp.sk_amp_cap = sp.thr_chunk_cap = 0;
-}
-
-bool systolic_supports(const SystolicPlan &sp, int wsel, int T) {
-    return wsel >= 0 && wsel < 3 && sp.ok[wsel] && T >= 1;  // (any number of sweeps: more than MAX_ITERS run as several launches)
-}
-
-const char *systolic_name(const SystolicPlan &sp) { return sp.name; }
-
-namespace {
-
-// Shapes and scratch pointers of one call.
-struct Geom {
-    int Tp, Kr, Kt, G, TpPad, NT, nwg;   // Kr: rounds of ROWL frames (the kernel's clock); Kt: groups of 64 frames (layout tiles)
-    int n_full, nwg_rest;   // batches larger than the chip: n_full spectrograms with one workgroup each, then the rest
-                            // (B - n_full, fewer than there are CUs) with nwg_rest workgroups each
-    int cb, rb;             // bytes per stored complex value / magnitude (Store<H16>)
-    char *state_w, *state_nyq;
-    char *amp_w, *amp_nyq;
-    unsigned *amax_bits, *progress;
-    float *thr_min;
-    int *err;
-};
-
-// dense threshold table of one launch of a schedule longer than MAX_ITERS sweeps (a synchronising hipMalloc when it grows)
-hipError_t ensure_thr_chunk(SystolicPlan &sp, int B, int iters) {
-    const size_t need = (size_t)B * MAX_ITERS * sizeof(float);
-    if (iters <= MAX_ITERS || (sp.thr_chunk && sp.thr_chunk_cap >= need)) return hipSuccess;
-    if (sp.thr_chunk) (void)hipFree(sp.thr_chunk);
-    sp.thr_chunk = nullptr; sp.thr_chunk_cap = 0;
-    hipError_t e = hipMalloc(&sp.thr_chunk, need);
-    if (e == hipSuccess) sp.thr_chunk_cap = need;
-    return e;
-}
-
-// (grows the plan's scratch if needed -- a synchronising hipMalloc; systolic_reserve() does that ahead of time)
-hipError_t prepare(SystolicPlan &sp, int B, int T, int iters, Geom &g) {
-    const int Q = sp.Q, F = sp.F;
-    g.cb = sp.h16 ? Store<true>::CB : Store<false>::CB;
-    g.rb = sp.h16 ? Store<true>::RB : Store<false>::RB;
-    g.Tp = T + 2 * (Q - 1);
-    // rounds of ROWL frames per pass; at least so many that a pass (G rows) is longer than the lag of the last sweep slot behind
-    // the loader plus what the loader reads ahead: pass g+1 follows pass g on the same clock and reads the rows pass g's last
-    // slot has written (only the short-frame builds, with their 14 / 24 slots and short rounds, ever need the padding)
-    constexpr int KR_MIN = (NSLOTS * LAG + 96 + ROWP - 1) / ROWP;
-    g.Kr = std::max((g.Tp + ROWL - 1) / ROWL, KR_MIN);
-    g.Kt = (g.Tp + LANES - 1) / LANES;
-    g.G = ROWP * g.Kr;
-    g.TpPad = (g.Tp + 63) & ~63;
-    g.NT = (SKEW * (LANES - 1) + (F - 1) + TILE - 1) / TILE;   // time tiles per round of 64 frames
-    // scratch: state_w, state_nyq | amp_w, amp_nyq, amax, smallest threshold, progress counters, error flag
-    const size_t n_w = (size_t)B * g.G * ROWL, n_n = (size_t)B * g.TpPad;
-    const size_t need_s = (n_w + n_n) * g.cb;
-    hipError_t e;
-    // workgroups per spectrogram: as many as there are CUs to keep busy and passes to share out; every workgroup must
-    // be resident (they wait for each other), which one workgroup per CU (the rings fill the LDS) and a grid no larger
-    // than the CU count guarantee on a device this process has to itself; if they are not (a shared or partitioned
-    // device), the hand-over times out and the call is re-run with one workgroup per spectrogram (run_kernel)
-    int n_cu = 0, dev = 0;
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-    if ((e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-    const int n_pass_max = ((iters < MAX_ITERS ? iters : MAX_ITERS) + NSLOTS - 1) / NSLOTS;
-    // each workgroup trails its producer by NSLOTS*LAG + 56 rows, and the first one starts its next pass G rows after
-    // its previous one: the lags around the ring must fit into one pass
-    const int ring_max = g.G / (NSLOTS * LAG + 96);
-    const int forced = sp.sw->systolic_nwg;
-    auto pick = [&](int nb) {
-        int n = nb > 0 ? n_cu / nb : 1;
-        if (n > n_pass_max) n = n_pass_max;
-        if (forced >= 1 && (long)forced * nb <= n_cu) n = forced;
-        if (n > ring_max) n = ring_max;
-        return n < 1 ? 1 : n;
-    };
-    const int nwg = pick(B);
-    g.nwg = nwg;
-    // a batch that does not fill the last round of workgroups: the spectrograms of that round share the idle CUs
-    g.n_full = B; g.nwg_rest = 1;
-    if (nwg == 1 && B > n_cu && B % n_cu != 0 && pick(B % n_cu) > 1) { g.n_full = B - B % n_cu; g.nwg_rest = pick(B % n_cu); }
-    // sized for the largest number of workgroups any iteration count can give this batch, so that the scratch of a shape
-    // does not grow with the schedule
-    const size_t n_prog = ((size_t)B * (size_t)(n_cu / (B > 0 ? B : 1) + 1) + (size_t)n_cu) * WPS + 8;
-    const size_t amp_bytes = ((n_w + n_n) * g.rb + 15) & ~(size_t)15;
-    const size_t need_a = amp_bytes + (size_t)B * sizeof(unsigned) + (size_t)B * sizeof(float) + n_prog * sizeof(unsigned);
-    if (need_s > sp.sk_state_cap) {
-        if (sp.sk_state) (void)hipFree(sp.sk_state);
-        sp.sk_state = nullptr; sp.sk_state_cap = 0;
-        if ((e = hipMalloc(&sp.sk_state, need_s)) != hipSuccess) return e;
-        sp.sk_state_cap = need_s;
-    }
-    if (need_a > sp.sk_amp_cap) {
-        if (sp.sk_amp) (void)hipFree(sp.sk_amp);
-        sp.sk_amp = nullptr; sp.sk_amp_cap = 0;
-        if ((e = hipMalloc(&sp.sk_amp, need_a)) != hipSuccess) return e;
-        sp.sk_amp_cap = need_a;
-    }
-    g.state_w = static_cast<char *>(sp.sk_state);
-    g.state_nyq = g.state_w + n_w * g.cb;
-    g.amp_w = static_cast<char *>(sp.sk_amp);
-    g.amp_nyq = g.amp_w + n_w * g.rb;
-    g.amax_bits = reinterpret_cast<unsigned *>(g.amp_w + amp_bytes);
-    g.thr_min = reinterpret_cast<float *>(g.amax_bits + B);
-    g.progress = reinterpret_cast<unsigned *>(g.thr_min + B);
-    g.err = reinterpret_cast<int *>(g.progress + (n_prog - 1));
-    return hipSuccess;
-}
-
-hipError_t clear_flags(const Geom &g, int B, hipStream_t stream) {   // amax | thr_min | progress counters | error flag
-    return hipMemsetAsync(g.amax_bits, 0, reinterpret_cast<char *>(g.err + 1) - reinterpret_cast<char *>(g.amax_bits), stream);
-}
-
 // One launch of the update kernel over spectrograms [b0, b0 + nb) with `nwg` workgroups each: n_it sweeps.
-hipError_t launch_update(SystolicPlan &sp, const Geom &g, int wsel, const float *thr, int n_it, int b0, int nb, int nwg,
-                         unsigned *progress, const int *gate, int T, hipStream_t stream) {
-    const Tables *tb = static_cast<const Tables *>(sp.tables[wsel]);
+hipError_t launch_update(SystolicPlan &sp, const SystolicCall &g, int wsel, const float *thr, int n_it, int b0, int nb, int nwg,
+                         unsigned *progress, const int *gate, int T, hipStream_t stream, const char **kind_out) {
+    const SystolicTables *tb = static_cast<const SystolicTables *>(sp.tables[wsel]);
     const int Q = sp.Q, L = sp.Lk, F = sp.F;
     SysArgs a;
     a.state_w = g.state_w + (size_t)b0 * g.G * ROWL * g.cb; a.amp_w = g.amp_w + (size_t)b0 * g.G * ROWL * g.rb;
@@ -2808,176 +2268,17 @@ hipError_t launch_update(SystolicPlan &sp, const Geom &g, int wsel, const float 
         else e = launch_k<2, 5, mask_all(2, 5)>(a, grid, h, stream);
     }
 #endif
-    snprintf(sp.name_buf, sizeof sp.name_buf, "systolic%s_q%d_l%d_%s%s", LWS_NAME_TAG, Q, L, kind,
-             h ? "_f16" : "");
-    sp.name = sp.name_buf;
-    return e;
-}
-
-// All sweeps of a call, state in the skewed layout.  `reload(gate)` re-creates that layout from the caller's (still
-// untouched) data, as a launch that only runs if *gate != 0.
-template <typename Reload>
-hipError_t run_kernel(SystolicPlan &sp, const Geom &g, int wsel, const float *thr, int B, int T, int iters,
-                      hipStream_t stream, int *launches, Reload reload) {
-    hipError_t e = hipSuccess;
-    if (sp.h16) {
-        hipLaunchKernelGGL(k_thr_min, dim3(B), dim3(64), 0, stream, thr, reinterpret_cast<const float *>(g.amax_bits), iters, g.thr_min);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    if ((e = ensure_thr_chunk(sp, B, iters)) != hipSuccess) return e;
-    int n_launch = 0;
-    bool multi = false, refused0 = false, refused1 = false;
-    // every sweep of the call, either with the workgroup counts of `g` or (single) with one workgroup per spectrogram
-    auto sweep_all = [&](bool single, const int *gate) -> hipError_t {
-        // more sweeps than one launch's threshold table holds: several launches over the same (resident) skewed state.
-        // Same results: a launch boundary is just a longer lag between two sweeps.
-        for (int it0 = 0; it0 < iters; it0 += MAX_ITERS) {
-            const int n_it = iters - it0 < MAX_ITERS ? iters - it0 : MAX_ITERS;
-            const float *thr_c = thr;
-            if (iters > MAX_ITERS) {   // the kernel reads a dense [B][n_iters] table: this launch's columns, copied in stream order
-                if ((e = hipMemcpy2DAsync(sp.thr_chunk, (size_t)n_it * sizeof(float), thr + it0, (size_t)iters * sizeof(float),
-                                          (size_t)n_it * sizeof(float), B, hipMemcpyDeviceToDevice, stream)) != hipSuccess) return e;
-                thr_c = static_cast<const float *>(sp.thr_chunk);
-            }
-            for (int chunk = 0; chunk < (single ? 1 : 2); ++chunk) {
-                // chunk 0: the first n_full spectrograms (all of them unless the batch leaves a partial last round on the
-                // chip); chunk 1: the rest, with several workgroups per spectrogram
-                const int b0 = (single || chunk == 0) ? 0 : g.n_full;
-                const int nb = single ? B : (chunk == 0 ? g.n_full : B - g.n_full);
-                const int nwg = single ? 1 : (chunk == 0 ? g.nwg : g.nwg_rest);
-                if (nb <= 0) continue;
-                unsigned *progress = g.progress + (chunk == 0 ? 0 : (size_t)B * g.nwg * WPS);
-                if (nwg > 1 && n_launch > 0) {   // multi-workgroup launches re-use the counters: start them from zero again
-                    if ((e = hipMemsetAsync(progress, 0, (size_t)nb * nwg * WPS * sizeof(unsigned), stream)) != hipSuccess) return e;
-                }
-                e = launch_update(sp, g, wsel, thr_c, n_it, b0, nb, nwg, progress, gate, T, stream);
-                if (e == hipErrorLaunchOutOfResources && nwg > 1 && it0 == 0) {
-                    // the occupancy guard refused a grid of several workgroups per spectrogram (launch_km): nothing was launched for
-                    // these spectrograms -- serve them with one workgroup each (same results), here and in the launches that follow
-                    (void)hipGetLastError();
-                    if (chunk == 0) refused0 = true; else refused1 = true;
-                }
-                if ((chunk == 0 ? refused0 : refused1) && nwg > 1)
-                    e = launch_update(sp, g, wsel, thr_c, n_it, b0, nb, 1, progress, gate, T, stream);
-                else multi |= nwg > 1;
-                if (e != hipSuccess) return e;
-                if (!gate) ++n_launch;
-            }
-        }
-        return hipSuccess;
-    };
-    if ((e = sweep_all(false, nullptr)) != hipSuccess) return e;
-    if (multi) {
-        // Several workgroups per spectrogram hand rows over through HBM and need each other resident.  If one of them
-        // timed out (flag set), everything is done again with one workgroup per spectrogram, from the caller's data: the
-        // launches below are enqueued unconditionally and return at once unless the flag is set, so the call stays
-        // asynchronous and never returns the results of a failed hand-over.
-        if ((e = reload(g.err)) != hipSuccess) return e;
-        if ((e = sweep_all(true, g.err)) != hipSuccess) return e;
-    }
-    sp.err_dev = g.err; sp.last_nwg = multi ? (g.nwg > g.nwg_rest ? g.nwg : g.nwg_rest) : 1;
-    if (launches) *launches = n_launch;
+    *kind_out = kind;
     return e;
 }
 
 }  // namespace
-
-hipError_t systolic_reserve(SystolicPlan &sp, int B, int T, int iters) {
-    Geom g;
-    hipError_t e = prepare(sp, B, T, iters, g);
-    if (e != hipSuccess) return e;
-    return ensure_thr_chunk(sp, B, iters);   // (schedules longer than one launch's table: sized here, not in the first call)
-}
-
-hipError_t launch_systolic(SystolicPlan &sp, int wsel, float2 *state, const float *amp, const float *thr, int B,
-                           int T, int iters, hipStream_t stream, int *launches, hipEvent_t ev0, hipEvent_t ev1) {
-    Geom g;
-    hipError_t e;
-    if ((e = prepare(sp, B, T, iters, g)) != hipSuccess) return e;
-    if ((e = clear_flags(g, B, stream)) != hipSuccess) return e;
-    const int Q = sp.Q, L = sp.L, F = sp.F;
-    auto load = [&](const int *gate) {
-        if (sp.h16) {
-            if (!gate) hipLaunchKernelGGL(k_amax_ext, dim3(64, B), dim3(256), 0, stream, amp, g.amax_bits, T, F + 2 * L, Q);
-            hipLaunchKernelGGL(k_to_skew<true>, dim3(g.Kt * g.NT, B), dim3(256), 0, stream, state, amp, (void *)g.state_w, (void *)g.amp_w,
-                               (void *)g.state_nyq, (void *)g.amp_nyq, g.amax_bits, T, F, L, Q, g.G, g.TpPad, g.NT, gate);
-        } else {
-            hipLaunchKernelGGL(k_to_skew<false>, dim3(g.Kt * g.NT, B), dim3(256), 0, stream, state, amp, (void *)g.state_w, (void *)g.amp_w,
-                               (void *)g.state_nyq, (void *)g.amp_nyq, g.amax_bits, T, F, L, Q, g.G, g.TpPad, g.NT, gate);
-        }
-        return hipGetLastError();
-    };
-    if ((e = load(nullptr)) != hipSuccess) return e;
-    if (ev0) (void)hipEventRecord(ev0, stream);
-    if ((e = run_kernel(sp, g, wsel, thr, B, T, iters, stream, launches, load)) != hipSuccess) return e;
-    if (ev1) (void)hipEventRecord(ev1, stream);
-    const float *amax = reinterpret_cast<const float *>(g.amax_bits);
-    if (sp.h16)
-        hipLaunchKernelGGL(k_from_skew<true>, dim3(g.Kt * g.NT, B), dim3(256), 0, stream, state, amp, (const void *)g.state_w,
-                           (const void *)g.state_nyq, amax, (const float *)g.thr_min, T, F, L, Q, g.G, g.TpPad, g.NT);
-    else
-        hipLaunchKernelGGL(k_from_skew<false>, dim3(g.Kt * g.NT, B), dim3(256), 0, stream, state, amp, (const void *)g.state_w,
-                           (const void *)g.state_nyq, amax, (const float *)g.thr_min, T, F, L, Q, g.G, g.TpPad, g.NT);
-    return hipGetLastError();
-}
-
-// ---- a call that is one batch stage on the caller's unpadded complex64 spectrograms: no extended buffers at all
-namespace {
-size_t io_partials_n(int F, int T, int Q) {            // one partial sum per tile of k_in_to_skew
-    const int NT = (SKEW * (LANES - 1) + (F - 1) + TILE - 1) / TILE;
-    const int Tp = T + 2 * (Q - 1), Kt = (Tp + LANES - 1) / LANES;
-    return (size_t)Kt * NT;
-}
-hipError_t io_load(SystolicPlan &sp, const Geom &g, const float2 *in, int B, int T, double *partial, hipStream_t stream, const int *gate) {
-    if (sp.h16) {
-        if (!gate) hipLaunchKernelGGL(k_amax_in, dim3(64, B), dim3(256), 0, stream, in, g.amax_bits, (size_t)T * sp.F);
-        hipLaunchKernelGGL(k_in_to_skew<true>, dim3(g.Kt * g.NT, B), dim3(256), 0, stream, in, (void *)g.state_w, (void *)g.amp_w,
-                           (void *)g.state_nyq, (void *)g.amp_nyq, g.amax_bits, partial, T, sp.F, sp.Q, g.G, g.TpPad, g.NT, gate);
-    } else {
-        hipLaunchKernelGGL(k_in_to_skew<false>, dim3(g.Kt * g.NT, B), dim3(256), 0, stream, in, (void *)g.state_w, (void *)g.amp_w,
-                           (void *)g.state_nyq, (void *)g.amp_nyq, g.amax_bits, partial, T, sp.F, sp.Q, g.G, g.TpPad, g.NT, gate);
-    }
-    return hipGetLastError();
-}
-}  // namespace
-size_t systolic_io_partials(const SystolicPlan &sp, int T) { return io_partials_n(sp.F, T, sp.Q); }
-
-hipError_t systolic_io_load(SystolicPlan &sp, const float2 *in, int B, int T, int iters, double *partial, double *mean_amp,
-                            hipStream_t stream) {
-    Geom g;
-    hipError_t e;
-    if ((e = prepare(sp, B, T, iters, g)) != hipSuccess) return e;
-    if ((e = clear_flags(g, B, stream)) != hipSuccess) return e;
-    const size_t n = io_partials_n(sp.F, T, sp.Q);
-    if ((e = io_load(sp, g, in, B, T, partial, stream, nullptr)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_mean_partials, dim3(B), dim3(256), 0, stream, partial, mean_amp, (int)n, (double)T * (double)sp.F);
-    return hipGetLastError();
-}
-
-hipError_t systolic_io_run(SystolicPlan &sp, int wsel, const float *thr, const float2 *in, float2 *out, double *partial, int B, int T,
-                           int iters, hipStream_t stream, int *launches, hipEvent_t ev0, hipEvent_t ev1) {
-    Geom g;
-    hipError_t e;
-    if ((e = prepare(sp, B, T, iters, g)) != hipSuccess) return e;   // same shapes: no reallocation, same pointers
-    if (ev0) (void)hipEventRecord(ev0, stream);
-    auto reload = [&](const int *gate) { return io_load(sp, g, in, B, T, partial, stream, gate); };
-    if ((e = run_kernel(sp, g, wsel, thr, B, T, iters, stream, launches, reload)) != hipSuccess) return e;
-    if (ev1) (void)hipEventRecord(ev1, stream);
-    const float *amax = reinterpret_cast<const float *>(g.amax_bits);
-    if (sp.h16)
-        hipLaunchKernelGGL(k_skew_to_out<true>, dim3(g.Kt * g.NT, B), dim3(256), 0, stream, out, in, (const void *)g.state_w,
-                           (const void *)g.state_nyq, amax, (const float *)g.thr_min, T, sp.F, sp.Q, g.G, g.TpPad, g.NT);
-    else
-        hipLaunchKernelGGL(k_skew_to_out<false>, dim3(g.Kt * g.NT, B), dim3(256), 0, stream, out, in, (const void *)g.state_w,
-                           (const void *)g.state_nyq, amax, (const float *)g.thr_min, T, sp.F, sp.Q, g.G, g.TpPad, g.NT);
-    return hipGetLastError();
-}
 
 const SystolicBuild &systolic_entry() {
-    static const SystolicBuild b = {systolic_build, systolic_release, systolic_supports, systolic_reserve, systolic_name,
-                                    launch_systolic, systolic_io_partials, systolic_io_load, systolic_io_run,
+    static const SystolicBuild b = {{ROWL_SHIFT, SKEW, LAG, NSLOTS, WPS},
                                     (LWS_SPW != 1 ? SYSTOLIC_SHORT : 0u) | (LWS_TW ? SYSTOLIC_TW : 0u) | (LWS_TWQ ? SYSTOLIC_TWQ : 0u) |
-                                        (LWS_R16 ? SYSTOLIC_R16 : 0u)};
+                                        (LWS_R16 ? SYSTOLIC_R16 : 0u),
+                                    LWS_NAME_TAG, systolic_build, launch_update};
     return b;
 }
 

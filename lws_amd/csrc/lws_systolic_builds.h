@@ -1,6 +1,8 @@
 // lws_systolic_builds.h -- the builds of lws_systolic.hip, one row each.  Preprocessor only: lws_systolic.hip takes its switches from
 // the row that -DLWS_BUILD=<name> selects (none: narrow), lws_systolic.h declares one entry per row, lws_capi.hip walks them in order.
-// A new build is one row, its name in LWS_SYSTOLIC_BUILDS below and in SYSTOLIC_BUILDS of the Makefile (object lws_systolic_<name>.o).
+// A new build is one row, its name in LWS_SYSTOLIC_BUILDS below and in SYSTOLIC_BUILDS of the Makefile (object lws_systolic_<name>.o):
+// the layout passes and the host driver (lws_systolic_driver.hip, compiled once) take its row length, skew, lag, slots and waves per slot
+// as numbers, from its entry.
 //
 // The switches (what they mean: lws_systolic.hip) -- WIDE: 1 / 2 = two / four waves per sweep slot; Q8: 64-step ring, halo of 7, helper
 // waves; SPW: sweep slots per wave; L7: frames 16 steps apart; R16: 16-step ring; TW: twiddles from a table; TWQ: ring of 8 TWQ steps.

@@ -1,8 +1,8 @@
 """The fp16-complex storage mode (LWS_STORAGE_FP16) restated on the CPU: the oracle's fp64 sweeps with the state and
-the target magnitudes held as IEEE half between passes over HBM, exactly where lws_systolic.hip rounds them --
+the target magnitudes held as IEEE half between passes over HBM, exactly where the systolic engine (lws_systolic.hip, lws_systolic_layout.h) rounds them --
 
   * the spectrogram is multiplied by the power of two that brings its largest fp32 magnitude to [1, 2) (store_scale; exact);
-  * the input state and the target magnitudes are rounded to half once, on the way in (k_in_to_skew / k_to_skew: round to
+  * the input state and the target magnitudes are rounded to half once, on the way in (k_to_skew: round to
     nearest even); the thresholds (float32(thr_i * mean|S|), those the largest magnitude exceeds) are scaled the same way and
     compared with the HALF magnitudes, and a bin is re-projected onto its HALF magnitude;
   * `nslots` consecutive effective sweeps form one pass: the state stays in fp32 (LDS rings; here fp64) inside a pass and is
@@ -16,7 +16,7 @@ import numpy as np
 
 
 def store_scale(amax):
-    """2^(127 - biased exponent) of the float32 amax: what lws_systolic.hip:store_scale returns."""
+    """2^(127 - biased exponent) of the float32 amax: what lws_systolic_store.h:store_scale returns."""
     e = (np.float32(amax).view(np.uint32) >> 23) & 0xFF
     if e == 0 or e == 0xFF:
         return 1.0

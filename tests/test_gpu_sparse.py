@@ -79,7 +79,7 @@ def check_exact(out, S, A, ref, cfg, stage, plan_kw, base=None):
     iso = sc.isolated(A, Q, L, po)
     if plan_kw.get("storage") == "fp16":
         # fp16 storage hands back the PHASE of its half state on the caller's fp32 magnitude for every bin that some sweep of the call
-        # could have updated -- magnitude above the smallest threshold in effect, here 0 -- written or not (lws_systolic.hip, "fp16
+        # could have updated -- magnitude above the smallest threshold in effect, here 0 -- written or not (lws_systolic_layout.h, "fp16
         # storage"; bins below that threshold keep their bits: test_fp16_storage_keeps_the_bits_below_the_thresholds).  The state is
         # stored scaled by a power of two that brings the largest magnitude to [1, 2): each component is off by at most half an
         # ulp of that binade, 2^-11, times at most the largest magnitude; the two components together by sqrt(2) of that.
